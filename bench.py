@@ -10,6 +10,16 @@ PCM left in HBM (`value`; the PCIe-inclusive rate with the PCM copied to host me
 reported beside it as `value_pcie_inclusive`). Weights are synthetic (no checkpoints
 offline) with the published shapes; "data": "synthetic".
 
+A plain run (`--gpus 1 --steps K --warmup W`) does only what `value` needs: load, W warmup
+steps, the K timed steps, then the result line (`ms_per_step` = the timed region / K; the
+stage times, `llm_ms_per_token` and `codec_roofline` come from the timed steps themselves).
+`--dump-outputs DIR` adds the last timed step's outputs as DIR/tokens.npy (float64) and
+DIR/pcm.npy (float32) (`tokens_00.npy`, `pcm_00.npy`, ... with `--utts-per-gpu B`); prompt,
+weights and sampler seeds are fixed, so two builds can be compared output for output.
+`--full` adds everything described below that takes runs of its own: `value_pcie_inclusive`,
+`stage_ms.pcm_finish_ms`, `roofline`, `eos_tail`, `batched`, `cpu_baseline*` and
+`baseline_configs` (null or absent in a plain run).
+
 Multi-GPU (`--gpus N`): one process per GPU. Under torchrun (WORLD_SIZE set) this process
 is one rank; otherwise, for N > 1, it starts N fresh child processes of itself (RANK /
 LOCAL_RANK / WORLD_SIZE / MASTER_* set) BEFORE anything touches the GPU and exits with
@@ -71,6 +81,13 @@ def parse_args(argv=None):
     p.add_argument("--utts-per-gpu", type=int, default=1,
                    help="B > 1: each step decodes B utterances together per GPU (batched engine)")
     p.add_argument("--workdir", default=os.environ.get("MIOTTS_BENCH_DIR", "/tmp/miotts_bench"))
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also measure everything beside the headline figure: the PCM copy "
+                        "to host, the WAV epilogue, roofline, eos_tail, the batched line, the CPU baselines and "
+                        "the other BASELINE configs (each has its own --no-* / --batch 0 switch)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed (its sampled token ids and its PCM) as "
+                        "DIR/<name>.npy")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-tokens", type=int, default=64)
     p.add_argument("--no-cpu-c1", action="store_true", help="skip the C1 leg (0.1B Q8_0 CPU utterance)")
@@ -79,7 +96,7 @@ def parse_args(argv=None):
                    help="also time B utterances decoded together per GPU (N=1 only; 0 = skip)")
     p.add_argument("--no-roofline", action="store_true")
     p.add_argument("--no-configs", action="store_true",
-                   help="skip the other BASELINE config lines (C2, C4 on both 2.6B shapes, C5) a default N=1 run adds")
+                   help="skip the other BASELINE config lines (C2, C4 on both 2.6B shapes, C5) a --full N=1 run adds")
     p.add_argument("--launcher-selftest", action="store_true",
                    help="tests only: the launcher + timed region with a CPU sleep as the utterance, no GPU; "
                         "prints a 'launcher self-test' line, never the metric")
@@ -274,9 +291,33 @@ def make_batch_step(tokens, B, llm, codec, dev, prompt, allow, d_emb, d_pcm):
         lens = codec.decode_pcm_batch_device(d_codes, [len(t) for t in outs], d_emb, d_outs)
         c_ms, _ = codec.last_timings()
         dev.sync()
+        step.last = (outs, d_outs, lens)
         return sum(lens), t1 - t0, c_ms, 0.0
 
+    step.last = None
     return step
+
+
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(dirname, arrays, rank=0, max_bytes=DUMP_MAX_BYTES):
+    """--dump-outputs: `arrays` (name -> ndarray, what the last timed step handed its caller) as
+    DIR/<name>.npy (rank r > 0: DIR/<name>_rank<r>.npy), integers as float64 and floats as
+    float32. Past 64 MB in all, every array is cut to the same fixed share of its elements
+    (sorted indices drawn once from a generator seeded with 0, so two runs keep the same ones)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    conv = {k: np.ascontiguousarray(v, np.float32 if np.issubdtype(v.dtype, np.floating) else np.float64).ravel()
+            for k, v in arrays.items()}
+    total = sum(v.nbytes for v in conv.values())
+    keep = min(1.0, max_bytes / total) if total else 1.0
+    rng = np.random.default_rng(0)
+    for name in sorted(conv):
+        v = conv[name]
+        if keep < 1.0:
+            v = v[np.sort(rng.choice(v.size, int(v.size * keep), replace=False))]
+        np.save(os.path.join(dirname, name + (f"_rank{rank}" if rank else "") + ".npy"), v)
 
 
 def baseline_configs(a, llm_path, codec_path, voice_path):
@@ -481,6 +522,7 @@ def main():
 
     stage = {"llm_ms": 0.0, "codec_ms": 0.0, "istft_ms": 0.0, "codec_wall_ms": 0.0}
     codec_flops = []
+    last = {}  # the latest single utterance's token ids and PCM length (--dump-outputs)
 
     d_emb = dev.upload(np.ascontiguousarray(emb, np.float32))
     d_pcm = dev.empty((a.tokens * codec.samples_per_token,), np.float32)
@@ -503,6 +545,7 @@ def main():
             codec_flops.append(codec.last_flops())
         if len(toks) != a.tokens or n != a.tokens * codec.samples_per_token:
             raise RuntimeError(f"utterance produced {len(toks)} tokens / {n} samples")
+        last["tokens"], last["samples"] = toks, n
         return n
 
     batch_llm_s = []
@@ -528,36 +571,52 @@ def main():
     value = audio_s / elapsed
     utt_per_rank = a.steps * (B if B > 1 else a.utts_per_step)
 
-    # PCIe-inclusive: each rank copies its utterances' PCM to host memory (ranks in parallel:
-    # the slowest rank's copy time counts, never `value`)
-    t0 = time.perf_counter()
-    for _ in range(3):
-        d_pcm.numpy()
-    d2h_s = all_reduce(dist, (time.perf_counter() - t0) / 3, "max")
-    value_pcie = audio_s / (elapsed + d2h_s * utt_per_rank)
+    if a.dump_outputs:
+        # what the last timed step handed back: its sampled token ids and its PCM (left in HBM
+        # by the timed path; copied to host memory here, after the clock has stopped)
+        if B > 1:
+            outs, d_outs, lens = bstep.last
+            arrays = {}
+            for b in range(B):
+                arrays[f"tokens_{b:02d}"] = np.asarray(outs[b])
+                arrays[f"pcm_{b:02d}"] = d_outs[b].numpy().ravel()[:lens[b]]
+        else:
+            arrays = {"tokens": np.asarray(last["tokens"]), "pcm": d_pcm.numpy().ravel()[:last["samples"]]}
+        dump_outputs(a.dump_outputs, arrays, rank)
 
-    # WAV epilogue on the device (mio_hip_pcm_finish: peak normalise + PCM16) of the last
-    # utterance, HIP events on the device stream; reported beside the stage times
-    n_pcm = a.tokens * codec.samples_per_token
-    d_pcm16 = dev.empty((n_pcm,), np.int16)
-    lib = m.lib()
-    pf_ms = []
-    for _ in range(4):
-        dev.mark(14)
-        m.check(lib.mio_hip_pcm_finish(dev.h, d_pcm.ptr, n_pcm, 1, d_pcm16.ptr, None, None))
-        dev.mark(15)
-        dev.sync()
-        pf_ms.append(dev.elapsed_ms(14, 15))
-    pcm_finish_ms = round(min(pf_ms[1:]), 4)
+    # everything below is beside the headline figure: --full only
+    value_pcie = pcm_finish_ms = None
+    if a.full:
+        # PCIe-inclusive: each rank copies its utterances' PCM to host memory (ranks in parallel:
+        # the slowest rank's copy time counts, never `value`)
+        t0 = time.perf_counter()
+        for _ in range(3):
+            d_pcm.numpy()
+        d2h_s = all_reduce(dist, (time.perf_counter() - t0) / 3, "max")
+        value_pcie = round(audio_s / (elapsed + d2h_s * utt_per_rank), 3)
+
+        # WAV epilogue on the device (mio_hip_pcm_finish: peak normalise + PCM16) of the last
+        # utterance, HIP events on the device stream; reported beside the stage times
+        n_pcm = a.tokens * codec.samples_per_token
+        d_pcm16 = dev.empty((n_pcm,), np.int16)
+        lib = m.lib()
+        pf_ms = []
+        for _ in range(4):
+            dev.mark(14)
+            m.check(lib.mio_hip_pcm_finish(dev.h, d_pcm.ptr, n_pcm, 1, d_pcm16.ptr, None, None))
+            dev.mark(15)
+            dev.sync()
+            pf_ms.append(dev.elapsed_ms(14, 15))
+        pcm_finish_ms = round(min(pf_ms[1:]), 4)
 
     roof = None
-    if rank == 0 and not a.no_roofline and B == 1:
+    if a.full and rank == 0 and not a.no_roofline and B == 1:
         # roofline at decode position ~400, the utterance's mean attention length and the
         # position of the PMC passes (tools/pmc_run.py)
         llm.generate(prompt, max(1, ROOF_POS + 2 - len(prompt)), 0.8, 7, allow=allow, check_interval=1000)
         roof = roofline(llm, a.preset)
     tail = None
-    if rank == 0 and B == 1 and stage["llm_ms"] > 0:
+    if a.full and rank == 0 and B == 1 and stage["llm_ms"] > 0:
         tail = eos_tail(llm, prompt, stage["llm_ms"] / utt_per_rank / a.tokens * 1e3)
 
     steps_total = utt_per_rank
@@ -590,7 +649,7 @@ def main():
                      "pcm_finish_ms": pcm_finish_ms},
         "llm_ms_per_token": round(stage["llm_ms"] / steps_total / a.tokens, 4),
         "roofline": roof,
-        "value_pcie_inclusive": round(value_pcie, 3),
+        "value_pcie_inclusive": value_pcie,
         "cpu_baseline": None,
         "eos_tail": tail,
     }
@@ -609,9 +668,9 @@ def main():
                                "step_frac": round(by / step_s / 1e9 / HBM_PEAK_GBS, 4),
                                "note": "decode steps incl. the prompt prefill; bytes = weights + K/V rows "
                                        "of B streams at the mean position"}
-    if world == 1 and a.batch > 0 and B == 1:
+    if a.full and world == 1 and a.batch > 0 and B == 1:
         out["batched"] = batched_line(a, llm, codec, dev, prompt, allow, d_emb, d_pcm)
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         share = int(os.environ.get("OMP_NUM_THREADS", 0) or min(16, os.cpu_count() or 1))
         out["cpu_baseline"] = cpu_baseline(llm_path, codec_path, voice_path, a.cpu_tokens, a.cpu_codes, a.tokens,
                                            share)
@@ -619,7 +678,7 @@ def main():
                                                      a.cpu_codes // 2, a.tokens, 4)
         if not a.no_cpu_c1:
             out["cpu_baseline_c1"] = cpu_baseline_c1(a.workdir, a.tokens, share)
-    if rank == 0 and world == 1 and B == 1 and not a.no_configs:
+    if a.full and rank == 0 and world == 1 and B == 1 and not a.no_configs:
         out["baseline_configs"] = baseline_configs(a, llm_path, codec_path, voice_path)
     if rank == 0:
         print(json.dumps(out, ensure_ascii=False), flush=True)

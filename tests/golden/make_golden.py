@@ -10,8 +10,11 @@ records inputs + the reference's outputs as small data fixtures:
   token_parser.json      strings -> parse_speech_tokens()              (token-parser.cpp:5-28)
   normalize.json         strings -> normalize_tts_text()               (text-normalize.cpp:108-158)
   wav_cases.npz          sample vectors -> exact wav_write() bytes     (wav-writer.cpp:24-44)
+  istft_live.npz         larger seeded spectra -> reference istft() PCM (`istft_live` argument)
+  reference_cli.json     option names, exit codes and messages of the reference's own CLIs built
+                         against include/ (`reference_cli` argument; recorded results only)
 
-Usage: python tests/golden/make_golden.py
+Usage: python tests/golden/make_golden.py [istft_live] [reference_cli]
 """
 import json
 import os
@@ -142,5 +145,85 @@ def main() -> None:
     print("golden fixtures written to", HERE)
 
 
+ISTFT_LIVE_SEED, ISTFT_LIVE_FRAMES = 99, (1, 4, 37, 200)
+
+
+def istft_live_specs():
+    """The spectra of tests/test_oracle_istft.py::test_oracle_matches_live_reference, regenerated
+    from their seed (only the reference's PCM is stored)."""
+    rng = np.random.default_rng(ISTFT_LIVE_SEED)
+    return {f: rng.standard_normal((f, 197, 2)).astype(np.float32) * 3 for f in ISTFT_LIVE_FRAMES}
+
+
+def istft_live() -> None:
+    """istft_live.npz: the reference istft() PCM of istft_live_specs()."""
+    subprocess.check_call(["make", "-s", "-C", os.path.join(REPO, "oracle"), "ref"])
+    out = {f"pcm_{f}": pyoracle.istft(s, use_ref=True) for f, s in istft_live_specs().items()}
+    np.savez_compressed(os.path.join(HERE, "istft_live.npz"), **out)
+
+
+CLI_NAMES = ["miotts", "miotts-stream-benchmark", "miotts-stream-compare"]
+CLI_USAGE_ARGS = [[], ["--bogus"], ["-c", "x.gguf"], ["-p", "hi"], ["--max-tokens"]]
+CLI_NO_GPU_EXTRA = {"miotts": ["-o", "x.wav"], "miotts-stream-benchmark": [], "miotts-stream-compare": []}
+
+
+def cli_flags(usage: str):
+    """Option names of a usage text: '-m, --model PATH  ...' -> {'-m', '--model'}."""
+    import re
+    out = set()
+    for line in usage.splitlines():
+        mm = re.match(r"\s+(-[\w-]+)(?:,\s*(--[\w-]+))?", line)
+        if mm:
+            out.update(x for x in mm.groups() if x)
+    return out
+
+
+def cli_first_err(err: str) -> str:
+    """First stderr line; a usage text (whose first line names the program's path) as 'Usage:'."""
+    first = err.strip().splitlines()[0] if err.strip() else ""
+    return "Usage:" if first.startswith("Usage:") else first
+
+
+def cli_record(exe: str, name: str, models=None) -> dict:
+    """What tests/test_reference_callers.py compares of one program: the option names its --help
+    lists, exit code / stdout / first stderr line of every usage error, and (models given, no GPU
+    visible) exit code / stdout / stderr of a synthesis attempt."""
+    def run(args):
+        p = subprocess.run([exe] + args, capture_output=True, text=True, timeout=120)
+        return p.returncode, p.stdout, p.stderr
+
+    rc, out, err = run(["--help"])
+    rec = {"help_rc": rc, "flags": sorted(cli_flags(out + err)), "usage_errors": []}
+    for args in CLI_USAGE_ARGS:
+        rc, out, err = run(args)
+        rec["usage_errors"].append({"args": args, "rc": rc, "stdout": out, "first_err": cli_first_err(err)})
+    if models is not None:
+        rc, out, err = run(["-m", models["llm"], "-c", models["codec"], "-v", models["voice"], "-p", "hello",
+                            "--max-tokens", "8"] + CLI_NO_GPU_EXTRA[name])
+        rec["no_gpu"] = {"rc": rc, "stdout": out, "stderr": err}
+    return rec
+
+
+def reference_cli() -> None:
+    """reference_cli.json: cli_record() of the reference's own programs (oracle/_ref/callers/,
+    `make -C oracle callers`), taken where no GPU is visible."""
+    sys.path.insert(0, os.path.join(REPO, "miotts-llama.cpp_amd", "python"))
+    import miotts_amd as m
+    if m.device_count() != 0:
+        sys.exit("reference_cli.json records the no-GPU failure path: run where no GPU is visible")
+    subprocess.check_call(["make", "-s", "-C", os.path.join(REPO, "oracle"), "callers"])
+    with tempfile.TemporaryDirectory() as td:
+        models = {"llm": m.synth_llm(os.path.join(td, "llm.gguf"), 0, 1),
+                  "codec": m.synth_codec(os.path.join(td, "codec.gguf"), 1, 1),
+                  "voice": m.synth_voice(os.path.join(td, "voice.emb.gguf"), 7)}
+        rec = {n: cli_record(os.path.join(REPO, "oracle", "_ref", "callers", n), n, models) for n in CLI_NAMES}
+    with open(os.path.join(HERE, "reference_cli.json"), "w", encoding="utf-8") as f:
+        json.dump(rec, f, ensure_ascii=False, indent=1)
+
+
 if __name__ == "__main__":
-    main()
+    # no argument: the fixtures of main(); `istft_live` / `reference_cli`: that fixture alone
+    if not os.path.isdir("/root/reference/src"):
+        sys.exit("reference sources not present; fixtures are generated in the build container only")
+    for what in sys.argv[1:] or ["main"]:
+        {"main": main, "istft_live": istft_live, "reference_cli": reference_cli}[what]()

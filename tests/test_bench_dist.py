@@ -88,3 +88,40 @@ def test_bench_launcher_spawns_ranks():
     r = json.loads(lines[0])
     assert r["n_gpus"] == 2 and r["samples"] == 2 * 3 * 1000
     assert r["elapsed"] >= 3 * 0.04  # the slower rank (rank 1) sets the time
+
+
+def test_plain_run_options():
+    """--full is off by default and --dump-outputs takes a directory; --steps / --warmup are the
+    counts the timed region gets."""
+    import bench
+
+    a = bench.parse_args(["--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert (a.gpus, a.steps, a.warmup, a.full, a.dump_outputs) == (1, 5, 2, False, None)
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+
+
+def test_dump_outputs_files(tmp_path):
+    """dump_outputs: one .npy per array, integers as float64 and floats as float32, values kept;
+    past the byte budget every array keeps the same seeded share of its elements, in order, and a
+    second dump keeps the same ones."""
+    import numpy as np
+
+    import bench
+
+    toks = np.arange(151000, 151700, dtype=np.int32)
+    pcm = np.random.default_rng(1).standard_normal(5000).astype(np.float32)
+    bench.dump_outputs(str(tmp_path / "a"), {"tokens": toks, "pcm": pcm})
+    assert sorted(os.listdir(tmp_path / "a")) == ["pcm.npy", "tokens.npy"]
+    t, p = np.load(tmp_path / "a" / "tokens.npy"), np.load(tmp_path / "a" / "pcm.npy")
+    assert t.dtype == np.float64 and np.array_equal(t, toks)
+    assert p.dtype == np.float32 and np.array_equal(p, pcm)
+    budget = (toks.size * 8 + pcm.size * 4) // 4
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"tokens": toks, "pcm": pcm}, rank=1, max_bytes=budget)
+    assert sorted(os.listdir(tmp_path / "b")) == ["pcm_rank1.npy", "tokens_rank1.npy"]
+    tb, pb = np.load(tmp_path / "b" / "tokens_rank1.npy"), np.load(tmp_path / "b" / "pcm_rank1.npy")
+    assert tb.nbytes + pb.nbytes <= budget and tb.size == toks.size // 4 and pb.size == pcm.size // 4
+    assert np.all(np.diff(tb) > 0) and np.isin(tb, toks).all() and np.isin(pb, pcm).all()
+    assert np.array_equal(tb, np.load(tmp_path / "c" / "tokens_rank1.npy"))
+    assert np.array_equal(pb, np.load(tmp_path / "c" / "pcm_rank1.npy"))

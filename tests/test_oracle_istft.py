@@ -2,13 +2,14 @@
 
 (1) against the committed fixtures produced by the reference's own istft.cpp
     (tests/golden/make_golden.py), bit-exact;
-(2) against a live build of the reference TUs when oracle/_ref exists here;
+(2) against the reference's recorded PCM of larger seeded spectra, and a live build of the
+    reference TUs against the same record when oracle/_ref exists here;
 (3) known-answer tests (SURVEY 8c KAT 1).
 """
 import os
+import sys
 
 import numpy as np
-import pytest
 
 import pyoracle
 
@@ -45,11 +46,21 @@ def test_oracle_empty_and_lengths():
         assert pyoracle.istft(np.zeros((f, 197, 2), np.float32)).size == 98 * f
 
 
-@pytest.mark.skipif(not pyoracle.ref_available(), reason="reference TUs not built here")
-def test_oracle_matches_live_reference():
-    rng = np.random.default_rng(99)
-    for f in (1, 4, 37, 200):
-        spec = rng.standard_normal((f, 197, 2)).astype(np.float32) * 3
+def test_oracle_matches_live_reference(golden_dir):
+    """Seeded spectra of 1 / 4 / 37 / 200 frames: the oracle equals the reference's PCM bit for
+    bit. The reference's PCM is the recorded one (tests/golden/istft_live.npz, written by
+    `make_golden.py istft_live`); where the reference TUs are built here, the live build must
+    give the recorded PCM too."""
+    sys.path.insert(0, golden_dir)
+    import make_golden
+
+    z = np.load(os.path.join(golden_dir, "istft_live.npz"))
+    specs = make_golden.istft_live_specs()
+    assert sorted(specs) == [1, 4, 37, 200]
+    for f, spec in specs.items():
+        b = z[f"pcm_{f}"]
+        assert b.shape == (98 * f,) and b.dtype == np.float32
+        if pyoracle.ref_available():
+            assert np.array_equal(pyoracle.istft(spec, use_ref=True), b)
         a = pyoracle.istft(spec)
-        b = pyoracle.istft(spec, use_ref=True)
         assert np.array_equal(a, b)
