@@ -132,7 +132,9 @@ int mio_hip_codec_decode_stage(mio_hip_codec *c, const int32_t *codes, int n_cod
 /* ---------------- LLM decode ----------------
  * Replaces llama_model_load_from_file + llama_init_from_model (test-to-speech.cpp:47-49,
  * :103-108): GGUF "llama" / "mistral" / "qwen2" / "qwen3" / "lfm2" (short-conv hybrid) with
- * Q8_0 / Q4_K / Q6_K matrices (Q4_K_M),
+ * Q8_0 / Q4_K / Q5_K / Q6_K / BF16 matrices (Q8_0, Q4_K_M, Q5_K_M, Q5_K_S, Q6_K and BF16 files;
+ * Q5_0 / Q4_0 rows run as the Q8_0 rows they equal); any other tensor type (Q5_1, Q4_1, Q2_K,
+ * Q3_K, IQ*) fails the load with the tensor's name and type,
  * F16 KV cache of n_ctx positions (0 -> 2048, :104). */
 int mio_hip_llm_load(mio_hip_device *d, const char *gguf_path, int n_ctx, mio_hip_llm **out);
 void mio_hip_llm_free(mio_hip_llm *m);

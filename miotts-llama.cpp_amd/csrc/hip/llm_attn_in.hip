@@ -125,14 +125,7 @@ void launch(const LlmDims &d, const LayerW &L, int il, const QMat &tok_embd, con
                                        L.attn_norm, L.wq, L.wk, L.wv, g_qk, b, tok_embd, nblk);
             });
         };
-        if constexpr (TQ == 8 || TQ == 30) {
-            go.template operator()<TQ>();
-        } else {
-            if (L.wv.type == 14)
-                go.template operator()<14>();
-            else
-                go.template operator()<12>();
-        }
+        dispatch_v<TQ>(L.wv.type, go);
     });
 }
 

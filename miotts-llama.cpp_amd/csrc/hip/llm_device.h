@@ -7,6 +7,8 @@
 
 #include <cfloat>
 #include <climits>
+#include <cstdio>
+#include <cstdlib>
 #include <type_traits>
 
 #include "llm_kernels.h"
@@ -344,7 +346,7 @@ __device__ inline void load_x(const float *x, const float *w, int K, XRegs<XV> &
 }
 
 // Activation kind of a weight type (ggml's vec_dot_type): 0 Q8_0 (Q8_0 weights), 1 Q8_K
-// (Q4_K / Q6_K), 2 BF16 (BF16 weights: the activation rounded to bf16, ggml_fp32_to_bf16).
+// (Q4_K / Q5_K / Q6_K), 2 BF16 (BF16 weights: the activation rounded to bf16, ggml_fp32_to_bf16).
 __host__ __device__ constexpr int akind(int T) { return T == 30 ? 2 : (T == 8 ? 0 : 1); }
 
 // ggml_compute_fp32_to_bf16: round to nearest even, NaN kept quiet
@@ -574,6 +576,8 @@ constexpr uint32_t M4 = 0x0F0F0F0Fu, M2 = 0x03030303u;
 // One unit's weight registers.
 //   Q4_K: a = 16 B of nibbles, c = dword (lane & 3) of the superblock header {d, dmin,
 //         4 x 24-bit scale pairs}
+//   Q5_K: a, c as Q4_K; b = the 16 B of the superblock's fifth-bit plane (qh) under the lane's
+//         nibble bytes (qh[16 (pc & 1) .. +16], pc = lane & 7; sub-block j's bit is bit j)
 //   Q6_K: a = 16 B of ql, b = 16 B of qh, c = the lane's two int8 sub-block scales, e = d
 //   Q8_0: a, b = the lane's 32 codes, e = d
 //   BF16: a, b, a2, b2 = the lane's 32 weights (bf16 pairs), one contiguous KB per register
@@ -649,6 +653,13 @@ __device__ __forceinline__ Frag load_frag(const QMat W, int row, int pass) {
         f.c = bld4<AUX>(W.p1, R * hb, sb * 16 + 4 * (pc & 3), r * hb);
         f.b = make_uint4(0, 0, 0, 0);
         f.e = 0;
+    } else if constexpr (T == 13) {
+        const int nsb = W.k >> 8, sb = min(pass * 8 + (lane >> 3), nsb - 1), pc = lane & 7;
+        const uint32_t qb = (uint32_t)(W.k / 2), fb = (uint32_t)(W.k / 8), hb = (uint32_t)nsb * 16;
+        f.a = bld16<AUX>(W.p0, R * qb, sb * 128 + pc * 16, r * qb);
+        f.b = bld16<AUX>(W.p1, R * fb, sb * 32 + 16 * (pc & 1), r * fb);
+        f.c = bld4<AUX>(W.p2, R * hb, sb * 16 + 4 * (pc & 3), r * hb);
+        f.e = 0;
     } else if constexpr (T == 14) {
         const int nsb = W.k >> 8, sb = min(pass * 8 + (lane >> 3), nsb - 1), pc = lane & 7;
         const uint32_t lb = (uint32_t)(W.k / 2), hb = (uint32_t)(W.k / 4), sbb = (uint32_t)(W.k / 16),
@@ -682,11 +693,11 @@ template <int T>
 __device__ __forceinline__ ALane load_alane(const ActL &a, int K, int pass) {
     const int lane = MIO_TIDX & 63;
     ALane r;
-    if constexpr (T == 12 || T == 14) {
+    if constexpr (T == 12 || T == 13 || T == 14) {
         const int nsb = K >> 8, sb = pass * 8 + (lane >> 3), pc = lane & 7;
         const int sbc = sb < nsb ? sb : 0;
         int e, e2;
-        if constexpr (T == 12) {
+        if constexpr (T == 12 || T == 13) {
             e = sbc * 256 + 64 * (pc >> 1) + 16 * (pc & 1);
             e2 = e + 32;
         } else {
@@ -724,7 +735,7 @@ __device__ __forceinline__ ALane load_alane(const ActL &a, int K, int pass) {
 template <int T>
 __device__ __forceinline__ float dot_frag(const Frag &f, const ALane &al, int K, int pass) {
     const int lane = MIO_TIDX & 63;
-    if constexpr (T == 12) {
+    if constexpr (T == 12 || T == 13) {
         const int jj = (lane & 7) >> 1;
         uint4 h;  // the superblock header {d|dmin, scale/min words} from the quad's four dwords
         h.x = (uint32_t)dpp_i<0x00>((int)f.c);
@@ -735,15 +746,25 @@ __device__ __forceinline__ float dot_frag(const Frag &f, const ALane &al, int K,
         const uint32_t whi = jj < 2 ? h.z : h.w;
         const uint32_t F = __builtin_amdgcn_alignbit(whi, wlo, (24 * jj) & 31);
         const int sc0 = F & 63, m0 = (F >> 6) & 63, sc1 = (F >> 12) & 63, m1 = (F >> 18) & 63;
+        // Q5_K: the fifth bit of sub-block 2 jj (low nibbles) is bit 2 jj of each qh byte, of
+        // sub-block 2 jj + 1 (high nibbles) the next one; moved to bit 4 of the code
+        auto lo = [&](uint32_t q, uint32_t h) {
+            if constexpr (T == 13) return (int)((q & M4) | (((h >> (2 * jj)) & 0x01010101u) << 4));
+            else return (int)(q & M4);
+        };
+        auto hi = [&](uint32_t q, uint32_t h) {
+            if constexpr (T == 13) return (int)(((q >> 4) & M4) | (((h >> (2 * jj + 1)) & 0x01010101u) << 4));
+            else return (int)((q >> 4) & M4);
+        };
         int dlo = 0, dhi = 0;
-        dlo = sdot4((int)(f.a.x & M4), al.lo.x, dlo);
-        dlo = sdot4((int)(f.a.y & M4), al.lo.y, dlo);
-        dlo = sdot4((int)(f.a.z & M4), al.lo.z, dlo);
-        dlo = sdot4((int)(f.a.w & M4), al.lo.w, dlo);
-        dhi = sdot4((int)((f.a.x >> 4) & M4), al.hi.x, dhi);
-        dhi = sdot4((int)((f.a.y >> 4) & M4), al.hi.y, dhi);
-        dhi = sdot4((int)((f.a.z >> 4) & M4), al.hi.z, dhi);
-        dhi = sdot4((int)((f.a.w >> 4) & M4), al.hi.w, dhi);
+        dlo = sdot4(lo(f.a.x, f.b.x), al.lo.x, dlo);
+        dlo = sdot4(lo(f.a.y, f.b.y), al.lo.y, dlo);
+        dlo = sdot4(lo(f.a.z, f.b.z), al.lo.z, dlo);
+        dlo = sdot4(lo(f.a.w, f.b.w), al.lo.w, dlo);
+        dhi = sdot4(hi(f.a.x, f.b.x), al.hi.x, dhi);
+        dhi = sdot4(hi(f.a.y, f.b.y), al.hi.y, dhi);
+        dhi = sdot4(hi(f.a.z, f.b.z), al.hi.z, dhi);
+        dhi = sdot4(hi(f.a.w, f.b.w), al.hi.w, dhi);
         int isum = __mul24(sc0, dlo) + __mul24(sc1, dhi);
         int imin = __mul24(m0, al.b0) + __mul24(m1, al.b1);
         isum = sum8_i(isum);
@@ -955,14 +976,17 @@ __device__ inline void wave_range(const LlmDims &d, int R, int &lo, int &hi) {
 
 // ------------------------------------------------------------------ embedding rows
 __device__ float dequant_elem(const QMat &W, int row, int e) {
-    if (W.type == 12) {
+    if (W.type == 12 || W.type == 13) {
         const int nsb = W.k >> 8, sb = e >> 8, c = e & 255, j = c >> 6, w = c & 63, hi = w >> 5, l = w & 31;
         const uint8_t q = W.p0[(size_t)row * (W.k / 2) + sb * 128 + 32 * j + l];
-        const uint8_t *hd = W.p1 + ((size_t)row * nsb + sb) * 16;
+        const uint8_t *hd = (W.type == 13 ? W.p2 : W.p1) + ((size_t)row * nsb + sb) * 16;
         const uint32_t F = (uint32_t)hd[4 + 3 * j] | ((uint32_t)hd[5 + 3 * j] << 8) | ((uint32_t)hd[6 + 3 * j] << 16);
         const int sc = (F >> (12 * hi)) & 63, m = (F >> (12 * hi + 6)) & 63;
         const float d1 = h2f(hd[0] | (hd[1] << 8)) * sc, m1 = h2f(hd[2] | (hd[3] << 8)) * m;
-        return d1 * (float)(hi ? (q >> 4) : (q & 0xF)) - m1;
+        int code = hi ? (q >> 4) : (q & 0xF);
+        // Q5_K: sub-block 2 j + hi's fifth bit of weight l is bit 2 j + hi of qh[l]
+        if (W.type == 13) code += ((W.p1[(size_t)row * (W.k / 8) + sb * 32 + l] >> (2 * j + hi)) & 1) << 4;
+        return d1 * (float)code - m1;
     } else if (W.type == 14) {
         const int nsb = W.k >> 8, sb = e >> 8, c = e & 255, n = c >> 7, w = c & 127, g = w >> 5, l = w & 31;
         const uint8_t ql = W.p0[(size_t)row * (W.k / 2) + sb * 128 + 64 * n + l + 32 * (g & 1)];
@@ -1110,6 +1134,14 @@ __device__ inline void embed_regs(const QMat &emb, int tok, int K, XRegs<XV> &xr
     }
 }
 
+// A launch asked for a weight type no kernel is instantiated for. The loader refuses such files
+// (llm.cpp upload_qmat, attn_v_supported), so this is a broken invariant: never run another
+// type's kernel on the bytes instead.
+[[noreturn]] inline void no_kernel(const char *what, int type, int k) {
+    fprintf(stderr, "miotts: no %s kernel for ggml type %d (%d)\n", what, type, k);
+    abort();
+}
+
 // Calls f.template operator()<NP, T>() for the matrix's pass count and weight type. BF = false:
 // the int8 types only (the multi-token engine: BF16 models prefill token by token).
 template <bool BF = true, class F>
@@ -1117,12 +1149,26 @@ void dispatch_nt(int K, int type, F &&f) {
     const int np = pick_np(K);
 #define NT_CASE(NPV, TV) \
     if (np == NPV && type == TV) return f.template operator()<NPV, TV>();
-    NT_CASE(1, 8) NT_CASE(1, 12) NT_CASE(1, 14) NT_CASE(3, 8) NT_CASE(3, 12) NT_CASE(3, 14)
-    NT_CASE(6, 8) NT_CASE(6, 12) NT_CASE(6, 14)
+    NT_CASE(1, 8) NT_CASE(1, 12) NT_CASE(1, 13) NT_CASE(1, 14) NT_CASE(3, 8) NT_CASE(3, 12) NT_CASE(3, 13)
+    NT_CASE(3, 14) NT_CASE(6, 8) NT_CASE(6, 12) NT_CASE(6, 13) NT_CASE(6, 14)
     if constexpr (BF) {
         NT_CASE(1, 30) NT_CASE(3, 30) NT_CASE(6, 30)
     }
 #undef NT_CASE
+    no_kernel("matvec", type, K);
+}
+
+// attn_v's type beside q|k of type TQ (attn_v_supported): calls f.template operator()<TV>().
+template <int TQ, class F>
+void dispatch_v(int tv, F &&f) {
+    if (tv == TQ) return f.template operator()<TQ>();
+    if constexpr (TQ == 12 || TQ == 13) {
+        if (tv == 14) return f.template operator()<14>();
+    }
+    if constexpr (TQ == 14) {
+        if (tv == 12) return f.template operator()<12>();
+    }
+    no_kernel("attn_v beside q|k", tv, TQ);
 }
 
 

@@ -87,10 +87,16 @@ __device__ __forceinline__ v4i act16(const int8_t *qs, int e) { return *reinterp
 // its 16 tokens.
 
 // Q4_K superblock s of row `row`: v = d * isum - dmin * imin per token (ggml vec_dot_q4_K_q8_K).
+// Q5 (Q5_K, vec_dot_q5_K_q8_K): the same with 5-bit codes; frow = the row's fifth-bit plane,
+// whose bytes 16 h .. + 16 of superblock s lie under this lane's nibble bytes of every chunk c,
+// sub-block 2c's bit at bit 2c and sub-block 2c + 1's at bit 2c + 1. The min term is unchanged.
+template <bool Q5 = false>
 __device__ __forceinline__ v16f sb_q4k(const uint8_t *qrow, const uint8_t *hrow, int s, const int8_t *aq,
-                                       const float *da_lds) {
+                                       const float *da_lds, const uint8_t *frow = nullptr) {
     const int lane = threadIdx.x & 63, h = lane >> 5;
     const uint4 hd = *reinterpret_cast<const uint4 *>(hrow + (size_t)s * 16);
+    uint4 fb = make_uint4(0, 0, 0, 0);
+    if constexpr (Q5) fb = *reinterpret_cast<const uint4 *>(frow + (size_t)s * 32 + 16 * h);
     uint4 nb[4];
     v4i al[4], ah[4];
 #pragma unroll
@@ -108,8 +114,15 @@ __device__ __forceinline__ v16f sb_q4k(const uint8_t *qrow, const uint8_t *hrow,
         const uint32_t F = __builtin_amdgcn_alignbit(whi, wlo, (24 * c) & 31);
         const int sc0 = F & 63, m0 = (F >> 6) & 63, sc1 = (F >> 12) & 63, m1 = (F >> 18) & 63;
         const uint4 q = nb[c];
-        const v4i blo = {(int)(q.x & M4), (int)(q.y & M4), (int)(q.z & M4), (int)(q.w & M4)};
-        const v4i bhi = {(int)((q.x >> 4) & M4), (int)((q.y >> 4) & M4), (int)((q.z >> 4) & M4), (int)((q.w >> 4) & M4)};
+        v4i blo = {(int)(q.x & M4), (int)(q.y & M4), (int)(q.z & M4), (int)(q.w & M4)};
+        v4i bhi = {(int)((q.x >> 4) & M4), (int)((q.y >> 4) & M4), (int)((q.z >> 4) & M4), (int)((q.w >> 4) & M4)};
+        if constexpr (Q5) {
+            constexpr uint32_t B1 = 0x01010101u;
+            blo |= v4i{(int)(((fb.x >> (2 * c)) & B1) << 4), (int)(((fb.y >> (2 * c)) & B1) << 4),
+                       (int)(((fb.z >> (2 * c)) & B1) << 4), (int)(((fb.w >> (2 * c)) & B1) << 4)};
+            bhi |= v4i{(int)(((fb.x >> (2 * c + 1)) & B1) << 4), (int)(((fb.y >> (2 * c + 1)) & B1) << 4),
+                       (int)(((fb.z >> (2 * c + 1)) & B1) << 4), (int)(((fb.w >> (2 * c + 1)) & B1) << 4)};
+        }
         const v16i clo = __builtin_amdgcn_mfma_i32_32x32x32_i8(al[c], blo, v16i{}, 0, 0, 0);
         const v16i chi = __builtin_amdgcn_mfma_i32_32x32x32_i8(ah[c], bhi, v16i{}, 0, 0, 0);
         const int mb0 = m0 * 0x01010101, mb1 = m1 * 0x01010101;
@@ -206,8 +219,12 @@ __device__ v16f slot_kq(const QMat &W, int row, int k, const int8_t *aq, const f
         const int s = p * 8 + k;
         v16f v = {};
         if (s < nsb) {
+            static_assert(T == 12 || T == 13 || T == 14, "slot_kq: K-quant types");
             if constexpr (T == 12)
                 v = sb_q4k(W.p0 + (size_t)row * (W.k / 2), W.p1 + (size_t)row * nsb * 16, s, aq, da_lds);
+            else if constexpr (T == 13)
+                v = sb_q4k<true>(W.p0 + (size_t)row * (W.k / 2), W.p2 + (size_t)row * nsb * 16, s, aq, da_lds,
+                                 W.p1 + (size_t)row * (W.k / 8));
             else
                 v = sb_q6k(W, row, s, aq, da_lds);
         }
@@ -318,6 +335,7 @@ __device__ v16f slot_q80(const QMat &W, int row, int k, const int8_t *aq, const 
 
 template <int T>
 __device__ __forceinline__ v16f slot_val(const QMat &W, int row, int k, const int8_t *aq, const float *da_lds) {
+    static_assert(T == 8 || T == 12 || T == 13 || T == 14, "slot_val: weight type");
     if constexpr (T == 8) return slot_q80(W, row, k, aq, da_lds);
     else return slot_kq<T>(W, row, k, aq, da_lds);
 }
@@ -498,17 +516,34 @@ struct Q4Pass {
     uint4 hd;
     v4i w[2];
 };
+// Q5_K: Q4_K's pass plus the lane's 8 bytes of the fifth-bit plane. After swap_halves a lane of
+// group g holds, of every 32-B nibble run, bytes 8 pi(g) .. + 8 with pi = {0, 2, 1, 3} (the
+// low / high halves are two runs in the same byte order), and the plane is indexed by the byte
+// within the run: one 8-B load at 8 pi(g), no swap.
+struct Q5Pass : Q4Pass {
+    uint2 f;
+};
 __device__ __forceinline__ void q4p_load(const uint8_t *qrow, const uint8_t *hrow, int s, Q4Pass &p) {
     const int g = (threadIdx.x & 63) >> 4;
     p.hd = *reinterpret_cast<const uint4 *>(hrow + (size_t)s * 16);
 #pragma unroll
     for (int i = 0; i < 2; ++i) p.w[i] = *reinterpret_cast<const v4i *>(qrow + (size_t)s * 128 + 64 * i + 16 * g);
 }
+__device__ __forceinline__ void q5p_load(const uint8_t *qrow, const uint8_t *frow, const uint8_t *hrow, int s,
+                                         Q5Pass &p) {
+    const int g = (threadIdx.x & 63) >> 4;
+    q4p_load(qrow, hrow, s, p);
+    p.f = *reinterpret_cast<const uint2 *>(frow + (size_t)s * 32 + 8 * (2 * (g & 1) + (g >> 1)));
+}
 // x: the superblock's activation codes of this lane, already swap_halves'd
-__device__ __forceinline__ v4f q4p_val(Q4Pass p, const v4i (&x)[4], int s, const float *da_lds) {
+template <class Pass>
+__device__ __forceinline__ v4f q4p_val(Pass p, const v4i (&x)[4], int s, const float *da_lds) {
+    constexpr bool Q5 = std::is_same_v<Pass, Q5Pass>;
     const int lane = threadIdx.x & 63;
     const uint4 hd = p.hd;
     v4i (&w)[2] = p.w;
+    long fb = 0;
+    if constexpr (Q5) fb = (long)(uint32_t)p.f.x | ((long)(uint32_t)p.f.y << 32);
 #pragma unroll
     for (int i = 0; i < 2; ++i) swap_halves(w[i]);
     v4i isum = {}, imin = {};
@@ -520,8 +555,13 @@ __device__ __forceinline__ v4f q4p_val(Q4Pass p, const v4i (&x)[4], int s, const
         const int sc0 = F & 63, m0 = (F >> 6) & 63, sc1 = (F >> 12) & 63, m1 = (F >> 18) & 63;
         const long q = (c & 1) ? hi8(w[c >> 1]) : lo8(w[c >> 1]);
         const long al = lo8(x[c]), ah = hi8(x[c]);
-        const v4i clo = mfma16(al, q & 0x0F0F0F0F0F0F0F0Fl, v4i{});
-        const v4i chi = mfma16(ah, (q >> 4) & 0x0F0F0F0F0F0F0F0Fl, v4i{});
+        long qlo = q & 0x0F0F0F0F0F0F0F0Fl, qhi = (q >> 4) & 0x0F0F0F0F0F0F0F0Fl;
+        if constexpr (Q5) {  // run c = sub-blocks 2c (low nibbles, plane bit 2c) and 2c + 1
+            qlo |= ((fb >> (2 * c)) & 0x0101010101010101l) << 4;
+            qhi |= ((fb >> (2 * c + 1)) & 0x0101010101010101l) << 4;
+        }
+        const v4i clo = mfma16(al, qlo, v4i{});
+        const v4i chi = mfma16(ah, qhi, v4i{});
         const long mb0 = (long)(uint32_t)(m0 * 0x01010101) * 0x100000001l;
         const long mb1 = (long)(uint32_t)(m1 * 0x01010101) * 0x100000001l;
         imin = mfma16(al, mb0, imin);
@@ -676,6 +716,27 @@ __device__ __forceinline__ v4f sb16_q6k(const QMat &W, int row, int s, const AP 
     return q6p_val(p, x, s, da_lds);
 }
 
+template <int T>
+using KqPass = std::conditional_t<T == 12, Q4Pass, std::conditional_t<T == 13, Q5Pass, Q6Pass>>;
+template <int T>
+__device__ __forceinline__ void kqp_load(const QMat &W, int row, int s, KqPass<T> &p) {
+    static_assert(T == 12 || T == 13 || T == 14, "kqp_load: K-quant types");
+    if constexpr (T == 12)
+        q4p_load(W.p0 + (size_t)row * (W.k / 2), W.p1 + (size_t)row * (W.k >> 8) * 16, s, p);
+    else if constexpr (T == 13)
+        q5p_load(W.p0 + (size_t)row * (W.k / 2), W.p1 + (size_t)row * (W.k / 8),
+                 W.p2 + (size_t)row * (W.k >> 8) * 16, s, p);
+    else
+        q6p_load(W, row, s, p);
+}
+template <int T>
+__device__ __forceinline__ v4f kqp_val(const KqPass<T> &p, const v4i (&x)[4], int s, const float *da) {
+    if constexpr (T == 14)
+        return q6p_val(p, x, s, da);
+    else
+        return q4p_val(p, x, s, da);
+}
+
 template <int T, class AP>
 __device__ v4f slot16_kq(const QMat &W, int row, int k, const AP &aq, const float *da_lds) {
     const int nsb = W.k >> 8, NP = (nsb + 7) / 8;
@@ -684,10 +745,18 @@ __device__ v4f slot16_kq(const QMat &W, int row, int k, const AP &aq, const floa
         const int s = p * 8 + k;
         v4f v = {};
         if (s < nsb) {
-            if constexpr (T == 12)
+            static_assert(T == 12 || T == 13 || T == 14, "slot16_kq: K-quant types");
+            if constexpr (T == 12) {
                 v = sb16_q4k(W.p0 + (size_t)row * (W.k / 2), W.p1 + (size_t)row * nsb * 16, s, aq, da_lds);
-            else
+            } else if constexpr (T == 13) {
+                Q5Pass ps;
+                kqp_load<13>(W, row, s, ps);
+                v4i x[4];
+                kq_act(aq, s, x);
+                v = q4p_val(ps, x, s, da_lds);
+            } else {
                 v = sb16_q6k(W, row, s, aq, da_lds);
+            }
         }
         acc = acc + v;  // the decode lane's pass accumulation (0 + v0 + v1 ...)
     }
@@ -817,11 +886,12 @@ __device__ __forceinline__ void slot16_q80p(const QMat &W, const QMat &U, int ro
 
 template <int T, class AP>
 __device__ __forceinline__ v4f slot16_val(const QMat &W, int row, int k, const AP &aq, const float *da_lds) {
+    static_assert(T == 8 || T == 12 || T == 13 || T == 14, "slot16_val: weight type");
     if constexpr (T == 8) {
         // the 8-B Q8_0 path (K % 256 != 0) never runs in an in-launch-quantization launch
-        // (launch_mmq_q takes K % 256 == 0 only)
-        if constexpr (std::is_same_v<AP, ActSc1>) return v4f{};
-        else return slot16_q80(W, row, k, aq, da_lds);
+        // (launch_mmq_q takes K % 256 == 0 only): no kernel with producers instantiates it
+        static_assert(!std::is_same_v<AP, ActSc1>, "slot16_val: the 8-B Q8_0 path reads plain records only");
+        return slot16_q80(W, row, k, aq, da_lds);
     } else {
         return slot16_kq<T>(W, row, k, aq, da_lds);
     }
@@ -909,23 +979,6 @@ __device__ __forceinline__ void mmq_quant_producer(const MmqArgs &a, const MmqQu
     if (threadIdx.x < 8)
         __hip_atomic_fetch_add((__attribute__((address_space(1))) int *)(q.cnt + 64 * threadIdx.x), 1,
                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-template <int T>
-using KqPass = std::conditional_t<T == 12, Q4Pass, Q6Pass>;
-template <int T>
-__device__ __forceinline__ void kqp_load(const QMat &W, int row, int s, KqPass<T> &p) {
-    if constexpr (T == 12)
-        q4p_load(W.p0 + (size_t)row * (W.k / 2), W.p1 + (size_t)row * (W.k >> 8) * 16, s, p);
-    else
-        q6p_load(W, row, s, p);
-}
-template <int T>
-__device__ __forceinline__ v4f kqp_val(const KqPass<T> &p, const v4i (&x)[4], int s, const float *da) {
-    if constexpr (T == 12)
-        return q4p_val(p, x, s, da);
-    else
-        return q6p_val(p, x, s, da);
 }
 
 // MIO_MMQ_XPRE (A/B builds; default 1): k_mmq16's residual epilogue adds values loaded at the
@@ -1037,7 +1090,7 @@ __global__ __launch_bounds__(MMQ_NT) void k_mmq16(MmqSeg s0, MmqSeg s1, MmqSeg s
             slot16_store(y, red);
             if constexpr (NV == 2) slot16_store(u, red + MMQ_NT * 4);
         } else {
-            if constexpr (NV == 1 && (T == 12 || T == 14) && (QF || MIO_MMQ_ACT1)) {
+            if constexpr (NV == 1 && (T == 12 || T == 13 || T == 14) && (QF || MIO_MMQ_ACT1)) {
                 // up to three passes' weights (K <= 6144, the 1.7B down) are in flight before
                 // the activations are read (with in-launch quantization: while the producers
                 // quantize); then slot16_kq's arithmetic. MIO_MMQ_ACT1: the activation codes of
@@ -1087,10 +1140,16 @@ __global__ __launch_bounds__(MMQ_NT) void k_mmq16(MmqSeg s0, MmqSeg s1, MmqSeg s
                     goto reduce;
                 }
             }
-            wait_act();
-            const auto aq = stage_act16<T, QF>(a, t0, a.K, da);
-            slot16_store(slot16_val<T>(sg.w, row, k, aq, da), red);
-            if constexpr (NV == 2) slot16_store(slot16_val<T>(a.w_up, row, k, aq, da), red + MMQ_NT * 4);
+            if constexpr (T == 8 && QF) {
+                // a Q8_0 launch with producers is compiled for the pair path alone (KP != 0, taken
+                // above): the 8-B path of slot16_val has no sc1 record loads and is not built in
+                static_assert(KP != 0, "k_mmq16: Q8_0 with in-launch quantization needs the pair path (KP 1 / 2)");
+            } else {
+                wait_act();
+                const auto aq = stage_act16<T, QF>(a, t0, a.K, da);
+                slot16_store(slot16_val<T>(sg.w, row, k, aq, da), red);
+                if constexpr (NV == 2) slot16_store(slot16_val<T>(a.w_up, row, k, aq, da), red + MMQ_NT * 4);
+            }
         }
     reduce:
         __syncthreads();
@@ -1415,7 +1474,7 @@ void launch_mmq(const MmqSeg *seg, const int *types, int nseg, int mode, const M
         if (t16) {
             const bool q8 = A == 8 && (B < 0 || B == 8) && (C < 0 || C == 8) && a.K % 256 == 0;
             const int kp = q8 ? (a.K <= 2048 ? 1 : 2) : 0;
-            if constexpr ((A == 12 || A == 14) && B < 0) {
+            if constexpr ((A == 12 || A == 13 || A == 14) && B < 0) {
                 if (a.K % 256 == 0 && a.K <= 2048 && tiles > n_cu() && mmq_loop_on() && (kq_loop_mask() & 1)) {
                     auto kl = [&](auto kern) {
                         if (lds > 64 * 1024) allow_lds_mmq(reinterpret_cast<const void *>(kern));
@@ -1461,19 +1520,23 @@ void launch_mmq(const MmqSeg *seg, const int *types, int nseg, int mode, const M
     };
     auto one = [&]<int A>() {
         if (nseg == 1) return go.template operator()<A, -1, -1>();
-        // attention input: q, k share a type; v is Q4_K / Q6_K (Q4_K_M) or Q8_0
-        if (types[2] == 14) return go.template operator()<A, A, 14>();
-        if (types[2] == 12) return go.template operator()<A, A, 12>();
-        return go.template operator()<A, A, 8>();
+        // attention input: q, k share a type; v has it too, or is Q6_K beside Q4_K / Q5_K (the
+        // *_K_M mixes) or Q4_K beside Q6_K (attn_v_supported)
+        if (types[1] != A || !attn_v_supported(A, types[2])) no_kernel("q|k|v matmul: v", types[2], types[1]);
+        if (types[2] == A) return go.template operator()<A, A, A>();
+        if constexpr (A == 12 || A == 13) return go.template operator()<A, A, 14>();
+        if constexpr (A == 14) return go.template operator()<A, A, 12>();
     };
     if (types[0] == 12) one.template operator()<12>();
+    else if (types[0] == 13) one.template operator()<13>();
     else if (types[0] == 14) one.template operator()<14>();
-    else one.template operator()<8>();
+    else if (types[0] == 8) one.template operator()<8>();
+    else no_kernel("matmul", types[0], a.K);
 }
 
 
 // The fused shapes of the batched decode (launch_layers): q|k|v of the K-quant models (three
-// segments, RMSNorm input), gate|up (Q4_K, or Q8_0 one-pass pairs; RMSNorm input) and the
+// segments, RMSNorm input), gate|up (Q4_K / Q5_K, or Q8_0 one-pass pairs; RMSNorm input) and the
 // K-quant down matmul (plain h rows of 3 passes). Anything else: false.
 bool launch_mmq_q(const MmqSeg *seg, const int *types, int nseg, int mode, const MmqArgs &a, const MmqQuant &q,
                   hipStream_t s) {
@@ -1506,18 +1569,23 @@ bool launch_mmq_q(const MmqSeg *seg, const int *types, int nseg, int mode, const
         if (types[2] == 12) return go(k_mmq16<12, 12, 12, MMQ_STORE, 0, 1, 0>);
         if (types[2] == 14) return go(k_mmq16<12, 12, 14, MMQ_STORE, 0, 1, 0>);
     }
+    if (mode == MMQ_STORE && nseg == 3 && q.mode == 0 && np == 1 && types[0] == 13 && types[1] == 13) {
+        if (types[2] == 13) return go(k_mmq16<13, 13, 13, MMQ_STORE, 0, 1, 0>);
+        if (types[2] == 14) return go(k_mmq16<13, 13, 14, MMQ_STORE, 0, 1, 0>);
+    }
     // Q8_0 q|k|v (one pass, K <= 2048) when MIO_BT_FQ=0 takes it off the dot4 in-launch path
     if (mode == MMQ_STORE && nseg == 3 && q.mode == 0 && np == 1 && types[0] == 8 && types[1] == 8 && types[2] == 8 &&
         a.K % 256 == 0 && a.K <= 2048)
         return go(k_mmq16<8, 8, 8, MMQ_STORE, 1, 1, 0>);
     if (mode == MMQ_SWIGLU && nseg == 1 && q.mode == 0 && np == 1) {
-        if (types[0] == 12) {
+        // Q4_K / Q5_K gate|up
+        auto kq_up = [&]<int T>() {
             // MIO_BT_IQ=1 (opt-in): the walk quantizes its <= 8 tokens in its own prologue instead
             // of behind producer workgroups. Bit-exact, but 8 streams 1.7B 1.366 vs 1.252 ms per
             // step (profiles/r06/bt_iq_ab.txt): one wave per token quantizing 8 superblocks in a
             // row is a longer chain than the producers' hop
             static const bool iq = getenv("MIO_BT_IQ") && getenv("MIO_BT_IQ")[0] == '1';
-            if (iq && a.nt <= 8 && a.K % 256 == 0 && a.K <= 2048 && tiles > n_cu() && mmq_loop_on() &&
+            if (T == 12 && iq && a.nt <= 8 && a.K % 256 == 0 && a.K <= 2048 && tiles > n_cu() && mmq_loop_on() &&
                 (kq_loop_mask() & 2)) {
                 auto kern = k_mmq16_loop_kq<12, MMQ_SWIGLU, 0, 0, true>;
                 const size_t l = (size_t)2 * MMQ_NT * 4 * sizeof(float) + (size_t)(a.K / 256) * TT16 * sizeof(float) +
@@ -1528,13 +1596,15 @@ bool launch_mmq_q(const MmqSeg *seg, const int *types, int nseg, int mode, const
             }
             const int nl = n_cu() - a.nt;  // the producers keep CUs of their own
             if (a.K % 256 == 0 && a.K <= 2048 && tiles > nl && nl > 0 && mmq_loop_on() && (kq_loop_mask() & 2)) {
-                auto kern = k_mmq16_loop_kq<12, MMQ_SWIGLU, 1, 0>;
+                auto kern = k_mmq16_loop_kq<T, MMQ_SWIGLU, 1, 0>;
                 if (lds > 64 * 1024) allow_lds_mmq(reinterpret_cast<const void *>(kern));
                 hipLaunchKernelGGL(kern, dim3(a.nt + nl), dim3(MMQ_NT), lds, s, sg[0], a, q, tiles);
                 return true;
             }
-            return go(k_mmq16<12, -1, -1, MMQ_SWIGLU, 0, 1, 0>);
-        }
+            return go(k_mmq16<T, -1, -1, MMQ_SWIGLU, 0, 1, 0>);
+        };
+        if (types[0] == 12) return kq_up.template operator()<12>();
+        if (types[0] == 13) return kq_up.template operator()<13>();
         if (types[0] == 8 && a.K % 256 == 0 && a.K <= 2048) {
             const int nl = n_cu() - a.nt;  // the producers keep CUs of their own
             if (tiles > nl && nl > 0 && mmq_loop_on()) {
@@ -1548,6 +1618,7 @@ bool launch_mmq_q(const MmqSeg *seg, const int *types, int nseg, int mode, const
     }
     if (mode == MMQ_RESID && nseg == 1 && q.mode == 1 && np == 3) {
         if (types[0] == 12) return go(k_mmq16<12, -1, -1, MMQ_RESID, 0, 3, 1>);
+        if (types[0] == 13) return go(k_mmq16<13, -1, -1, MMQ_RESID, 0, 3, 1>);
         if (types[0] == 14) return go(k_mmq16<14, -1, -1, MMQ_RESID, 0, 3, 1>);
     }
     // Q8_0 down (multi-pass pair path) when MIO_MMQ_MASK puts it on the matrix cores

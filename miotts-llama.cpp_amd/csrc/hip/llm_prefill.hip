@@ -1305,14 +1305,7 @@ void launch_layers(const LlmDims &d, const LayerW *layers, int n_layer, _Float16
                             hipLaunchKernelGGL((k_pf_attn_in<NP, TQ, TV>), dim3(GW), dim3(MT), lds, s, d, L.attn_norm,
                                                L.wq, L.wk, L.wv, g_qk, q, n);
                         };
-                        if constexpr (TQ == 8 || TQ == 30) {
-                            go.template operator()<TQ>();
-                        } else {
-                            if (L.wv.type == 14)
-                                go.template operator()<14>();
-                            else
-                                go.template operator()<12>();
-                        }
+                        dispatch_v<TQ>(L.wv.type, go);
                     });
                 });
             }

@@ -21,6 +21,7 @@ enum GgmlType : uint32_t {
     GGML_Q5_0 = 6,
     GGML_Q8_0 = 8,
     GGML_Q4_K = 12,
+    GGML_Q5_K = 13,
     GGML_Q6_K = 14,
     GGML_Q8_K = 15,
     GGML_I8 = 24,

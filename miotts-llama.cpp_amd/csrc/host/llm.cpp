@@ -193,9 +193,9 @@ bool upload_qmat(mio_hip_llm *m, const mio::GgufTensor *t, mio::QMat &q) {
         return false;
     }
     const bool repack = mio::repacks_to_q8_0(t->type);
-    if (t->type != mio::GGML_Q8_0 && t->type != mio::GGML_Q4_K && t->type != mio::GGML_Q6_K &&
-        t->type != mio::GGML_BF16 && !repack) {
-        mio::set_error("llm: tensor %s has type %s; supported: bf16, q8_0, q4_K, q6_K, q5_0 / q4_0 (run as q8_0)",
+    if (t->type != mio::GGML_Q8_0 && t->type != mio::GGML_Q4_K && t->type != mio::GGML_Q5_K &&
+        t->type != mio::GGML_Q6_K && t->type != mio::GGML_BF16 && !repack) {
+        mio::set_error("llm: tensor %s has type %s; supported: bf16, q8_0, q4_K, q5_K, q6_K, q5_0 / q4_0 (run as q8_0)",
                        t->name.c_str(), mio::ggml_type_name(t->type));
         return false;
     }
@@ -910,6 +910,11 @@ extern "C" int mio_hip_llm_load(mio_hip_device *d, const char *path, int n_ctx, 
             D.n_ff > 12288 ||
             D.n_embd > 64 * 8 * D.n_wg) {
             mio::set_error("llm_load: layer %d shapes / quant families not supported", i);
+            return fail(MIO_ERR_UNSUPPORTED);
+        }
+        if (!mio::attn_v_supported(L.wq.type, L.wv.type)) {
+            mio::set_error("llm_load: layer %d: attn_v %s beside attn_q %s has no kernel", i,
+                           mio::ggml_type_name(L.wv.type), mio::ggml_type_name(L.wq.type));
             return fail(MIO_ERR_UNSUPPORTED);
         }
         m->layers.push_back(L);

@@ -130,8 +130,11 @@ bool repack_to_q8_0(uint32_t type, const void *src, int64_t R, int64_t K, void *
 // Simplified K-quant quantizers (one pass, min/max scales). Any byte pattern of the
 // right layout is a valid model for the synthetic benchmark; these keep the
 // dequantized weights close to the generating N(0, s) values.
-void quantize_row_q4_K(const float *x, void *vy, int64_t k) {
-    BlockQ4_K *y = (BlockQ4_K *)vy;
+// Q4_K (NL = 15) and Q5_K (NL = 31) share the scheme and the scale / min packing; Q5_K's fifth
+// bit of weight e goes to bit e / 32 of qh[e % 32].
+template <class Block, int NL>
+static void quantize_row_q45_K(const float *x, void *vy, int64_t k) {
+    Block *y = (Block *)vy;
     for (int64_t i = 0; i < k / 256; ++i) {
         const float *xb = x + i * 256;
         float scales[8], mins[8];
@@ -143,7 +146,7 @@ void quantize_row_q4_K(const float *x, void *vy, int64_t k) {
                 mx = std::max(mx, xb[32 * j + l]);
             }
             if (mx < 0.0f) mx = 0.0f;
-            scales[j] = (mx - mn) / 15.0f;
+            scales[j] = (mx - mn) / (float)NL;
             mins[j] = -mn;
             max_scale = std::max(max_scale, scales[j]);
             max_min = std::max(max_min, mins[j]);
@@ -174,16 +177,22 @@ void quantize_row_q4_K(const float *x, void *vy, int64_t k) {
             const float dd = d * ls[j], dm = dmin * lm[j];
             for (int l = 0; l < 32; ++l) {
                 int q = dd > 0 ? nearest_int((xb[32 * j + l] + dm) / dd) : 0;
-                L[32 * j + l] = (uint8_t)std::min(15, std::max(0, q));
+                L[32 * j + l] = (uint8_t)std::min(NL, std::max(0, q));
             }
         }
         uint8_t *q = y[i].qs;
         for (int j = 0; j < 256; j += 64) {
-            for (int l = 0; l < 32; ++l) q[l] = L[j + l] | (L[j + l + 32] << 4);
+            for (int l = 0; l < 32; ++l) q[l] = (L[j + l] & 0xF) | ((L[j + l + 32] & 0xF) << 4);
             q += 32;
+        }
+        if constexpr (NL == 31) {
+            std::memset(y[i].qh, 0, 32);
+            for (int e = 0; e < 256; ++e) y[i].qh[e & 31] |= (uint8_t)((L[e] >> 4) << (e >> 5));
         }
     }
 }
+void quantize_row_q4_K(const float *x, void *y, int64_t k) { quantize_row_q45_K<BlockQ4_K, 15>(x, y, k); }
+void quantize_row_q5_K(const float *x, void *y, int64_t k) { quantize_row_q45_K<BlockQ5_K, 31>(x, y, k); }
 
 void quantize_row_q6_K(const float *x, void *vy, int64_t k) {
     BlockQ6_K *y = (BlockQ6_K *)vy;
@@ -239,6 +248,7 @@ bool quantize_row(uint32_t type, const float *x, void *y, int64_t k) {
         case GGML_Q4_0: quantize_row_q4_0(x, y, k); return true;
         case GGML_Q5_0: quantize_row_q5_0(x, y, k); return true;
         case GGML_Q4_K: quantize_row_q4_K(x, y, k); return true;
+        case GGML_Q5_K: quantize_row_q5_K(x, y, k); return true;
         case GGML_Q6_K: quantize_row_q6_K(x, y, k); return true;
         default: return false;
     }
@@ -307,6 +317,24 @@ bool dequantize_row(uint32_t type, const void *vx, float *y, int64_t k) {
             }
             return true;
         }
+        case GGML_Q5_K: {
+            const BlockQ5_K *x = (const BlockQ5_K *)vx;
+            for (int64_t i = 0; i < k / 256; ++i) {
+                const uint8_t *ql = x[i].qs, *qh = x[i].qh, *s = x[i].scales;
+                const float d = fp16_to_f32(x[i].d), min = fp16_to_f32(x[i].dmin);
+                for (int j = 0; j < 8; ++j) {  // sub-block j: nibble j & 1 of chunk j / 2, bit j of qh
+                    const uint8_t sc = j < 4 ? (s[j] & 63) : ((s[j + 4] & 0xF) | ((s[j - 4] >> 6) << 4));
+                    const uint8_t m = j < 4 ? (s[j + 4] & 63) : ((s[j + 4] >> 4) | ((s[j] >> 6) << 4));
+                    const float d1 = d * sc, m1 = min * m;
+                    for (int l = 0; l < 32; ++l) {
+                        const uint8_t b = ql[32 * (j >> 1) + l];
+                        const int q = ((j & 1) ? (b >> 4) : (b & 0xF)) + (((qh[l] >> j) & 1) << 4);
+                        *y++ = d1 * q - m1;
+                    }
+                }
+            }
+            return true;
+        }
         case GGML_Q6_K: {
             const BlockQ6_K *x = (const BlockQ6_K *)vx;
             for (int64_t i = 0; i < k / 256; ++i) {
@@ -350,6 +378,9 @@ SplitLayout split_layout(uint32_t type, int64_t R, int64_t K) {
     switch (type) {
         case GGML_Q8_0: take(0, (size_t)R * K), take(1, (size_t)R * (K / 32) * 2); break;
         case GGML_Q4_K: take(0, (size_t)R * K / 2), take(1, (size_t)R * (K / 256) * 16); break;
+        case GGML_Q5_K:
+            take(0, (size_t)R * K / 2), take(1, (size_t)R * K / 8), take(2, (size_t)R * (K / 256) * 16);
+            break;
         case GGML_Q6_K:
             take(0, (size_t)R * K / 2), take(1, (size_t)R * K / 4), take(2, (size_t)R * K / 16),
                 take(3, (size_t)R * (K / 256) * 2);
@@ -361,6 +392,26 @@ SplitLayout split_layout(uint32_t type, int64_t R, int64_t K) {
     }
     L.bytes = o;
     return L;
+}
+
+// The 16-B split-layout header of a Q4_K / Q5_K superblock: {d, dmin}, then the scales re-packed
+// (same 96 bits) as 4 x 24-bit pairs {sc(2j), m(2j), sc(2j+1), m(2j+1)} at bit 24j, so a lane
+// extracts its pair with one funnel shift
+static void split_header_k4(uint16_t d, uint16_t dmin, const uint8_t *sc, uint8_t *hd) {
+    std::memcpy(hd, &d, 2);
+    std::memcpy(hd + 2, &dmin, 2);
+    for (int j = 0; j < 4; ++j) {
+        uint32_t f = 0;
+        for (int t = 0; t < 2; ++t) {
+            const int sj = 2 * j + t;
+            const uint32_t s = sj < 4 ? (sc[sj] & 63) : ((sc[sj + 4] & 0xF) | ((sc[sj - 4] >> 6) << 4));
+            const uint32_t m = sj < 4 ? (sc[sj + 4] & 63) : ((sc[sj + 4] >> 4) | ((sc[sj] >> 6) << 4));
+            f |= (s | (m << 6)) << (12 * t);
+        }
+        hd[4 + 3 * j + 0] = (uint8_t)f;
+        hd[4 + 3 * j + 1] = (uint8_t)(f >> 8);
+        hd[4 + 3 * j + 2] = (uint8_t)(f >> 16);
+    }
 }
 
 bool to_split(uint32_t type, const void *src, int64_t R, int64_t K, uint8_t *dst) {
@@ -388,23 +439,17 @@ bool to_split(uint32_t type, const void *src, int64_t R, int64_t K, uint8_t *dst
             uint8_t *hd = dst + L.off[1] + (size_t)r * (K / 256) * 16;
             for (int64_t i = 0; i < K / 256; ++i) {
                 std::memcpy(qs + 128 * i, b[i].qs, 128);
-                std::memcpy(hd + 16 * i, &b[i].d, 2);
-                std::memcpy(hd + 16 * i + 2, &b[i].dmin, 2);
-                // scales re-packed (same 96 bits) as 4 x 24-bit pairs {sc(2j), m(2j), sc(2j+1),
-                // m(2j+1)} at bit 24j, so a lane extracts its pair with one funnel shift
-                for (int j = 0; j < 4; ++j) {
-                    uint32_t f = 0;
-                    for (int t = 0; t < 2; ++t) {
-                        const int sj = 2 * j + t;
-                        const uint8_t *sc = b[i].scales;
-                        const uint32_t d = sj < 4 ? (sc[sj] & 63) : ((sc[sj + 4] & 0xF) | ((sc[sj - 4] >> 6) << 4));
-                        const uint32_t m = sj < 4 ? (sc[sj + 4] & 63) : ((sc[sj + 4] >> 4) | ((sc[sj] >> 6) << 4));
-                        f |= (d | (m << 6)) << (12 * t);
-                    }
-                    hd[16 * i + 4 + 3 * j + 0] = (uint8_t)f;
-                    hd[16 * i + 4 + 3 * j + 1] = (uint8_t)(f >> 8);
-                    hd[16 * i + 4 + 3 * j + 2] = (uint8_t)(f >> 16);
-                }
+                split_header_k4(b[i].d, b[i].dmin, b[i].scales, hd + 16 * i);
+            }
+        } else if (type == GGML_Q5_K) {
+            const BlockQ5_K *b = (const BlockQ5_K *)row;
+            uint8_t *qs = dst + L.off[0] + (size_t)r * K / 2;
+            uint8_t *qh = dst + L.off[1] + (size_t)r * K / 8;
+            uint8_t *hd = dst + L.off[2] + (size_t)r * (K / 256) * 16;
+            for (int64_t i = 0; i < K / 256; ++i) {
+                std::memcpy(qs + 128 * i, b[i].qs, 128);
+                std::memcpy(qh + 32 * i, b[i].qh, 32);
+                split_header_k4(b[i].d, b[i].dmin, b[i].scales, hd + 16 * i);
             }
         } else {  // Q6_K
             const BlockQ6_K *b = (const BlockQ6_K *)row;

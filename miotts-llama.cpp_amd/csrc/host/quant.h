@@ -1,10 +1,11 @@
 // ggml block quant formats (public ggml spec) on the host:
-// fp16 conversion, row quantizers (used to make synthetic Q8_0 / Q4_K_M models),
+// fp16 conversion, row quantizers (used to make synthetic Q8_0 / Q4_K_M / Q5_K_M models),
 // row dequantizers (embedding get_rows), and the re-layout of a GGUF quantized matrix
 // into the "split" layout the gfx950 matvec kernels stream:
 //
 //   Q8_0 : qs [R][K]      int8          | d  [R][K/32]  f16
 //   Q4_K : qs [R][K/2]    u8 nibbles    | hd [R][K/256] 16 B = {d, dmin, 4 x 24-bit scale pairs}
+//   Q5_K : qs [R][K/2]    u8 nibbles    | qh [R][K/8] u8 fifth-bit plane | hd [R][K/256] 16 B as Q4_K's
 //   Q6_K : ql [R][K/2]    u8            | qh [R][K/4] u8 | sc [R][K/16] i8 (lane-pair order) | d [R][K/256] f16
 //
 // Same bytes per weight as GGUF (algorithmic bytes unchanged); each row's quant payload
@@ -38,6 +39,13 @@ struct BlockQ4_K {
     uint8_t scales[12];
     uint8_t qs[128];
 };
+// Q4_K plus one plane of fifth bits: weight e of sub-block j = e / 32 has bit (qh[e % 32] >> j) & 1
+struct BlockQ5_K {
+    uint16_t d, dmin;
+    uint8_t scales[12];
+    uint8_t qh[32];
+    uint8_t qs[128];
+};
 struct BlockQ6_K {
     uint8_t ql[128];
     uint8_t qh[64];
@@ -49,6 +57,7 @@ static_assert(sizeof(BlockQ8_0) == 34, "q8_0");
 static_assert(sizeof(BlockQ4_0) == 18, "q4_0");
 static_assert(sizeof(BlockQ5_0) == 22, "q5_0");
 static_assert(sizeof(BlockQ4_K) == 144, "q4_K");
+static_assert(sizeof(BlockQ5_K) == 176, "q5_K");
 static_assert(sizeof(BlockQ6_K) == 210, "q6_K");
 
 float fp16_to_f32(uint16_t h);
@@ -59,6 +68,7 @@ void quantize_row_q8_0(const float *x, void *y, int64_t k);
 void quantize_row_q4_0(const float *x, void *y, int64_t k);
 void quantize_row_q5_0(const float *x, void *y, int64_t k);
 void quantize_row_q4_K(const float *x, void *y, int64_t k);
+void quantize_row_q5_K(const float *x, void *y, int64_t k);
 void quantize_row_q6_K(const float *x, void *y, int64_t k);
 bool quantize_row(uint32_t type, const float *x, void *y, int64_t k);
 bool dequantize_row(uint32_t type, const void *x, float *y, int64_t k);

@@ -12,8 +12,8 @@
 extern "C" int mio_hip_debug_matvec(mio_hip_device *d, uint32_t type, const void *gguf_rows, int rows, int k,
                                     const float *x, float *y) {
     MIO_REQUIRE(d && gguf_rows && x && y && rows > 0 && k > 0, MIO_ERR_INVALID, "debug_matvec: bad args");
-    MIO_REQUIRE(type == mio::GGML_Q8_0 || type == mio::GGML_Q4_K || type == mio::GGML_Q6_K ||
-                    type == mio::GGML_BF16 || mio::repacks_to_q8_0(type),
+    MIO_REQUIRE(type == mio::GGML_Q8_0 || type == mio::GGML_Q4_K || type == mio::GGML_Q5_K ||
+                    type == mio::GGML_Q6_K || type == mio::GGML_BF16 || mio::repacks_to_q8_0(type),
                 MIO_ERR_UNSUPPORTED, "debug_matvec: type %u", type);
     const bool k32 = type == mio::GGML_Q8_0 || type == mio::GGML_BF16 || mio::repacks_to_q8_0(type);
     MIO_REQUIRE(k % (k32 ? 32 : 256) == 0, MIO_ERR_INVALID, "debug_matvec: k %d", k);
@@ -51,8 +51,9 @@ extern "C" int mio_hip_debug_mmq(mio_hip_device *d, uint32_t type, const void *g
     MIO_REQUIRE(d && gguf_rows && x && y && rows > 0 && k > 0 && nt > 0 && nt <= 4096 && mode >= 0 && mode <= 2 &&
                     (mode != 2 || gguf_up),
                 MIO_ERR_INVALID, "debug_mmq: bad args");
-    MIO_REQUIRE(type == mio::GGML_Q8_0 || type == mio::GGML_Q4_K || type == mio::GGML_Q6_K, MIO_ERR_UNSUPPORTED,
-                "debug_mmq: type %u", type);
+    MIO_REQUIRE(type == mio::GGML_Q8_0 || type == mio::GGML_Q4_K || type == mio::GGML_Q5_K ||
+                    type == mio::GGML_Q6_K,
+                MIO_ERR_UNSUPPORTED, "debug_mmq: type %u", type);
     MIO_REQUIRE(k % (type == mio::GGML_Q8_0 ? 32 : 256) == 0, MIO_ERR_INVALID, "debug_mmq: k %d", k);
     int rc = mio::bind(d);
     if (rc) return rc;
@@ -90,5 +91,15 @@ extern "C" int mio_quantize_rows(uint32_t type, const float *x, int rows, int k,
     MIO_REQUIRE(rb, MIO_ERR_UNSUPPORTED, "quantize_rows: type %u / k %d", type, k);
     for (int r = 0; r < rows; ++r)
         if (!mio::quantize_row(type, x + (size_t)r * k, (uint8_t *)out + r * rb, k)) return MIO_ERR_UNSUPPORTED;
+    return MIO_OK;
+}
+
+extern "C" int mio_dequantize_rows(uint32_t type, const void *rows_bytes, int rows, int k, float *out) {
+    MIO_REQUIRE(rows_bytes && out && rows > 0 && k > 0, MIO_ERR_INVALID, "dequantize_rows: bad args");
+    const size_t rb = mio::ggml_row_bytes(type, k);
+    MIO_REQUIRE(rb, MIO_ERR_UNSUPPORTED, "dequantize_rows: type %u / k %d", type, k);
+    for (int r = 0; r < rows; ++r)
+        if (!mio::dequantize_row(type, (const uint8_t *)rows_bytes + r * rb, out + (size_t)r * k, k))
+            return MIO_ERR_UNSUPPORTED;
     return MIO_OK;
 }

@@ -33,7 +33,9 @@ struct SynthLlmCfg {
     int n_embd = 256, n_layer = 2, n_head = 4, n_head_kv = 2, head_dim = 64, n_ff = 512;
     int n_vocab = 13312, n_ctx = 4096;
     float rope_base = 10000.f, rms_eps = 1e-6f, w_std = 0.02f;
-    int qtype = 8;   // 8 = all Q8_0; 15 = Q4_K_M mix (Q4_K + Q6_K); 2 = Q4_0; 30 = all BF16
+    // 8 = all Q8_0; 15 = Q4_K_M mix (Q4_K + Q6_K); 17 = Q5_K_M mix (Q5_K + Q6_K); 16 = Q5_K_S (Q5_K,
+    // Q6_K output); 2 = Q4_0; 30 = all BF16
+    int qtype = 8;
     // llama-quantize's fallback for rows whose length is not a multiple of 256: Q4_K -> Q5_0,
     // Q6_K -> Q8_0 (llama-quant.cpp); Q4_K_M files of the 0.1B model (n_embd 576) carry them
     bool kq_fallback = true;
@@ -49,8 +51,13 @@ struct SynthLlmCfg {
 //         width, FFN, vocab and GQA; short-conv / attention layer hybrid), 7 tiny Q8_0 lfm2,
 //         8 tiny Q4_K_M lfm2, 9 tiny Q4_K_M at the 0.1B width (n_embd 576: q/k/v, O, gate/up and
 //         the embedding fall back to Q5_0 / Q8_0 as llama-quantize does), 10 tiny Q4_0,
-//         11 tiny BF16 (qwen3), 12 "1.7B" BF16
+//         11 tiny BF16 (qwen3), 12 "1.7B" BF16, 13 tiny Q5_K_M (qwen3, 3 layers: attn_v / ffn_down
+//         Q5_K on layers 0-1, Q6_K on layer 2), 14 tiny Q5_K_S (llama, untied: token_embd Q5_K,
+//         output Q6_K), 15 tiny Q5_K_M lfm2, 16 "1.7B" Q5_K_M
+constexpr int kSynthLlmPresets = 17;
 SynthLlmCfg synth_llm_preset(int preset);
+// null, or why the writer refuses the configuration
+const char *synth_llm_check(const SynthLlmCfg &cfg);
 bool synth_write_llm(const std::string &path, const SynthLlmCfg &cfg);
 // Token ids of the synthetic vocabulary.
 constexpr int kSynthTokStartOfText = 256, kSynthTokImStart = 257, kSynthTokImEnd = 258,

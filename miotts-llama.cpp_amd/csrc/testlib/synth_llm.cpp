@@ -1,6 +1,7 @@
 // Synthetic LLM GGUF writer (see synth.h). Tensor names / KV keys follow llama.cpp's
 // GGUF conventions; quant types follow llama.cpp's Q4_K_M recipe: Q4_K everywhere,
-// Q6_K for attn_v / ffn_down on "use_more_bits" layers and for the (tied) output.
+// Q6_K for attn_v / ffn_down on "use_more_bits" layers and for the (tied) output. Q5_K_M is the
+// same recipe with Q5_K for Q4_K; Q5_K_S has Q5_K everywhere and a Q6_K output.
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -79,9 +80,32 @@ SynthLlmCfg synth_llm_preset(int p) {
             c = synth_llm_preset(3);
             c.name = "MioTTS-1.7B-bf16-synthetic", c.qtype = 30;
             break;
+        case 13:  // use_more_bits picks layer 2 of 3: both attn_v / ffn_down mixes occur
+            c.name = "tiny-q5km", c.arch = "qwen3", c.n_layer = 3, c.n_ff = 768, c.qtype = 17;
+            c.rope_base = 1000000.f;
+            break;
+        case 14:
+            c.name = "tiny-q5ks", c.qtype = 16, c.tied = false;
+            break;
+        case 15:
+            c = synth_llm_preset(8);
+            c.name = "tiny-lfm2-q5km", c.qtype = 17;
+            break;
+        case 16:
+            c = synth_llm_preset(3);
+            c.name = "MioTTS-1.7B-q5km-synthetic", c.qtype = 17;
+            break;
         default: break;
     }
     return c;
+}
+
+const char *synth_llm_check(const SynthLlmCfg &c) {
+    // llama-quantize turns Q5_K rows that are not whole 256-element superblocks into Q5_1, which
+    // the loader refuses: such a file would be of no use
+    if ((c.qtype == 16 || c.qtype == 17) && (c.n_embd % 256 || c.n_ff % 256 || (c.n_head * c.head_dim) % 256))
+        return "Q5_K_S / Q5_K_M need n_embd, n_ff and n_head * head_dim to be multiples of 256";
+    return nullptr;
 }
 
 // GPT-2 byte-level unicode for byte b (bytes_to_unicode), UTF-8 encoded
@@ -113,13 +137,16 @@ bool synth_lfm2_is_attn(const SynthLlmCfg &c, int i) {
 }
 
 bool synth_write_llm(const std::string &path, const SynthLlmCfg &c) {
+    if (synth_llm_check(c)) return false;
     GgufWriter w;
     const std::string a = c.arch;
     const bool lfm2 = a == "lfm2";
     w.kv_str("general.architecture", a);
     w.kv_str("general.name", c.name);
-    // llama_ftype: 7 MOSTLY_Q8_0, 15 MOSTLY_Q4_K_M, 2 MOSTLY_Q4_0, 32 MOSTLY_BF16
-    w.kv_u32("general.file_type", c.qtype == 15 ? 15 : (c.qtype == 2 ? 2 : (c.qtype == 30 ? 32 : 7)));
+    // llama_ftype: 7 MOSTLY_Q8_0, 15 MOSTLY_Q4_K_M, 16 MOSTLY_Q5_K_S, 17 MOSTLY_Q5_K_M, 2 MOSTLY_Q4_0,
+    // 32 MOSTLY_BF16
+    const bool kmix = c.qtype == 15 || c.qtype == 16 || c.qtype == 17;
+    w.kv_u32("general.file_type", kmix ? c.qtype : (c.qtype == 2 ? 2 : (c.qtype == 30 ? 32 : 7)));
     w.kv_u32(a + ".context_length", c.n_ctx);
     w.kv_u32(a + ".embedding_length", c.n_embd);
     w.kv_u32(a + ".block_count", c.n_layer);
@@ -164,11 +191,15 @@ bool synth_write_llm(const std::string &path, const SynthLlmCfg &c) {
     };
     std::vector<T> ts;
     auto pick = [&](uint32_t k_mix, uint32_t q4) -> uint32_t {
-        return c.qtype == 15 ? k_mix : (c.qtype == 2 ? q4 : (c.qtype == 30 ? (uint32_t)GGML_BF16 : GGML_Q8_0));
+        return kmix ? k_mix : (c.qtype == 2 ? q4 : (c.qtype == 30 ? (uint32_t)GGML_BF16 : GGML_Q8_0));
     };
-    const uint32_t base = pick(GGML_Q4_K, GGML_Q4_0), more = pick(GGML_Q6_K, GGML_Q4_0);
+    // K-quant mixes: base everywhere, `more` for attn_v / ffn_down on use_more_bits layers (the
+    // _S mix has none), Q6_K for the output matrix (the tied embedding is one)
+    const uint32_t kbase = c.qtype == 15 ? GGML_Q4_K : GGML_Q5_K;
+    const uint32_t base = pick(kbase, GGML_Q4_0), more = pick(c.qtype == 16 ? kbase : GGML_Q6_K, GGML_Q4_0);
+    const uint32_t outp = pick(GGML_Q6_K, GGML_Q4_0);
     const int q_dim = c.n_head * c.head_dim, kv_dim = c.n_head_kv * c.head_dim;
-    const uint32_t emb = pick(GGML_Q6_K, GGML_Q4_0);
+    const uint32_t emb = c.tied ? outp : pick(c.qtype == 15 ? GGML_Q6_K : kbase, GGML_Q4_0);
     ts.push_back({"token_embd.weight", emb, c.n_embd, c.n_vocab, false});
     for (int i = 0; i < c.n_layer; ++i) {
         const std::string p = "blk." + std::to_string(i) + ".";
@@ -201,7 +232,7 @@ bool synth_write_llm(const std::string &path, const SynthLlmCfg &c) {
     }
     // lfm2's final norm is token_embd_norm (llama.cpp model.tok_norm)
     ts.push_back({lfm2 ? "token_embd_norm.weight" : "output_norm.weight", GGML_F32, c.n_embd, 1, true});
-    if (!c.tied) ts.push_back({"output.weight", more, c.n_embd, c.n_vocab, false});
+    if (!c.tied) ts.push_back({"output.weight", outp, c.n_embd, c.n_vocab, false});
     // llama-quantize: a K-quant needs rows of whole 256-element super-blocks
     if (c.kq_fallback)
         for (auto &t : ts)

@@ -132,6 +132,7 @@ def _declare(L: ctypes.CDLL) -> None:
         "mio_hip_llm_kv_rows": (c_int, [_vp, c_int, c_int, _vp, _vp]),
         "mio_hip_debug_matvec": (c_int, [_vp, ctypes.c_uint32, _vp, c_int, c_int, _vp, _vp]),
         "mio_quantize_rows": (c_int, [ctypes.c_uint32, _vp, c_int, c_int, _vp]),
+        "mio_dequantize_rows": (c_int, [ctypes.c_uint32, _vp, c_int, c_int, _vp]),
         "mio_hip_debug_mmq": (c_int, [_vp, ctypes.c_uint32, _vp, c_int, c_int, _vp, c_int, c_int, _vp, _vp]),
         "mio_hip_llm_info": (c_int, [_vp, _i32p]),
         "mio_hip_llm_weight_bytes": (c_int, [_vp, ctypes.POINTER(ctypes.c_uint64)]),
@@ -596,7 +597,8 @@ class Llm:
         return [out[b, : n[b]].copy() for b in range(B)]
 
 
-GGML_BLOCK = {2: (32, 18), 6: (32, 22), 8: (32, 34), 12: (256, 144), 14: (256, 210), 30: (1, 2)}
+GGML_BLOCK = {2: (32, 18), 6: (32, 22), 8: (32, 34), 12: (256, 144), 13: (256, 176), 14: (256, 210),
+              30: (1, 2)}
 
 
 def quantize_rows(qtype: int, x: np.ndarray) -> np.ndarray:
@@ -606,6 +608,17 @@ def quantize_rows(qtype: int, x: np.ndarray) -> np.ndarray:
     be, bb = GGML_BLOCK[qtype]
     out = np.zeros((rows, k // be * bb), np.uint8)
     check(lib().mio_quantize_rows(qtype, _ptr(x), rows, k, _ptr(out)))
+    return out
+
+
+def dequantize_rows(qtype: int, rows_bytes: np.ndarray, k: int) -> np.ndarray:
+    """Host dequantizer (csrc/host/quant.cpp dequantize_row) on GGUF block bytes [rows][row_bytes]
+    -> f32 [rows][k]."""
+    rows_bytes = np.ascontiguousarray(rows_bytes, dtype=np.uint8)
+    be, bb = GGML_BLOCK[qtype]
+    assert rows_bytes.ndim == 2 and rows_bytes.shape[1] == k // be * bb, rows_bytes.shape
+    out = np.empty((rows_bytes.shape[0], k), np.float32)
+    check(lib().mio_dequantize_rows(qtype, _ptr(rows_bytes), rows_bytes.shape[0], k, _ptr(out)))
     return out
 
 
