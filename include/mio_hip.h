@@ -119,7 +119,10 @@ int mio_hip_codec_decode_pcm(mio_hip_codec *c, const int32_t *codes, int n_codes
  * MIO_CODEC_STREAMS (default 3) streams at once, each with its own workspace, so one decode's
  * small GEMM grids and row kernels leave the CUs to the others; every utterance's arithmetic is
  * mio_hip_codec_decode_pcm's (same kernels, same tiling: bit-identical PCM). Joined on `stream`
- * before return. Flags as mio_hip_codec_decode_pcm (no MIO_CODEC_INCREMENTAL). */
+ * before return. Flags as mio_hip_codec_decode_pcm (no MIO_CODEC_INCREMENTAL). Host codes
+ * of every utterance are checked against [0, n_codes) before anything is queued; an error
+ * after that still joins the lanes on `stream` (and, with host output, waits for it), so
+ * nothing is left writing out_pcm when the call returns. */
 int mio_hip_codec_decode_pcm_batch(mio_hip_codec *c, const int32_t *const *codes, const int *n_codes, int B,
                                    const float *global_emb, float *const *out_pcm, int *out_len,
                                    unsigned flags, void *stream);

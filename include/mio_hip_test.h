@@ -26,6 +26,58 @@ int mio_dequantize_rows(uint32_t type, const void *rows_bytes, int rows, int k, 
 int mio_hip_debug_mmq(mio_hip_device *d, uint32_t type, const void *gguf_rows, int rows, int k,
                       const float *x, int nt, int mode, const void *gguf_up, float *y);
 
+/* ---------------- MioCodec kernels, one launch each ----------------
+ * Parity entry points of csrc/hip/codec_kernels.hip (csrc/testlib/debug_codec_capi.cpp). Every
+ * pointer is host memory; a call uploads its operands, launches on the device's stream, waits
+ * and downloads. Every output lives between two 256-byte guard zones, and guards and output
+ * are filled with a sentinel (a quiet NaN with a payload) before the launch, so that a write
+ * outside the buffer and an element no thread wrote both show: *guards_ok is 1 when both
+ * zones still hold the sentinel, and an unwritten output element comes back as the sentinel.
+ * (Outputs that are also inputs - the GEMM's C, an in-place row norm, a conv residual that
+ * aliases Y - carry the caller's values between the guards instead.)
+ * Arguments outside a kernel's documented preconditions are refused with MIO_ERR_INVALID. */
+#define MIO_DEBUG_SENTINEL_F32 0x7FC5A5A5u
+#define MIO_DEBUG_SENTINEL_F16 0x7E5Au
+
+/* GemmArgs (csrc/hip/codec_kernels.h) field for field, plus the epilogue, the K-group count
+ * (0: launch_gemm_f32 picks it and the tile order; 1, 2, 4: launch_gemm_f32_cfg(.., kg, 11))
+ * and the row count of C (M rows, rows_out for the ConvT epilogues). */
+typedef struct mio_debug_gemm {
+    int a_seg, a_row_off, a_rows;
+    int M, N, K;
+    int ldc, c_rows;
+    int f, trim, cout, rows_out;
+    int m_major; /* passed through; both launchers overwrite it */
+    int a_f16;
+    int epi, kg;
+} mio_debug_gemm;
+/* A [a_rows][a_seg], B [N][K], C [c_rows][ldc] in/out; bias / aux / aux2 may be NULL where the
+ * epilogue does not read them (per column: N values; ConvT epilogues: cout values). */
+int mio_hip_debug_codec_gemm(mio_hip_device *d, const mio_debug_gemm *g, const float *A, const float *B,
+                             float *C, const float *bias, const float *aux, const float *aux2,
+                             int *guards_ok);
+/* launch_conv_f16: xa [L][Cin] and w [Cout][taps*Cin] are f16 bit patterns, y [L][Cout].
+ * resid_mode 0: no residual; 1: resid [L][Cout] is a buffer of its own; 2: the residual
+ * aliases Y (y holds it on entry). */
+int mio_hip_debug_codec_conv(mio_hip_device *d, const uint16_t *xa, int L, int Cin, int taps, int pad,
+                             const uint16_t *w, int Cout, const float *bias, int resid_mode,
+                             const float *resid, float *y, int *guards_ok);
+/* launch_rownorm on x [M][D]; in_place: y is the x buffer (y still receives the result). */
+int mio_hip_debug_codec_rownorm(mio_hip_device *d, const float *x, int M, int D, float eps, int mode,
+                                const float *p0, const float *p1, int in_place, float *y, int *guards_ok);
+/* launch_groupnorm_apply on x [L][C] (MIO_GN picks the pipeline): xa [L][C] f16 bit patterns. */
+int mio_hip_debug_codec_groupnorm(mio_hip_device *d, const float *x, int L, int C, int G, float eps,
+                                  const float *gamma, const float *beta, uint16_t *xa, int *guards_ok);
+/* launch_band_attention: qkv [S][3*H*64], rope [S][32] (cos, sin) pairs, out [S][H*64]. */
+int mio_hip_debug_codec_band_attention(mio_hip_device *d, const float *qkv, int S, int H, int window,
+                                       const float *rope, float *out, int *guards_ok);
+/* launch_cond_gemv: W [R][A], b [R], e [A] -> y [R]. */
+int mio_hip_debug_codec_cond_gemv(mio_hip_device *d, const float *W, const float *b, const float *e, int R,
+                                  int A, int e_f16, float *y, int *guards_ok);
+/* launch_embed: table [n_rows][D], codes [T] in [0, n_rows) -> x [T][D]. */
+int mio_hip_debug_codec_embed(mio_hip_device *d, const float *table, int n_rows, int D, const int32_t *codes,
+                              int T, float *x, int *guards_ok);
+
 /* ---------------- synthetic model files ----------------
  * No GGUF model files exist offline. These write files with the
  * reference's tensor names and KV keys (miocodec.cpp:448-481, 599-728;

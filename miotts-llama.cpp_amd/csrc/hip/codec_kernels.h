@@ -17,6 +17,11 @@ enum GemmEpi : int {
     EPI_HEAD = 7,       // B rows interleaved per 32 (logmag|phase): spec[m][k] = polar
 };
 
+// Precondition: K % 4 == 0 and a_seg % 4 == 0 (A and B 16-byte aligned). Every operand load
+// is a float4 masked by its first element only (k < K, source row inside [0, a_rows)), so a
+// K or a row length that is no multiple of 4 would take the tail of the load from the next
+// row. The loader guarantees it (model widths are multiples of 64, ff % 16 == 0, upsampler
+// channels % 4 == 0).
 struct GemmArgs {
     const float *A;   // element (m,k) at A[(m + a_row_off) * a_seg + k]
     int a_seg;        // floats per source row (Cin); K = taps * a_seg

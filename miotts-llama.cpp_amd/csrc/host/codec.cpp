@@ -927,34 +927,56 @@ extern "C" int mio_hip_codec_decode_pcm_batch(mio_hip_codec *c, const int32_t *c
         Ws w;
         if ((rc = plan_ws(c, tmax, w, true, nullptr, k))) return rc;
     }
+    // host codes are checked before anything is queued: a refusal leaves no lane running
+    if (!(flags & MIO_IN_DEVICE))
+        for (int b = 0; b < B; ++b)
+            for (int i = 0; i < n_codes[b]; ++i)
+                MIO_REQUIRE(codes[b][i] >= 0 && codes[b][i] < c->n_codes, MIO_ERR_INVALID,
+                            "miocodec: utterance %d: code %d at %d outside [0, %d)", b, codes[b][i], i, c->n_codes);
     MIO_HIP_CHECK(hipEventRecord(c->ev[0], s));
     for (int k = 1; k < NS; ++k) MIO_HIP_CHECK(hipStreamWaitEvent(c->xs[k - 1], c->ev[0], 0));
     double flops = 0.0;
-    for (int b = 0; b < B; ++b) {
-        const int k = b % NS;
-        hipStream_t ls = k ? c->xs[k - 1] : s;
-        Ws w;
-        if ((rc = plan_ws(c, n_codes[b], w, false, nullptr, k))) return rc;
-        if ((rc = prepare_inputs(c, w, codes[b], n_codes[b], emb, flags, ls))) return rc;
-        const float *buf = nullptr;
-        int r = 0, cc = 0;
-        t_flops = 0.0;
-        if ((rc = run_decode(c, w, ls, 1 << 20, &buf, &r, &cc))) return rc;
-        flops += t_flops;
-        int len = 0;
-        if ((rc = mio_hip_istft_out_len(c->ist, w.Lf, c->hop, &len))) return rc;
-        if (flags & MIO_OUT_DEVICE) {
-            if ((rc = mio_istft_launch_device(c->ist, w.spec, w.Lf, c->hop, out_pcm[b], ls))) return rc;
-        } else {
-            if ((rc = mio_istft_launch_device(c->ist, w.spec, w.Lf, c->hop, w.pcm, ls))) return rc;
-            MIO_HIP_CHECK(hipMemcpyAsync(out_pcm[b], w.pcm, (size_t)len * 4, hipMemcpyDeviceToHost, ls));
+    auto issue = [&]() -> int {
+        int rc = MIO_OK;
+        for (int b = 0; b < B; ++b) {
+            const int k = b % NS;
+            hipStream_t ls = k ? c->xs[k - 1] : s;
+            Ws w;
+            if ((rc = plan_ws(c, n_codes[b], w, false, nullptr, k))) return rc;
+            if ((rc = prepare_inputs(c, w, codes[b], n_codes[b], emb, flags, ls))) return rc;
+            const float *buf = nullptr;
+            int r = 0, cc = 0;
+            t_flops = 0.0;
+            if ((rc = run_decode(c, w, ls, 1 << 20, &buf, &r, &cc))) return rc;
+            flops += t_flops;
+            int len = 0;
+            if ((rc = mio_hip_istft_out_len(c->ist, w.Lf, c->hop, &len))) return rc;
+            if (flags & MIO_OUT_DEVICE) {
+                if ((rc = mio_istft_launch_device(c->ist, w.spec, w.Lf, c->hop, out_pcm[b], ls))) return rc;
+            } else {
+                if ((rc = mio_istft_launch_device(c->ist, w.spec, w.Lf, c->hop, w.pcm, ls))) return rc;
+                MIO_HIP_CHECK(hipMemcpyAsync(out_pcm[b], w.pcm, (size_t)len * 4, hipMemcpyDeviceToHost, ls));
+            }
+            if (out_len) out_len[b] = len;
         }
-        if (out_len) out_len[b] = len;
-    }
+        return MIO_OK;
+    };
+    rc = issue();
+    // the lanes join s whether or not every utterance was issued: after an error the earlier
+    // lanes are still queued and still write the caller's out_pcm
+    int jrc = MIO_OK;
     for (int k = 1; k < NS; ++k) {
-        MIO_HIP_CHECK(hipEventRecord(c->xev[k - 1], c->xs[k - 1]));
-        MIO_HIP_CHECK(hipStreamWaitEvent(s, c->xev[k - 1], 0));
+        if (hipEventRecord(c->xev[k - 1], c->xs[k - 1]) != hipSuccess ||
+            hipStreamWaitEvent(s, c->xev[k - 1], 0) != hipSuccess) {
+            hipStreamSynchronize(c->xs[k - 1]);  // no join through s: wait for the lane here
+            jrc = MIO_ERR_HIP;
+        }
     }
+    if (rc) {  // the first error's text stands; host buffers are quiet when the caller sees it
+        if (!(flags & MIO_OUT_DEVICE)) hipStreamSynchronize(s);
+        return rc;
+    }
+    MIO_REQUIRE(jrc == MIO_OK, MIO_ERR_HIP, "codec_decode_pcm_batch: joining the lane streams failed");
     MIO_HIP_CHECK(hipGetLastError());
     // last_timings: codec = the whole batch (decodes and iSTFTs overlap), iSTFT 0
     MIO_HIP_CHECK(hipEventRecord(c->ev[1], s));

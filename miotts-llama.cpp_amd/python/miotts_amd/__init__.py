@@ -134,6 +134,18 @@ def _declare(L: ctypes.CDLL) -> None:
         "mio_quantize_rows": (c_int, [ctypes.c_uint32, _vp, c_int, c_int, _vp]),
         "mio_dequantize_rows": (c_int, [ctypes.c_uint32, _vp, c_int, c_int, _vp]),
         "mio_hip_debug_mmq": (c_int, [_vp, ctypes.c_uint32, _vp, c_int, c_int, _vp, c_int, c_int, _vp, _vp]),
+        "mio_hip_debug_codec_gemm": (c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(c_int)]),
+        "mio_hip_debug_codec_conv": (c_int, [_vp, _vp, c_int, c_int, c_int, c_int, _vp, c_int, _vp, c_int, _vp, _vp,
+                                             ctypes.POINTER(c_int)]),
+        "mio_hip_debug_codec_rownorm": (c_int, [_vp, _vp, c_int, c_int, ctypes.c_float, c_int, _vp, _vp, c_int, _vp,
+                                                ctypes.POINTER(c_int)]),
+        "mio_hip_debug_codec_groupnorm": (c_int, [_vp, _vp, c_int, c_int, c_int, ctypes.c_float, _vp, _vp, _vp,
+                                                  ctypes.POINTER(c_int)]),
+        "mio_hip_debug_codec_band_attention": (c_int, [_vp, _vp, c_int, c_int, c_int, _vp, _vp,
+                                                       ctypes.POINTER(c_int)]),
+        "mio_hip_debug_codec_cond_gemv": (c_int, [_vp, _vp, _vp, _vp, c_int, c_int, c_int, _vp,
+                                                  ctypes.POINTER(c_int)]),
+        "mio_hip_debug_codec_embed": (c_int, [_vp, _vp, c_int, c_int, _vp, c_int, _vp, ctypes.POINTER(c_int)]),
         "mio_hip_llm_info": (c_int, [_vp, _i32p]),
         "mio_hip_llm_weight_bytes": (c_int, [_vp, ctypes.POINTER(ctypes.c_uint64)]),
         "mio_hip_llm_eval": (c_int, [_vp, ctypes.c_int32, c_int, _vp]),
@@ -410,9 +422,23 @@ class Codec:
                                                    MIO_IN_DEVICE | MIO_OUT_DEVICE, stream or None))
         return [int(x) for x in ln]
 
-    def decode_pcm_batch(self, codes, emb):
-        """Host convenience of decode_pcm_batch_device: list of code arrays -> list of PCM."""
+    def decode_pcm_batch(self, codes, emb, host: bool = False):
+        """Host convenience of decode_pcm_batch_device: list of code arrays -> list of PCM.
+        host: pass host pointers with no MIO_*_DEVICE flag, as tts.cpp does (the call checks the
+        codes, copies them itself and returns with the PCM in host memory)."""
         dev = self.dev
+        if host:
+            B = len(codes)
+            hc = [np.ascontiguousarray(c, np.int32) for c in codes]
+            he = np.ascontiguousarray(emb, np.float32)
+            ho = [np.empty(len(c) * self.samples_per_token + self.n_fft, np.float32) for c in hc]
+            cp = (ctypes.c_void_p * B)(*[_ptr(c) for c in hc])
+            op = (ctypes.c_void_p * B)(*[_ptr(o) for o in ho])
+            nc = (ctypes.c_int * B)(*[len(c) for c in hc])
+            ln = (ctypes.c_int * B)()
+            check(lib().mio_hip_codec_decode_pcm_batch(self.h, ctypes.cast(cp, _vp), ctypes.cast(nc, _vp), B, _ptr(he),
+                                                       ctypes.cast(op, _vp), ctypes.cast(ln, _vp), 0, None))
+            return [o[:int(n)] for o, n in zip(ho, ln)]
         d_codes = [dev.upload(np.ascontiguousarray(c, np.int32)) for c in codes]
         d_emb = dev.upload(np.ascontiguousarray(emb, np.float32))
         outs = [dev.empty((len(c) * self.samples_per_token + self.n_fft,), np.float32) for c in codes]
@@ -641,6 +667,123 @@ def debug_mmq(dev: Device, qtype: int, w_rows: np.ndarray, k: int, x: np.ndarray
     check(lib().mio_hip_debug_mmq(dev.h, qtype, _ptr(w_rows), w_rows.shape[0], k, _ptr(x), x.shape[0], mode,
                                   _ptr(up) if up is not None else None, _ptr(y)))
     return y
+
+
+# MioCodec kernels, one launch each (include/mio_hip_test.h). Every helper returns
+# (output, guards_ok): the output between its guard zones, and whether both zones still hold
+# the sentinel. An element no thread wrote comes back as the sentinel bit pattern.
+SENTINEL_F32 = 0x7FC5A5A5
+SENTINEL_F16 = 0x7E5A
+EPI_STORE, EPI_RESID, EPI_GATED, EPI_SWIGLU, EPI_CONVT, EPI_CONVT_SNAKE, EPI_SNAKE, EPI_HEAD = range(8)
+
+
+class _DebugGemm(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int) for n in ("a_seg", "a_row_off", "a_rows", "M", "N", "K", "ldc", "c_rows", "f", "trim",
+                                            "cout", "rows_out", "m_major", "a_f16", "epi", "kg")]
+
+
+def sentinel_f32(shape) -> np.ndarray:
+    return np.full(shape, SENTINEL_F32, np.uint32).view(np.float32)
+
+
+def _opt_f32(a):
+    return None if a is None else np.ascontiguousarray(a, dtype=np.float32)
+
+
+def debug_codec_gemm(dev: Device, A: np.ndarray, B: np.ndarray, C: np.ndarray, M: int, epi: int = EPI_STORE,
+                     kg: int = 0, a_row_off: int = 0, bias=None, aux=None, aux2=None, f: int = 0, trim: int = 0,
+                     cout: int = 0, rows_out: int = 0, a_f16: int = 0, m_major: int = 0):
+    """One gemm_f32_kernel launch (GemmArgs field for field): A [a_rows][a_seg], B [N][K],
+    C [c_rows][ldc] (copied; in/out). kg 0: launch_gemm_f32 picks the K-groups; 1, 2, 4 forced."""
+    A = np.ascontiguousarray(A, dtype=np.float32)
+    B = np.ascontiguousarray(B, dtype=np.float32)
+    C = np.array(C, dtype=np.float32, order="C")
+    bias, aux, aux2 = _opt_f32(bias), _opt_f32(aux), _opt_f32(aux2)
+    g = _DebugGemm(a_seg=A.shape[1], a_row_off=a_row_off, a_rows=A.shape[0], M=M, N=B.shape[0], K=B.shape[1],
+                   ldc=C.shape[1], c_rows=C.shape[0], f=f, trim=trim, cout=cout, rows_out=rows_out, m_major=m_major,
+                   a_f16=a_f16, epi=epi, kg=kg)
+    ok = ctypes.c_int(0)
+    check(lib().mio_hip_debug_codec_gemm(dev.h, ctypes.addressof(g), _ptr(A), _ptr(B), _ptr(C),
+                                         None if bias is None else _ptr(bias), None if aux is None else _ptr(aux),
+                                         None if aux2 is None else _ptr(aux2), ctypes.byref(ok)))
+    return C, bool(ok.value)
+
+
+def debug_codec_conv(dev: Device, xa: np.ndarray, w: np.ndarray, bias: np.ndarray, taps: int, pad: int,
+                     resid=None, alias: bool = False):
+    """launch_conv_f16: xa [L][Cin] f16, w [Cout][taps*Cin] f16 -> y [L][Cout] f32; resid
+    [L][Cout] is added from a buffer of its own, or (alias) from Y itself."""
+    xa = np.ascontiguousarray(xa, dtype=np.float16)
+    w = np.ascontiguousarray(w, dtype=np.float16)
+    bias = np.ascontiguousarray(bias, dtype=np.float32)
+    L, Cin = xa.shape
+    Cout = w.shape[0]
+    assert w.shape[1] == taps * Cin and (resid is not None or not alias)
+    resid = _opt_f32(resid)
+    y = resid.copy() if alias else np.empty((L, Cout), np.float32)
+    mode = 0 if resid is None else (2 if alias else 1)
+    ok = ctypes.c_int(0)
+    check(lib().mio_hip_debug_codec_conv(dev.h, _ptr(xa), L, Cin, taps, pad, _ptr(w), Cout, _ptr(bias), mode,
+                                         _ptr(resid) if mode == 1 else None, _ptr(y), ctypes.byref(ok)))
+    return y, bool(ok.value)
+
+
+def debug_codec_rownorm(dev: Device, x: np.ndarray, eps: float, mode: int = 0, p0=None, p1=None,
+                        in_place: bool = False):
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    p0, p1 = _opt_f32(p0), _opt_f32(p1)
+    y = np.empty_like(x)
+    ok = ctypes.c_int(0)
+    check(lib().mio_hip_debug_codec_rownorm(dev.h, _ptr(x), x.shape[0], x.shape[1], eps, mode,
+                                            None if p0 is None else _ptr(p0), None if p1 is None else _ptr(p1),
+                                            int(in_place), _ptr(y), ctypes.byref(ok)))
+    return y, bool(ok.value)
+
+
+def debug_codec_groupnorm(dev: Device, x: np.ndarray, G: int, eps: float, gamma: np.ndarray, beta: np.ndarray):
+    """launch_groupnorm_apply (pipeline per MIO_GN): x [L][C] -> f16 [L][C]."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    gamma = np.ascontiguousarray(gamma, dtype=np.float32)
+    beta = np.ascontiguousarray(beta, dtype=np.float32)
+    xa = np.empty(x.shape, np.uint16)
+    ok = ctypes.c_int(0)
+    check(lib().mio_hip_debug_codec_groupnorm(dev.h, _ptr(x), x.shape[0], x.shape[1], G, eps, _ptr(gamma),
+                                              _ptr(beta), _ptr(xa), ctypes.byref(ok)))
+    return xa.view(np.float16), bool(ok.value)
+
+
+def debug_codec_band_attention(dev: Device, qkv: np.ndarray, H: int, window: int, rope: np.ndarray):
+    """launch_band_attention: qkv [S][3*H*64], rope [S][32][2] (cos, sin) -> out [S][H*64]."""
+    qkv = np.ascontiguousarray(qkv, dtype=np.float32)
+    rope = np.ascontiguousarray(rope, dtype=np.float32)
+    S = qkv.shape[0]
+    assert qkv.shape[1] == 3 * H * 64 and rope.shape == (S, 32, 2)
+    out = np.empty((S, H * 64), np.float32)
+    ok = ctypes.c_int(0)
+    check(lib().mio_hip_debug_codec_band_attention(dev.h, _ptr(qkv), S, H, window, _ptr(rope), _ptr(out),
+                                                   ctypes.byref(ok)))
+    return out, bool(ok.value)
+
+
+def debug_codec_cond_gemv(dev: Device, W: np.ndarray, b: np.ndarray, e: np.ndarray, e_f16: int = 0):
+    W = np.ascontiguousarray(W, dtype=np.float32)
+    b = np.ascontiguousarray(b, dtype=np.float32)
+    e = np.ascontiguousarray(e, dtype=np.float32)
+    y = np.empty(W.shape[0], np.float32)
+    ok = ctypes.c_int(0)
+    check(lib().mio_hip_debug_codec_cond_gemv(dev.h, _ptr(W), _ptr(b), _ptr(e), W.shape[0], W.shape[1], e_f16,
+                                              _ptr(y), ctypes.byref(ok)))
+    return y, bool(ok.value)
+
+
+def debug_codec_embed(dev: Device, table: np.ndarray, codes):
+    table = np.ascontiguousarray(table, dtype=np.float32)
+    codes = np.ascontiguousarray(codes, dtype=np.int32)
+    x = np.empty((len(codes), table.shape[1]), np.float32)
+    ok = ctypes.c_int(0)
+    check(lib().mio_hip_debug_codec_embed(dev.h, _ptr(table), table.shape[0], table.shape[1], _ptr(codes),
+                                          len(codes), _ptr(x), ctypes.byref(ok)))
+    return x, bool(ok.value)
 
 
 # ---------------------------------------------------------------- tokenizer

@@ -127,6 +127,28 @@ def test_codec_rejects_bad_codes(device, files, emb):
         gc.decode([5, 12800], emb)
 
 
+def test_codec_batch_host_inputs_bad_code_then_valid(device, files, emb):
+    """The host-input batch path (no MIO_*_DEVICE flag, as tts.cpp calls it): every utterance's
+    codes are checked before anything is queued, so one out-of-range code in utterance 2 of 4
+    refuses the whole batch with nothing left running, and a following valid batch on the same
+    codec gives each utterance's single-decode PCM bit for bit."""
+    gc = m.Codec(device, files["tiny"])
+    rng = np.random.default_rng(11)
+    lens = [9, 5, 14, 3]
+    codes = [rng.integers(0, gc.n_codes, n).astype(np.int32) for n in lens]
+    bad = [c.copy() for c in codes]
+    bad[2][7] = gc.n_codes
+    with pytest.raises(m.HipError, match="utterance 2"):
+        gc.decode_pcm_batch(bad, emb, host=True)
+    bad[2][7] = -1
+    with pytest.raises(m.HipError, match="utterance 2"):
+        gc.decode_pcm_batch(bad, emb, host=True)
+    got = gc.decode_pcm_batch(codes, emb, host=True)
+    for c, g in zip(codes, got):
+        want = gc.decode_pcm(c, emb)
+        assert g.shape == want.shape and np.array_equal(g, want), len(c)
+
+
 def test_codec_incremental_streaming_decode(device, files, emb):
     """f3 (test-to-speech.cpp:526-529 re-decodes every committed prefix): an incremental
     decode reuses the prenet rows of the previous one whose +-192-code receptive field was
