@@ -26,6 +26,18 @@ int mio_dequantize_rows(uint32_t type, const void *rows_bytes, int rows, int k, 
 int mio_hip_debug_mmq(mio_hip_device *d, uint32_t type, const void *gguf_rows, int rows, int k,
                       const float *x, int nt, int mode, const void *gguf_up, float *y);
 
+/* ---------------- LLM attention on injected K/V ----------------
+ * The inverse of mio_hip_llm_kv_rows: f16 bit patterns k, v [n_kv][n_pos][head_dim] are written to
+ * cache positions [p0, p0 + n_pos) of layer il. */
+int mio_hip_llm_set_kv_rows(mio_hip_llm *m, int il, int p0, int n_pos, const uint16_t *k, const uint16_t *v);
+/* One attention launch of layer il at position pos on the raw q|k|v row qkv[(H + 2 Hkv) * hd]
+ * (the projections' output: bias, q/k norm, RoPE and the f16 rounding are the launch's own):
+ * which = 1 the attention launch, 10 the attention + O launch (MIO_ERR_UNSUPPORTED where the
+ * head shape has none; any other value too). att[H * hd] receives the merged attention output.
+ * Cache row pos of the layer is written, the decode state is left at pos (eval / generate set
+ * their own). A short-conv layer is refused with MIO_ERR_INVALID. */
+int mio_hip_llm_debug_attention(mio_hip_llm *m, int il, int pos, int which, const float *qkv, float *att);
+
 /* ---------------- MioCodec kernels, one launch each ----------------
  * Parity entry points of csrc/hip/codec_kernels.hip (csrc/testlib/debug_codec_capi.cpp). Every
  * pointer is host memory; a call uploads its operands, launches on the device's stream, waits
@@ -87,7 +99,7 @@ int mio_synth_codec_gguf(const char *path, int preset, uint64_t seed);
 int mio_synth_voice_gguf(const char *path, uint64_t seed);
 /* Synthetic LLM (llama.cpp GGUF conventions, byte-level vocab + 12,800 speech tokens):
  * preset 0 tiny Q8_0, 1 tiny Q4_K_M, 2 "0.1B" Q8_0, 3 "1.7B" Q4_K_M, 4 "2.6B" Q8_0,
- * 5 tiny Q8_0 qwen2 with attn_{q,k,v}.bias, ... (csrc/testlib/synth.h lists all 17). */
+ * 5 tiny Q8_0 qwen2 with attn_{q,k,v}.bias, ... (csrc/testlib/synth.h lists all 19). */
 int mio_synth_llm_gguf(const char *path, int preset, uint64_t seed);
 
 #ifdef __cplusplus

@@ -1600,18 +1600,27 @@ struct AttM {
 };
 static_assert(ATT_CHUNK % 32 == 0, "attention chunk: whole 32-position k-steps");
 
-// This thread's K / V chunks of the chunk's rows t0 .. t0 + ATT_CHUNK - 1 (rows past pos read
-// row pos: finite values under a zero probability), issued early.
+// This thread's K / V chunks of the chunk's rows t0 .. t0 + ATT_CHUNK - 1, issued early.
+// Rows past pos are masked positions: their score is replaced by -inf and their probability is
+// 0, but 0 x NaN and 0 x Inf are NaN in the P.V MFMA, so their V rows must be finite whatever
+// the cache holds (row pos itself is stale or never written while the decode step that appends
+// it runs). Both loads are therefore range-checked buffer loads over the written rows alone
+// ([0, pos), or [0, pos] where an earlier launch wrote row pos: the prefill): a row past them
+// reads 0, with one 32-bit offset for K and V, no address clamp and no select. (A masked K row
+// could hold anything: its score is replaced, not multiplied.)
 template <int HD>
 __device__ __forceinline__ void kv_issue(const _Float16 *kb, const _Float16 *vb, int t0, int pos,
-                                         h8 (&kr)[AttM<HD>::VI], h8 (&vr)[AttM<HD>::VI]) {
+                                         h8 (&kr)[AttM<HD>::VI], h8 (&vr)[AttM<HD>::VI],
+                                         bool row_pos_written = false) {
     using A = AttM<HD>;
+    const uint32_t bytes = (uint32_t)(pos + (row_pos_written ? 1 : 0)) * (uint32_t)A::RB;
+    const __amdgpu_buffer_rsrc_t kres = rsrc(kb, bytes), vres = rsrc(vb, bytes);
 #pragma unroll
     for (int it = 0; it < A::VI; ++it) {
         const int c = it * A::NT + (int)MIO_TIDX, row = c / A::CH, ch = c % A::CH;
-        const size_t o = (size_t)min(t0 + row, pos) * HD + ch * 8;
-        kr[it] = *reinterpret_cast<const h8 *>(kb + o);
-        vr[it] = *reinterpret_cast<const h8 *>(vb + o);
+        const uint32_t o = (uint32_t)(t0 + row) * (uint32_t)A::RB + 16u * ch;
+        kr[it] = __builtin_bit_cast(h8, __builtin_amdgcn_raw_buffer_load_b128(kres, o, 0, 0));
+        vr[it] = __builtin_bit_cast(h8, __builtin_amdgcn_raw_buffer_load_b128(vres, o, 0, 0));
     }
 }
 

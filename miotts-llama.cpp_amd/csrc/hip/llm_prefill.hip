@@ -662,7 +662,7 @@ __global__ __launch_bounds__(AttCfg<HD>::NT) void k_pf_attention(LlmDims d, cons
     __shared__ __attribute__((aligned(16))) char img[2 * A::IMG];
     __shared__ __attribute__((aligned(16))) _Float16 qh[G][HD];
     h8 kr[A::VI], vr[A::VI];
-    kv_issue<HD>(kc + kvo, vc + kvo, t0, pos, kr, vr);
+    kv_issue<HD>(kc + kvo, vc + kvo, t0, pos, kr, vr, true);  // row pos: written by k_pf_rope
     for (int e = threadIdx.x; e < G * HD; e += C::NT) qh[e / HD][e % HD] = (_Float16)qsrc[e];
     kv_stage<HD>(kr, vr, -1, img, img + A::IMG);
     lds_barrier();

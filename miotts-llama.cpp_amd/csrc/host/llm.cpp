@@ -1165,6 +1165,58 @@ extern "C" int mio_hip_llm_kv_rows(mio_hip_llm *m, int il, int n_pos, uint16_t *
     return MIO_OK;
 }
 
+// The inverse of mio_hip_llm_kv_rows (parity tests): rows [n_kv][n_pos][head_dim] into cache
+// positions [p0, p0 + n_pos) of layer il.
+int mio::llm_set_kv_rows(mio_hip_llm *m, int il, int p0, int n_pos, const uint16_t *k, const uint16_t *v) {
+    MIO_REQUIRE(m && k && v && il >= 0 && il < m->n_layer && p0 >= 0 && n_pos >= 0 && p0 <= m->dims.n_ctx &&
+                    n_pos <= m->dims.n_ctx - p0,
+                MIO_ERR_INVALID, "llm_set_kv_rows: bad args");
+    int rc = mio::bind(m->d);
+    if (rc) return rc;
+    const mio::LlmDims &D = m->dims;
+    hipStream_t s = m->d->stream;
+    for (int h = 0; h < D.n_kv && n_pos > 0; ++h) {
+        const size_t dst = (((size_t)il * D.n_kv + h) * D.n_ctx + p0) * D.hd, src = (size_t)h * n_pos * D.hd;
+        MIO_HIP_CHECK(hipMemcpyAsync(m->kc + dst, k + src, (size_t)n_pos * D.hd * 2, hipMemcpyHostToDevice, s));
+        MIO_HIP_CHECK(hipMemcpyAsync(m->vc + dst, v + src, (size_t)n_pos * D.hd * 2, hipMemcpyHostToDevice, s));
+    }
+    MIO_HIP_CHECK(hipStreamSynchronize(s));
+    return MIO_OK;
+}
+
+// One attention launch on an injected q|k|v row (parity tests): the state is set to pos, the
+// row replaces buf.qkv, launch_step_kernel(which) of layer il runs alone, and buf.att comes
+// back. which 10 also runs the O workgroups (buf.x += W_o att, on token 0's embedding).
+int mio::llm_debug_attention(mio_hip_llm *m, int il, int pos, int which, const float *qkv, float *att) {
+    MIO_REQUIRE(m && qkv && att && il >= 0 && il < m->n_layer && pos >= 0 && pos < m->dims.n_ctx, MIO_ERR_INVALID,
+                "llm_debug_attention: bad args");
+    MIO_REQUIRE(!m->layers[il].conv, MIO_ERR_INVALID, "llm_debug_attention: layer %d is a short-conv layer", il);
+    const mio::LlmDims &D = m->dims;
+    MIO_REQUIRE(which == 1 || which == 10, MIO_ERR_UNSUPPORTED, "llm_debug_attention: which %d (1 or 10)", which);
+    MIO_REQUIRE(which == 1 || (D.n_kv <= mio::kRdyOff && mio::att_o_supported(D.hd, D.n_head / D.n_kv) &&
+                               m->layers[il].wo.k <= 2048),  // k_att_o: one 2048-weight pass of W_o
+                MIO_ERR_UNSUPPORTED, "llm_debug_attention: no attention + O launch for this shape");
+    int rc = mio::bind(m->d);
+    if (rc) return rc;
+    hipStream_t s = m->d->stream;
+    if ((rc = set_state(m, pos, 0))) return rc;  // tickets and merge counters zeroed, state at pos
+    const size_t n_qkv = (size_t)(D.n_head + 2 * D.n_kv) * D.hd, n_att = (size_t)D.n_head * D.hd;
+    MIO_HIP_CHECK(hipMemcpyAsync(m->buf.qkv, qkv, n_qkv * 4, hipMemcpyHostToDevice, s));
+    mio::launch_step_kernel(which, D, m->layers.data(), il, m->kc, m->vc, m->out_norm, m->lm, m->tok, m->buf, s);
+    MIO_HIP_CHECK(hipGetLastError());
+    MIO_HIP_CHECK(hipMemcpyAsync(att, m->buf.att, n_att * 4, hipMemcpyDeviceToHost, s));
+    // the O workgroups' wait flag, read here whatever MIO_ATT_FUSE_O says (check_handoff follows it)
+    int flag = 0;
+    MIO_HIP_CHECK(hipMemcpyAsync(&flag, m->buf.att_cnt + mio::kRdyFlag, sizeof(int), hipMemcpyDeviceToHost, s));
+    MIO_HIP_CHECK(hipStreamSynchronize(s));
+    if (flag) {
+        MIO_HIP_CHECK(hipMemsetAsync(m->buf.att_cnt + mio::kRdyFlag, 0, sizeof(int), s));
+        mio::set_error("llm_debug_attention: the attention -> O hand-off wait timed out");
+        return MIO_ERR_HIP;
+    }
+    return check_handoff(m);
+}
+
 extern "C" int mio_hip_llm_tail(const mio_hip_llm *m, int *steps, int *timed_steps, float *timed_ms) {
     MIO_REQUIRE(m && steps && timed_steps && timed_ms, MIO_ERR_INVALID, "llm_tail: null argument");
     *steps = m->tail_steps, *timed_steps = m->tail_timed_steps, *timed_ms = m->tail_ms;

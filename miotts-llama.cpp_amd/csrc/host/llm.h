@@ -36,4 +36,14 @@ int llm_poll(mio_hip_llm *m, std::vector<int32_t> &out, bool *done);
 LlmInfo llm_info(const mio_hip_llm *m);
 uint64_t llm_step_weight_bytes(const mio_hip_llm *m);
 
+// Parity-test entry points of the attention launches (exported as C by the test-support
+// library, include/mio_hip_test.h; no product path calls them).
+// F16 rows k, v [n_kv][n_pos][head_dim] into cache positions [p0, p0 + n_pos) of layer il (the
+// inverse of mio_hip_llm_kv_rows).
+int llm_set_kv_rows(mio_hip_llm *m, int il, int p0, int n_pos, const uint16_t *k, const uint16_t *v);
+// One attention launch of layer il at position pos on the raw q|k|v row qkv[(H + 2 Hkv) hd]:
+// which = 1 (k_attention) or 10 (k_att_o); att[H hd] receives LlmBuffers.att. Leaves the decode
+// state at pos and cache row pos written.
+int llm_debug_attention(mio_hip_llm *m, int il, int pos, int which, const float *qkv, float *att);
+
 }  // namespace mio

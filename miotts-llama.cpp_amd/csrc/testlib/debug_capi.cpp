@@ -5,6 +5,7 @@
 
 #include "common.h"
 #include "gguf.h"
+#include "llm.h"
 #include "llm_kernels.h"
 #include "mio_hip_test.h"
 #include "quant.h"
@@ -83,6 +84,19 @@ extern "C" int mio_hip_debug_mmq(mio_hip_device *d, uint32_t type, const void *g
     hipFree(dw), hipFree(dx), hipFree(dy), hipFree(da);
     MIO_HIP_CHECK(e);
     return MIO_OK;
+}
+
+// The attention launches on injected K/V rows and an injected q|k|v row: the work is done next
+// to the runner's state (csrc/host/llm.cpp), exported here so the product library carries no
+// test entry point.
+extern "C" int mio_hip_llm_set_kv_rows(mio_hip_llm *m, int il, int p0, int n_pos, const uint16_t *k,
+                                       const uint16_t *v) {
+    return mio::llm_set_kv_rows(m, il, p0, n_pos, k, v);
+}
+
+extern "C" int mio_hip_llm_debug_attention(mio_hip_llm *m, int il, int pos, int which, const float *qkv,
+                                           float *att) {
+    return mio::llm_debug_attention(m, il, pos, which, qkv, att);
 }
 
 extern "C" int mio_quantize_rows(uint32_t type, const float *x, int rows, int k, void *out) {

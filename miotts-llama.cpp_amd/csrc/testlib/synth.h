@@ -41,6 +41,7 @@ struct SynthLlmCfg {
     bool kq_fallback = true;
     bool tied = true;
     bool qkv_bias = false;  // attn_{q,k,v}.bias tensors (qwen2)
+    bool qk_norm_varied = false;  // attn_{q,k}_norm.weight = 1 + N(0, 0.25) instead of ones
     // lfm2: layer i is attention when (i % attn_mod) is in attn_at, else a gated short conv
     int attn_mod = 4, attn_at0 = 2, attn_at1 = -1;
     uint64_t seed = 1;
@@ -53,8 +54,10 @@ struct SynthLlmCfg {
 //         the embedding fall back to Q5_0 / Q8_0 as llama-quantize does), 10 tiny Q4_0,
 //         11 tiny BF16 (qwen3), 12 "1.7B" BF16, 13 tiny Q5_K_M (qwen3, 3 layers: attn_v / ffn_down
 //         Q5_K on layers 0-1, Q6_K on layer 2), 14 tiny Q5_K_S (llama, untied: token_embd Q5_K,
-//         output Q6_K), 15 tiny Q5_K_M lfm2, 16 "1.7B" Q5_K_M
-constexpr int kSynthLlmPresets = 17;
+//         output Q6_K), 15 tiny Q5_K_M lfm2, 16 "1.7B" Q5_K_M, 17 tiny Q4_K_M qwen3 with the 1.7B
+//         head shape (hd 128, 2 query heads per kv head; q/k norm weights 1 + N(0, 0.25)),
+//         18 tiny Q8_0 llama with the 2.6B head shape (hd 64, 4 query heads per kv head)
+constexpr int kSynthLlmPresets = 19;
 SynthLlmCfg synth_llm_preset(int preset);
 // null, or why the writer refuses the configuration
 const char *synth_llm_check(const SynthLlmCfg &cfg);

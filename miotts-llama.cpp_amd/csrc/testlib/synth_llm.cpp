@@ -95,6 +95,15 @@ SynthLlmCfg synth_llm_preset(int p) {
             c = synth_llm_preset(3);
             c.name = "MioTTS-1.7B-q5km-synthetic", c.qtype = 17;
             break;
+        // the big models' head shapes at tiny widths (attention parity tests at n_ctx 32768): the
+        // attention launches take the (hd, G, W_o type) instantiations of presets 3 and 4
+        case 17:
+            c.name = "tiny-hd128-g2-q4km", c.arch = "qwen3", c.n_head = 4, c.n_head_kv = 2, c.head_dim = 128;
+            c.qtype = 15, c.rope_base = 1000000.f, c.qk_norm_varied = true;
+            break;
+        case 18:
+            c.name = "tiny-hd64-g4", c.n_head = 8, c.n_head_kv = 2, c.head_dim = 64;
+            break;
         default: break;
     }
     return c;
@@ -187,7 +196,8 @@ bool synth_write_llm(const std::string &path, const SynthLlmCfg &c) {
         std::string name;
         uint32_t type;
         int64_t k, rows;
-        int fill;  // 0 quantized N(0, w_std) rows, 1 ones, 2 f32 N(0, 0.5) (biases / conv taps)
+        int fill;  // 0 quantized N(0, w_std) rows, 1 ones, 2 f32 N(0, 0.5) (biases / conv taps),
+                   // 3 f32 1 + N(0, 0.25) (q/k norm weights of qk_norm_varied)
     };
     std::vector<T> ts;
     auto pick = [&](uint32_t k_mix, uint32_t q4) -> uint32_t {
@@ -221,8 +231,8 @@ bool synth_write_llm(const std::string &path, const SynthLlmCfg &c) {
             ts.push_back({p + "attn_v.bias", GGML_F32, kv_dim, 1, 2});
         }
         if (a == "qwen3" || lfm2) {
-            ts.push_back({p + "attn_q_norm.weight", GGML_F32, c.head_dim, 1, true});
-            ts.push_back({p + "attn_k_norm.weight", GGML_F32, c.head_dim, 1, true});
+            ts.push_back({p + "attn_q_norm.weight", GGML_F32, c.head_dim, 1, c.qk_norm_varied ? 3 : 1});
+            ts.push_back({p + "attn_k_norm.weight", GGML_F32, c.head_dim, 1, c.qk_norm_varied ? 3 : 1});
         }
         }
         ts.push_back({p + "ffn_norm.weight", GGML_F32, c.n_embd, 1, true});
@@ -248,11 +258,13 @@ bool synth_write_llm(const std::string &path, const SynthLlmCfg &c) {
     }
     return w.write(path, [&](size_t idx, uint8_t *dst, size_t nbytes) {
         const T &t = ts[idx];
-        if (t.fill == 1 || t.fill == 2) {
+        if (t.fill >= 1) {
             float *f = (float *)dst;
             const uint64_t key = synth_key(c.seed, t.name);
             for (int64_t i = 0; i < t.k * t.rows; ++i)
-                f[i] = t.fill == 1 ? 1.0f : 0.5f * synth_normal_fast(key, (uint64_t)i);
+                f[i] = t.fill == 1 ? 1.0f
+                                   : (t.fill == 2 ? 0.5f : 0.25f) * synth_normal_fast(key, (uint64_t)i) +
+                                         (t.fill == 3 ? 1.0f : 0.0f);
             return;
         }
         const size_t rb = ggml_row_bytes(t.type, t.k);

@@ -130,6 +130,8 @@ def _declare(L: ctypes.CDLL) -> None:
         "mio_hip_llm_conv_ring": (c_int, [_vp, c_int, _vp, c_int]),
         "mio_hip_llm_eval_layers": (c_int, [_vp, ctypes.c_int32, c_int, _vp, _vp]),
         "mio_hip_llm_kv_rows": (c_int, [_vp, c_int, c_int, _vp, _vp]),
+        "mio_hip_llm_set_kv_rows": (c_int, [_vp, c_int, c_int, c_int, _vp, _vp]),
+        "mio_hip_llm_debug_attention": (c_int, [_vp, c_int, c_int, c_int, _vp, _vp]),
         "mio_hip_debug_matvec": (c_int, [_vp, ctypes.c_uint32, _vp, c_int, c_int, _vp, _vp]),
         "mio_quantize_rows": (c_int, [ctypes.c_uint32, _vp, c_int, c_int, _vp]),
         "mio_dequantize_rows": (c_int, [ctypes.c_uint32, _vp, c_int, c_int, _vp]),
@@ -576,6 +578,24 @@ class Llm:
         v = np.empty_like(k)
         check(lib().mio_hip_llm_kv_rows(self.h, il, n_pos, _ptr(k), _ptr(v)))
         return k, v
+
+    def set_kv_rows(self, il: int, p0: int, k: np.ndarray, v: np.ndarray) -> None:
+        """Writes F16 rows k, v [n_kv, n_pos, head_dim] to cache positions [p0, p0 + n_pos) of
+        layer il (the inverse of kv_rows; test-support library)."""
+        k = np.ascontiguousarray(k, np.float16)
+        v = np.ascontiguousarray(v, np.float16)
+        assert k.shape == v.shape and k.ndim == 3 and k.shape[0] == self.n_kv and k.shape[2] == self.head_dim, k.shape
+        check(lib().mio_hip_llm_set_kv_rows(self.h, il, p0, k.shape[1], _ptr(k), _ptr(v)))
+
+    def debug_attention(self, il: int, pos: int, which: int, qkv: np.ndarray) -> np.ndarray:
+        """One attention launch (which 1: attention, 10: attention + O) of layer il at position
+        pos on the raw q|k|v row [(n_head + 2 n_kv) * head_dim]: the attention output
+        [n_head, head_dim] (test-support library). Writes cache row pos."""
+        qkv = np.ascontiguousarray(qkv, np.float32).reshape(-1)
+        assert qkv.size == (self.n_head + 2 * self.n_kv) * self.head_dim, qkv.size
+        att = np.empty((self.n_head, self.head_dim), np.float32)
+        check(lib().mio_hip_llm_debug_attention(self.h, il, pos, which, _ptr(qkv), _ptr(att)))
+        return att
 
     def step_kinds(self) -> list:
         """The decode step's launches in order, as time_kernel's `which` (0 attn_in,

@@ -38,7 +38,8 @@ def test_test_support_symbols_live_in_the_test_library():
     by libmiotts_test.so only: the product library carries no test code's entry points."""
     libs = m.lib()
     declared = _declared_symbols(test_header=True)
-    assert {"mio_synth_llm_gguf", "mio_hip_debug_matvec", "mio_quantize_rows"} <= declared
+    assert {"mio_synth_llm_gguf", "mio_hip_debug_matvec", "mio_quantize_rows", "mio_hip_llm_set_kv_rows",
+            "mio_hip_llm_debug_attention"} <= declared
     assert libs.test is not None
     missing = [n for n in sorted(declared) if not hasattr(libs.test, n)]
     assert not missing, f"declared but not exported: {missing}"

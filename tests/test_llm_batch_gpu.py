@@ -49,6 +49,22 @@ def test_batch_equals_single_streams(device, llm_files, preset, B):
         assert (got[0] == to).sum() >= 22
 
 
+@pytest.mark.parametrize("preset", [17, 18])
+def test_batch_equals_single_streams_long_context(device, synth_llm_path, preset):
+    """The batched decode attention past 64 chunks (9 merge batches): after prompts of about 4100
+    tokens, every stream's tokens equal its single-stream generate (tiny models with the 1.7B
+    and 2.6B head shapes)."""
+    g = m.Llm(device, synth_llm_path(preset), 4352)
+    rng = np.random.default_rng(preset)
+    prompts = [list(rng.integers(0, 256, n)) for n in (4100, 4033, 4159)]
+    seeds = [31, 32, 33]
+    got = g.generate_batch(prompts, 16, 0.8, seeds, allow=ALLOW)
+    for b in range(3):
+        ref = g.generate(prompts[b], 16, 0.8, seeds[b], allow=ALLOW)
+        assert len(ref) == 16 and np.array_equal(got[b], ref), (b, got[b], ref)
+    g.close()
+
+
 def test_batch_greedy_and_identical_streams(device, llm_files):
     """temperature 0 = greedy; two streams with the same prompt and seed stay identical."""
     g = m.Llm(device, llm_files[1], 256)

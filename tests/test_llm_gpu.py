@@ -340,6 +340,20 @@ def test_batched_prefill_matches_sequential(device, llm_files, preset, n):
     assert np.abs(batched - lo).max() <= 5e-2 * np.abs(lo).max()
 
 
+@pytest.mark.parametrize("preset,n", [(17, 4097), (18, 8200)])
+def test_batched_prefill_matches_sequential_long(device, synth_llm_path, preset, n):
+    """The multi-token attention at long context (65 and 129 chunks: 9 and 17 merge batches, the
+    last prefill chunk of 1 and of 8 tokens): the logits after prefill(n) equal the sequential
+    eval loop's bit for bit, on the tiny models with the 1.7B and 2.6B head shapes."""
+    g = m.Llm(device, synth_llm_path(preset), n + 56)
+    toks = np.random.default_rng(n).integers(0, g.n_vocab, n)
+    batched = g.prefill(toks)
+    for pos, t in enumerate(toks):
+        seq = g.eval(int(t), pos)
+    assert np.array_equal(batched, seq), float(np.abs(batched - seq).max())
+    g.close()
+
+
 def test_batched_prefill_then_generate(device, llm_files):
     """generate() prefills in batches; the sampled ids still follow the oracle's decode."""
     g = m.Llm(device, llm_files[1], 256)
@@ -415,6 +429,21 @@ h = hashlib.sha256(toks.tobytes())
 for pos in (3, 70, 129):
     h.update(g.eval(int(toks[0]), pos).tobytes())
 k = g.step_kinds()
+# long context on a peaked K/V state (scores of std ~8: K rows 8 N(0, 1) against q rows of unit
+# RMS), the same rows in every layer, written with set_kv_rows up to the last evaluated position
+g.close()
+long_pos = [int(p) for p in sys.argv[3].split(",")]
+g = m.Llm(dev, sys.argv[1], 32768)
+rng = np.random.default_rng(11)
+n = max(long_pos)
+ks = (8.0 * rng.standard_normal((g.n_kv, n, g.head_dim), dtype=np.float32)).astype(np.float16)
+vs = rng.standard_normal((g.n_kv, n, g.head_dim), dtype=np.float32).astype(np.float16)
+for il in range(g.n_layer):
+    g.set_kv_rows(il, 0, ks, vs)
+for pos in long_pos:
+    lg = g.eval(int(toks[1]), pos)
+    assert np.isfinite(lg).all(), pos
+    h.update(lg.tobytes())
 print(k.count(11), k.count(10), k.count(12), k.count(13), h.hexdigest())
 """
 
@@ -426,11 +455,16 @@ def test_fused_attention_launches_bit_identical(synth_llm_path, tmp_path, preset
     (k_att_o) and the separate launches run the same arithmetic: 80 free-run tokens and the
     logits of three later evaluations are bit-identical across MIO_LAYER_FUSE / MIO_LAYER_GATE /
     MIO_LAYER_ATT / MIO_ATT_FUSE_O / MIO_FFN_FUSE (each variant is a fresh process: the switches
-    are read once). k_layer is instantiated for the 1.7B Q4_K_M shapes (preset 3)."""
+    are read once). k_layer is instantiated for the 1.7B Q4_K_M shapes (preset 3).
+    The same holds at long context on a peaked K/V state (written with set_kv_rows into every
+    layer of a second load at n_ctx 32768): the logits at positions 4096 and 32767 (4096 only for
+    the 1.7B model) join the digest. The single-launch attention these paths share their chunk
+    and merge code with is checked against float64 at those positions in test_attention_gpu.py."""
     import os
     import subprocess
     import sys
     path = synth_llm_path(preset)
+    long_pos = "4096" if preset == 3 else "4096,32767"
     script = tmp_path / "fusion.py"
     script.write_text(_FUSION_SCRIPT)
     pkg = os.path.dirname(os.path.dirname(m.__file__))
@@ -439,7 +473,7 @@ def test_fused_attention_launches_bit_identical(synth_llm_path, tmp_path, preset
                       ("layer_att", {"MIO_LAYER_FUSE": "0", "MIO_LAYER_ATT": "1"}),
                       ("att_o", {"MIO_LAYER_FUSE": "0", "MIO_LAYER_ATT": "0"}),
                       ("separate", {"MIO_ATT_FUSE_O": "0", "MIO_FFN_FUSE": "0"})):
-        p = subprocess.run([sys.executable, str(script), path, pkg], capture_output=True, text=True, timeout=240,
+        p = subprocess.run([sys.executable, str(script), path, pkg, long_pos], capture_output=True, text=True, timeout=240,
                            env=dict(os.environ, **env))
         assert p.returncode == 0, p.stderr[-2000:]
         outs[name] = p.stdout.split()

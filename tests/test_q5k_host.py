@@ -77,6 +77,12 @@ def test_gguf_round_trip(tmp_path, monkeypatch, preset, file_type):
         assert lg.shape == (13312,) and np.isfinite(lg).all()
 
 
-def test_presets_end_at_16(tmp_path):
+def test_presets_end_at_18(tmp_path):
+    """17 and 18 are the tiny models with the 1.7B and 2.6B head shapes; nothing follows them."""
+    for preset, shape in ((17, (4, 2, 128)), (18, (8, 2, 64))):
+        g = gguf_np.GGUFReader(m.synth_llm(str(tmp_path / f"p{preset}.gguf"), preset, 1))
+        a = g.kv["general.architecture"]
+        assert (g.kv[f"{a}.attention.head_count"], g.kv[f"{a}.attention.head_count_kv"],
+                g.kv[f"{a}.attention.key_length"]) == shape
     with pytest.raises(m.HipError, match="bad args"):
-        m.synth_llm(str(tmp_path / "x.gguf"), 17, 1)
+        m.synth_llm(str(tmp_path / "x.gguf"), 19, 1)
