@@ -187,16 +187,37 @@ bool batch_supported(const LlmDims &d, int B, int lm_type);
 void launch_batch_embed(const LlmDims &d, const QMat &tok_embd, const PrefillBuffers &pb, const BatchBuffers &bb,
                         int B, hipStream_t s);
 
-// Launch one kernel of a decode step (which: 0 attn_in, 1 attention, 2 attn_out, 3 ffn_in,
-// 4 ffn_down of layer il; 6 lm_head, 7 sampler; lfm2 short-conv layers: 8 conv_in, 9
-// conv_out in place of 0..2; 10 attention + O (k_att_o, for 1 + 2), 11 the whole attention
-// block (k_layer_att, for 0 + 1 + 2), 12 the FFN pair (k_ffn, for 3 + 4), 13 the whole layer
-// (k_layer, for 11 + 12)) on stream s.
+// The launches of a decode step. The numbers are an interface and stay as they are: bench.py,
+// tools/, the tests and the callers of mio_hip_llm_step_kinds / _time_kernel / _trace_kernel
+// pass them as int (the C ABI keeps int). 5 was the final norm, now inside lm_head.
+enum StepKind : int {
+    kAttnIn = 0,      // RMSNorm + q|k|v (+ layer 0: the previous step's sampler)
+    kAttention = 1,   // attention chunks + merge
+    kAttnOut = 2,     // O projection + residual
+    kFfnIn = 3,       // RMSNorm + gate|up (+ layer 0: pos / step advance)
+    kFfnDown = 4,     // down projection + residual
+    kLmHead = 6,      // final norm + lm_head + sampler partials
+    kSample = 7,      // flush sampler (after the last step)
+    kConvIn = 8,      // lfm2 short-conv layer: RMSNorm + in_proj, in place of 0
+    kConvOut = 9,     // lfm2 short-conv layer: gated conv + out_proj, in place of 1 + 2
+    kAttO = 10,       // k_att_o: 1 + 2
+    kLayerAtt = 11,   // k_layer_att: 0 + 1 + 2
+    kFfn = 12,        // k_ffn: 3 + 4
+    kLayer = 13,      // k_layer: 11 + 12
+    kStepKindEnd = 14,
+};
+// What every launch of a model's step shares (the host builds it once per model).
+struct StepCtx {
+    LlmDims dims;
+    const LayerW *layers;
+    _Float16 *kc, *vc;
+    const float *out_norm;
+    QMat lm, tok;
+};
 // an empty one-workgroup launch (the timing reference of mio_hip_llm_time_kernel)
 void launch_nop(hipStream_t s);
-void launch_step_kernel(int which, const LlmDims &d, const LayerW *layers, int il, _Float16 *kcache,
-                        _Float16 *vcache, const float *out_norm, const QMat &lm, const QMat &tok_embd,
-                        const LlmBuffers &b, hipStream_t s);
+// Launch kernel `which` of a decode step (of layer il where it is a layer's) on stream s.
+void launch_step_kernel(StepKind which, const StepCtx &c, int il, const LlmBuffers &b, hipStream_t s);
 // Embedding of `token` (row of token_embd) -> b.x, and state reset to (pos, token).
 void launch_embed_token(const LlmDims &d, const QMat &tok_embd, const LlmBuffers &b, hipStream_t s);
 int lm_head_blocks(const LlmDims &d);

@@ -615,24 +615,25 @@ int pick_su(int units, int np) {
     if (np == 3 && units <= 3) return 3;
     return 0;
 }
-// Launch one kernel of the step: which = 0 attn_in, 1 attention, 2 attn_out (+ chunk
-// merge), 3 ffn_in, 4 ffn_down (layer il), 5 (unused: the final norm is fused into
-// lm_head), 6 lm_head, 7 flush sampler; lfm2 short-conv layer il: 8 conv_in (RMSNorm +
-// in_proj, the attn_in kernel), 9 conv_out (gated conv + out_proj). Layer 0's attn_in samples the pending token of the
-// previous step and layer 0's ffn_in advances pos / step (StepState.pending).
-void launch_step_kernel(int which, const LlmDims &d, const LayerW *layers, int il, _Float16 *kcache,
-                        _Float16 *vcache, const float *out_norm, const QMat &lm, const QMat &tok_embd,
-                        const LlmBuffers &b, hipStream_t s) {
+// Launch one kernel of the step (StepKind, llm_kernels.h): kAttnOut includes the chunk merge,
+// kConvIn is the attn_in kernel on in_proj's rows. Layer 0's attn_in samples the pending token of
+// the previous step and layer 0's ffn_in advances pos / step (StepState.pending).
+void launch_step_kernel(StepKind which, const StepCtx &c, int il, const LlmBuffers &b, hipStream_t s) {
+    const LlmDims &d = c.dims;
+    const LayerW *layers = c.layers;
+    _Float16 *kcache = c.kc, *vcache = c.vc;
+    const float *out_norm = c.out_norm;
+    const QMat &lm = c.lm, &tok_embd = c.tok;
     const size_t layer_kv = (size_t)d.n_kv * d.n_ctx * d.hd;
     const int G = d.n_head / d.n_kv;
     // diagnostic instantiations only when a trace / timeline buffer is attached
     auto go_dg = [&]<bool DG>() {
     switch (which) {
-        case 0: {
+        case kAttnIn: {
             launch_attn_in(d, layers[il], il, tok_embd, b, DG, s);
             break;
         }
-        case 1: {
+        case kAttention: {
             const LayerW &L = layers[il];
             const dim3 grid(d.max_splits, d.n_kv);
             if (d.hd == 128)
@@ -641,7 +642,7 @@ void launch_step_kernel(int which, const LlmDims &d, const LayerW *layers, int i
                 launch_attention<64, DG>(G, grid, s, d, L, kcache + il * layer_kv, vcache + il * layer_kv, b);
             break;
         }
-        case 2: {
+        case kAttnOut: {
             const LayerW &L = layers[il];
             const int grid = matvec_grid(d, L.wo.rows);
             dispatch_nt(L.wo.k, L.wo.type, [&]<int NP, int T>() {
@@ -651,7 +652,7 @@ void launch_step_kernel(int which, const LlmDims &d, const LayerW *layers, int i
             });
             break;
         }
-        case 10: {  // attention + O in one launch (k_att_o)
+        case kAttO: {  // attention + O in one launch (k_att_o)
             const LayerW &L = layers[il];
             const int grid = d.max_splits * d.n_kv + matvec_grid(d, L.wo.rows);
             dispatch_nt(L.wo.k, L.wo.type, [&]<int NP, int T>() {
@@ -663,10 +664,10 @@ void launch_step_kernel(int which, const LlmDims &d, const LayerW *layers, int i
             });
             break;
         }
-        case 11:  // the attention block in one launch (k_layer_att)
+        case kLayerAtt:  // the attention block in one launch (k_layer_att)
             launch_layer_att(d, layers[il], kcache + il * layer_kv, vcache + il * layer_kv, b, DG, s);
             break;
-        case 3: {
+        case kFfnIn: {
             const LayerW &L = layers[il];
             const int grid = matvec_grid(d, L.gate.rows);
             dispatch_nt(d.n_embd, L.gate.type, [&]<int NP, int T>() {
@@ -677,7 +678,7 @@ void launch_step_kernel(int which, const LlmDims &d, const LayerW *layers, int i
             });
             break;
         }
-        case 4: {
+        case kFfnDown: {
             const LayerW &L = layers[il];
             const int grid = matvec_grid(d, L.down.rows);
             dispatch_nt(L.down.k, L.down.type, [&]<int NP, int T>() {
@@ -688,13 +689,13 @@ void launch_step_kernel(int which, const LlmDims &d, const LayerW *layers, int i
             });
             break;
         }
-        case 12:  // the FFN pair in one launch (k_ffn)
+        case kFfn:  // the FFN pair in one launch (k_ffn)
             launch_ffn<DG>(d, layers[il], b, il == 0 ? 1 : 0, s, false);
             break;
-        case 13:  // the whole layer in one launch (k_layer, layers >= 1)
+        case kLayer:  // the whole layer in one launch (k_layer, layers >= 1)
             launch_layer(d, layers[il], il, kcache + il * layer_kv, vcache + il * layer_kv, b, DG, s);
             break;
-        case 8: {  // lfm2 conv_in: RMSNorm + in_proj as the attn_in launch (B | C rows, X rows)
+        case kConvIn: {  // lfm2 conv_in: RMSNorm + in_proj as the attn_in launch (B | C rows, X rows)
             const LayerW &L = layers[il];
             const int n = d.n_embd;
             LayerW V = L;
@@ -705,7 +706,7 @@ void launch_step_kernel(int which, const LlmDims &d, const LayerW *layers, int i
             launch_attn_in(d, V, il, tok_embd, b, DG, s);
             break;
         }
-        case 9: {
+        case kConvOut: {
             const LayerW &L = layers[il];
             const int grid = matvec_grid(d, L.out_proj.rows);
             float *ring = b.ring + (size_t)il * kConvSlots * d.n_embd;
@@ -717,7 +718,7 @@ void launch_step_kernel(int which, const LlmDims &d, const LayerW *layers, int i
             });
             break;
         }
-        case 6: {
+        case kLmHead: {
             const LlmDims dl = lm_dims(d);
             dispatch_nt(d.n_embd, lm.type, [&]<int NP, int T>() {
                 hipLaunchKernelGGL((k_lm_head<NP, T, DG>), dim3(lm_head_blocks(d)), dim3(MT), lm_lds(d.n_embd), s, dl,
@@ -725,7 +726,7 @@ void launch_step_kernel(int which, const LlmDims &d, const LayerW *layers, int i
             });
             break;
         }
-        case 7:
+        case kSample:
             hipLaunchKernelGGL(k_sample<DG>, dim3(1), dim3(ST), 0, s, d, tok_embd, lm_head_blocks(d), b);
             break;
         default: break;

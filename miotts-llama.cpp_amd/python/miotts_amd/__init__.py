@@ -467,6 +467,10 @@ class Codec:
 SYNTH_SPEECH0 = 260      # id of <|s_0|> in the synthetic vocabulary (csrc/testlib/synth.h)
 SYNTH_IM_END = 258
 SYNTH_EOT = 259
+# The decode step's launch kinds (enum StepKind, csrc/hip/llm_kernels.h): what step_kinds()
+# returns and time_kernel / trace_kernel take. 7 is the flush sampler (after the last step).
+STEP_KIND_NAMES = {0: "attn_in", 1: "attention", 2: "attn_out", 3: "ffn_in", 4: "ffn_down", 6: "lm_head",
+                   7: "sample", 8: "conv_in", 9: "conv_out", 10: "att_o", 11: "layer_att", 12: "ffn", 13: "layer"}
 
 
 def synth_llm(path: str, preset: int = 0, seed: int = 1) -> str:
@@ -598,8 +602,7 @@ class Llm:
         return att
 
     def step_kinds(self) -> list:
-        """The decode step's launches in order, as time_kernel's `which` (0 attn_in,
-        1 attention, 2 attn_out, 3 ffn_in, 4 ffn_down, 8 conv_in, 9 conv_out; 6 lm_head)."""
+        """The decode step's launches in order, as time_kernel's `which` (STEP_KIND_NAMES)."""
         n = ctypes.c_int(0)
         check(lib().mio_hip_llm_step_kinds(self.h, None, 0, ctypes.byref(n)))
         k = np.zeros(n.value, np.int32)

@@ -25,8 +25,7 @@ import miotts_amd as m  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E
 N_SHORT, N_LONG, REPS = 64, 464, 3
-KINDS = {0: "attn_in", 1: "attention", 2: "attn_out", 3: "ffn_in", 4: "ffn_down", 6: "lm_head", 10: "att_o",
-         11: "layer_att", 12: "ffn", 13: "layer"}
+KINDS = m.STEP_KIND_NAMES
 
 
 def timed_generate(dev, llm, prompt, n, allow):

@@ -28,7 +28,7 @@ for k in range(K):
     llm.generate(prompt, 700, 0.8, 2 + k, allow=allow, check_interval=CI)
     ts.append(time.perf_counter() - t0)
 ev = {}
-for which, nm in ((0, "attn_in"), (1, "attention"), (2, "attn_out"), (3, "ffn_in"), (4, "ffn_down"), (6, "lm_head")):
-    ev[nm] = round(llm.time_kernel(which, 100)[0] * 1e3, 3)
+for which in (0, 1, 2, 3, 4, 6):
+    ev[m.STEP_KIND_NAMES[which]] = round(llm.time_kernel(which, 100)[0] * 1e3, 3)
 print(json.dumps({"build": os.environ.get("MIO_BUILD_DIR", "build"), "ms": [round(t * 1e3, 2) for t in ts],
                   "ms_per_token": round(min(ts) * 1e3 / 700, 4), "event_us_at_end": ev}), flush=True)

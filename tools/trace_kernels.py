@@ -22,7 +22,7 @@ dev = m.Device(0)
 llm = m.Llm(dev, path, 2048)
 prompt = [256, 257, 65, 258, 257]
 llm.generate(prompt, a.pos, 0.8, 1, allow=(m.SYNTH_SPEECH0, m.SYNTH_SPEECH0 + 12800), check_interval=50)
-names = {0: "attn_in", 1: "attention", 2: "attn_out", 3: "ffn_in", 4: "ffn_down", 6: "lm_head", 7: "sample"}
+names = {k: m.STEP_KIND_NAMES[k] for k in (0, 1, 2, 3, 4, 6, 7)}
 for which, name in names.items():
     best = None
     for rep in range(5):
