@@ -1054,10 +1054,12 @@ __device__ inline uint64_t mix64(uint64_t x) {
     return x ^ (x >> 31);
 }
 
-// same counter-based Gumbel noise as oracle/llm_ref.c mo_gumbel
+// same counter-based Gumbel noise as oracle/llm_ref.c mo_gumbel. The largest draw, h >> 40 ==
+// 2^24 - 1, rounds to 2^24 in the f32 sum (u == 1, -logf(u) == -0, noise +inf: that id would win
+// whatever its logit): u is clamped to the largest f32 below 1, which changes that draw alone.
 __device__ inline float gumbel(uint64_t seed, int step, int idx) {
     const uint64_t h = mix64(seed ^ mix64(((uint64_t)(uint32_t)step << 32) | (uint32_t)idx));
-    const float u = ((float)(h >> 40) + 0.5f) * (1.0f / 16777216.0f);
+    const float u = fminf(((float)(h >> 40) + 0.5f) * (1.0f / 16777216.0f), 0x1.fffffep-1f);
     return -logf(-logf(u));
 }
 

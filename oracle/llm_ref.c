@@ -409,9 +409,11 @@ static inline uint64_t mix64(uint64_t x) {
     return x ^ (x >> 31);
 }
 
+/* u < 1 for every draw: (float)(2^24 - 1) + 0.5f rounds to 2^24, and u == 1 would give +inf noise;
+ * the clamp to the largest f32 below 1 changes that one draw only */
 float mo_gumbel(uint64_t seed, int step, int idx) {
     const uint64_t h = mix64(seed ^ mix64(((uint64_t)(uint32_t)step << 32) | (uint32_t)idx));
-    const float u = ((float)(h >> 40) + 0.5f) * (1.0f / 16777216.0f);
+    const float u = fminf(((float)(h >> 40) + 0.5f) * (1.0f / 16777216.0f), 0x1.fffffep-1f);
     return -logf(-logf(u));
 }
 
