@@ -162,7 +162,11 @@ int mio_hip_llm_logits(mio_hip_llm *m, float *logits);
  * on the device (Gumbel-max over a counter-based hash of (seed, step, id)); temperature <= 0 is
  * greedy. The sampler stores the end token's flag to a mapped host word, and the host stops
  * issuing step graphs (8 steps each, at most 2 queued ahead) once it is set; check_interval is
- * accepted for ABI compatibility and no longer paces the stop (round 6). */
+ * accepted for ABI compatibility and no longer paces the stop (round 6).
+ * Where mio_hip_llm_set_sampling has moved a knob off its neutral value, the sampler chain
+ * (penalties -> top-k -> top-p -> min-p) runs as one more launch of every step, between the
+ * lm_head and the launch that takes the token (the next step's first launch, or the flush after
+ * the last step): the draw is then over the ids the chain keeps, on the penalised logits. */
 int mio_hip_llm_generate(mio_hip_llm *m, const int32_t *prompt, int n_prompt, int max_tokens,
                          float temperature, uint64_t seed, int32_t allow_lo, int32_t allow_hi,
                          int32_t eos0, int32_t eos1, int32_t check_interval,
@@ -178,6 +182,33 @@ int mio_hip_llm_generate_batch(mio_hip_llm *m, const int32_t *prompts, const int
                                int max_tokens, float temperature, const uint64_t *seeds, int32_t allow_lo,
                                int32_t allow_hi, int32_t eos0, int32_t eos1, int32_t check_interval,
                                int32_t *out_tokens, int32_t *n_out);
+
+/* The sampler chain, on the device ("sampler chain"): per step and stream, over the
+ * window [allow_lo, allow_hi),
+ *   penalties  for every id among the last repeat_last_n SAMPLED tokens of this generate (prompt
+ *              and forced tokens are no history), c = its occurrences there:
+ *              l = l > 0 ? l / repeat_penalty : l * repeat_penalty, then
+ *              l = l - (c * frequency_penalty + presence_penalty), each operation rounded f32;
+ *   order      ids by penalised logit descending, then id ascending; every cut keeps a prefix and
+ *              the first id always stays;
+ *   top_k      the first k ids (k <= 0 or k >= the window: off);
+ *   top_p      id i stays iff the probability mass (softmax at temperature 1 over the top-k
+ *              survivors) of the ids before it is < top_p (>= 1: off; <= 0: one id);
+ *   min_p      id i stays iff l_i >= l_max + log(min_p) (<= 0: off);
+ *   draw       argmax of l / temperature + noise over the ids left (temperature <= 0: of l).
+ * Neutral values: top_k 0, top_p 1, min_p 0, repeat_penalty 1, frequency_penalty 0,
+ * presence_penalty 0 (repeat_last_n then does not matter; its default is 64, its range 0..256,
+ * 0 = no penalties). With every knob neutral the step has exactly the launches it has without
+ * this call. Settings stay on the handle and apply to later mio_hip_llm_generate /
+ * _generate_batch calls (every stream of a batch shares them); s == NULL sets the neutral
+ * values. NaN, repeat_penalty <= 0 and repeat_last_n outside 0..256: MIO_ERR_INVALID. */
+typedef struct mio_sampling {
+    int32_t top_k;
+    float top_p, min_p, repeat_penalty, frequency_penalty, presence_penalty;
+    int32_t repeat_last_n;
+} mio_sampling;
+int mio_hip_llm_set_sampling(mio_hip_llm *m, const mio_sampling *s);
+int mio_hip_llm_get_sampling(const mio_hip_llm *m, mio_sampling *s);
 
 /* Parity helpers: one decode step of `token` at `pos` (as mio_hip_llm_eval), its residual
  * stream before layer 0 and after every layer into x_layers[(n_layer + 1) * n_embd] (and the
@@ -206,9 +237,12 @@ int mio_hip_llm_trace_kernel(mio_hip_llm *m, int which, uint64_t *out);
  * prepared; 3-6 = prologue steps in -DMIO_TL_DIAG builds.
  * Advances the decode state. */
 int mio_hip_llm_timeline(mio_hip_llm *m, uint64_t *out, int max_launches, int *n_launches);
-/* The launches of one decode step in order, as the `which` of mio_hip_llm_time_kernel: per
- * layer 0 attn_in, 1 attention, 2 attn_out (or 10 / 11: fused), or for an lfm2 short-conv
- * layer 8 conv_in, 9 conv_out; then 3 ffn_in, 4 ffn_down (or 12: fused); last 6 lm_head. *n = the count; kinds may be null (count only), else it needs
+/* The launches of one decode step in order, as the `which` of mio_hip_llm_time_kernel:
+ * per layer 0 attn_in, 1 attention, 2 attn_out (or 10 / 11: fused), or for an lfm2 short-conv
+ * layer 8 conv_in, 9 conv_out; then 3 ffn_in, 4 ffn_down (or 12: fused); then 6 lm_head; and
+ * last, while mio_hip_llm_set_sampling has a knob off its neutral value, 14 the sampler chain.
+ * mio_hip_llm_time_kernel / _trace_kernel refuse 14 (MIO_ERR_INVALID), and mio_hip_llm_timeline
+ * replays the step without it. *n = the count; kinds may be null (count only), else it needs
  * cap >= *n entries. */
 int mio_hip_llm_step_kinds(const mio_hip_llm *m, int *kinds, int cap, int *n);
 /* lfm2 short-conv state of layer il: [4][n_embd] floats, slot p & 3 = the B*X row of position

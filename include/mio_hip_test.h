@@ -38,6 +38,20 @@ int mio_hip_llm_set_kv_rows(mio_hip_llm *m, int il, int p0, int n_pos, const uin
  * their own). A short-conv layer is refused with MIO_ERR_INVALID. */
 int mio_hip_llm_debug_attention(mio_hip_llm *m, int il, int pos, int which, const float *qkv, float *att);
 
+/* ---------------- the sampler chain on an injected logits row ----------------
+ * One launch of the chain kernel (penalties -> top-k -> top-p -> min-p -> draw, mio_hip.h
+ * mio_sampling) followed by the flush sampler that takes its token: logits[n_vocab] is the row,
+ * history[n_history] the tokens the run is taken to have sampled before `step` (oldest first;
+ * the launch reads the last repeat_last_n of them; step >= n_history, step < n_ctx), the
+ * window is [lo, hi) exactly (0 <= lo < n_vocab, hi <= n_vocab; hi <= lo: empty, the token is
+ * lo). *token is the sampled id, *kept the number of ids the chain kept, *cut_id the last kept
+ * id of the order (logit descending, then id ascending); kept / cut_id / penalised may be NULL.
+ * penalised[n_vocab]: the row after the penalties (bits of ids outside the history unchanged).
+ * Every knob neutral runs the launch all the same (it keeps every id). */
+int mio_hip_llm_debug_sample_chain(mio_hip_llm *m, const float *logits, const int32_t *history, int n_history,
+                                   const mio_sampling *s, float temperature, uint64_t seed, int step, int32_t lo,
+                                   int32_t hi, int32_t *token, int32_t *kept, int32_t *cut_id, float *penalised);
+
 /* ---------------- MioCodec kernels, one launch each ----------------
  * Parity entry points of csrc/hip/codec_kernels.hip (csrc/testlib/debug_codec_capi.cpp). Every
  * pointer is host memory; a call uploads its operands, launches on the device's stream, waits

@@ -58,7 +58,12 @@ public:
         int device = -1;  // extension: GPU index (-1 = MIO_DEVICE / LOCAL_RANK / 0)
     };
 
-    struct Options {
+    // The sampler chain's fields grew Options past the 12 bytes it had. The tag puts the layout
+    // into the mangled name of every member function that takes an Options, so a program compiled
+    // against this header binds to the entry points that read the new fields, and one compiled
+    // against the earlier header keeps binding to the untagged ones, which the library still
+    // exports and runs with the neutral values (csrc/host/tts.cpp, "earlier entry points").
+    struct [[gnu::abi_tag("opt2")]] Options {
         float temperature = -1.0f; // negative => use Config default
         int max_tokens = -1;       // negative => use Config default
         bool skip_llm = false;     // when true, text is raw <|s_N|> token text
@@ -67,6 +72,16 @@ public:
         // speech ids / never stop at an end token
         bool speech_only = false;
         bool ignore_eos = false;
+        // extensions: the on-device sampler chain (mio_hip.h mio_sampling: penalties -> top-k
+        // -> top-p -> min-p before the temperature draw). These defaults are the neutral
+        // values: the reference's temp + dist pair, unchanged.
+        int top_k = 0;
+        float top_p = 1.0f;
+        float min_p = 0.0f;
+        float repeat_penalty = 1.0f;
+        int repeat_last_n = 64;
+        float frequency_penalty = 0.0f;
+        float presence_penalty = 0.0f;
     };
 
     using StreamCallback = std::function<bool(const float * samples,

@@ -72,7 +72,15 @@ struct SampleCfg {
     int *out_tokens;     // [max_steps] sampled/forced next token per step
     int max_steps;
     int *host_done;      // mapped host word set to 1 with StepState.done (null: none)
+    // the sampler chain (k_sample_chain, llm_sample_chain.hip); read by that launch alone, which
+    // is in the step only when a knob is off its neutral value
+    int top_k;                // <= 0 or >= the window: off
+    float top_p, min_p;       // >= 1: off; <= 0: off
+    float repeat_penalty, frequency_penalty, presence_penalty;  // 1, 0, 0: off
+    int repeat_last_n;        // history length, 0..kChainHistMax (0: no penalties)
+    int first_step;           // the first sampled step: out_tokens[first_step .. step) is the history
 };
+constexpr int kChainHistMax = 256;
 
 // lfm2 gated short conv: kernel width (shortconv.l_cache) and the ring of bx values kept per
 // layer (slot p & 3 holds position p; positions p-2, p-1 are read while p is written)
@@ -177,10 +185,11 @@ struct BatchBuffers {
     float *smp;
 };
 // One decode step of all B sequences: every layer with one weight pass per launch, the
-// lm_head for all B, then per-sequence sampling + next embedding + state advance.
+// lm_head for all B, (chain: the sampler chain launch,) then per-sequence sampling + next
+// embedding + state advance.
 void launch_batch_step(const LlmDims &d, const LayerW *layers, int n_layer, _Float16 *kcache, _Float16 *vcache,
                        const float *out_norm, const QMat &lm, const QMat &tok_embd, const PrefillBuffers &pb,
-                       const BatchBuffers &bb, int B, hipStream_t s);
+                       const BatchBuffers &bb, int B, bool chain, hipStream_t s);
 // B streams fit one batched step (B <= kBatchMax and the lm_head's LDS for its weight type)
 bool batch_supported(const LlmDims &d, int B, int lm_type);
 // Embedding of st[b].token into pb.x[b] for every sequence (decode start).
@@ -204,7 +213,8 @@ enum StepKind : int {
     kLayerAtt = 11,   // k_layer_att: 0 + 1 + 2
     kFfn = 12,        // k_ffn: 3 + 4
     kLayer = 13,      // k_layer: 11 + 12
-    kStepKindEnd = 14,
+    kSampleChain = 14,  // k_sample_chain: penalties + top-k / top-p / min-p + draw (after 6, chain on only)
+    kStepKindEnd = 15,
 };
 // What every launch of a model's step shares (the host builds it once per model).
 struct StepCtx {
@@ -214,6 +224,20 @@ struct StepCtx {
     const float *out_norm;
     QMat lm, tok;
 };
+// The sampler chain launch: stream t (one workgroup each, B of them) reads logits + t * stride,
+// st[t], cfg[t] and rewrites its nblk sampling partials smp + t * nblk * 2. dbg (parity entry,
+// or null): {kept count, id at the cut, 1} per stream; keep: the penalised row stays in logits.
+struct ChainArgs {
+    float *logits;
+    size_t stride;
+    const StepState *st;
+    const SampleCfg *cfg;
+    float *smp;
+    int nblk;
+    int *dbg;
+    int keep;
+};
+void launch_sample_chain(const ChainArgs &a, int B, hipStream_t s);
 // an empty one-workgroup launch (the timing reference of mio_hip_llm_time_kernel)
 void launch_nop(hipStream_t s);
 // Launch kernel `which` of a decode step (of layer il where it is a layer's) on stream s.

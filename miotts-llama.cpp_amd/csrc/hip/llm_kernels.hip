@@ -726,6 +726,9 @@ void launch_step_kernel(StepKind which, const StepCtx &c, int il, const LlmBuffe
             });
             break;
         }
+        case kSampleChain:
+            launch_sample_chain(ChainArgs{b.logits, 0, b.st, b.cfg, b.smp, lm_head_blocks(d), nullptr, 0}, 1, s);
+            break;
         case kSample:
             hipLaunchKernelGGL(k_sample<DG>, dim3(1), dim3(ST), 0, s, d, tok_embd, lm_head_blocks(d), b);
             break;

@@ -1454,7 +1454,7 @@ bool batch_supported(const LlmDims &d, int B, int lm_type) {
 
 void launch_batch_step(const LlmDims &d, const LayerW *layers, int n_layer, _Float16 *kcache, _Float16 *vcache,
                        const float *out_norm, const QMat &lm, const QMat &tok_embd, const PrefillBuffers &pb,
-                       const BatchBuffers &bb, int B, hipStream_t s) {
+                       const BatchBuffers &bb, int B, bool chain, hipStream_t s) {
     launch_layers(d, layers, n_layer, kcache, vcache, pb, B, d.max_splits, true, s);
     launch_quant(d, 0, pb.x, d.n_embd, out_norm, akind(lm.type), pb, B, s);
     const int nblk = matvec_grid(d, d.n_vocab);  // the batched lm_head keeps one workgroup per CU
@@ -1468,6 +1468,7 @@ void launch_batch_step(const LlmDims &d, const LayerW *layers, int n_layer, _Flo
         launch_mmq(&sg, &lm.type, 1, MMQ_STORE,
                    MmqArgs{pb.act, act_bytes(d.n_embd), d.n_embd, B, bb.logits, lm.rows, {}}, s);
         hipLaunchKernelGGL(k_bt_gumbel, dim3(nblk), dim3(MT), 0, s, lm.rows, bb, B);
+        if (chain) launch_sample_chain(ChainArgs{bb.logits, (size_t)lm.rows, bb.st, bb.cfg, bb.smp, nblk, nullptr, 0}, B, s);
         hipLaunchKernelGGL(k_bt_sample, dim3(B), dim3(ST), 0, s, d, tok_embd, nblk, pb, bb);
         return;
     }
@@ -1476,6 +1477,7 @@ void launch_batch_step(const LlmDims &d, const LayerW *layers, int n_layer, _Flo
         hipLaunchKernelGGL((k_bt_lm_head<NP, T>), dim3(nblk), dim3(MT), batch_lm_head_lds(d, B, T), s, d, out_norm, lm,
                            pb, bb, B);
     });
+    if (chain) launch_sample_chain(ChainArgs{bb.logits, (size_t)lm.rows, bb.st, bb.cfg, bb.smp, nblk, nullptr, 0}, B, s);
     hipLaunchKernelGGL(k_bt_sample, dim3(B), dim3(ST), 0, s, d, tok_embd, nblk, pb, bb);
 }
 

@@ -110,17 +110,36 @@ int layer_kinds(const mio_hip_llm *m, int il, mio::StepKind *w) {
     return n;
 }
 
-// every launch of a step in order: the layers', then lm_head
+// A sampler-chain knob is off its neutral value: the step gains the chain launch.
+bool chain_on(const mio::SamplingParams &sp) {
+    return sp.top_k > 0 || sp.top_p < 1.0f || sp.min_p > 0.0f || sp.repeat_penalty != 1.0f ||
+           sp.frequency_penalty != 0.0f || sp.presence_penalty != 0.0f;
+}
+
+int check_chain(const mio::SamplingParams &sp, const char *who) {
+    const float f[5] = {sp.top_p, sp.min_p, sp.repeat_penalty, sp.frequency_penalty, sp.presence_penalty};
+    for (float v : f) MIO_REQUIRE(v == v, MIO_ERR_INVALID, "%s: a sampling parameter is NaN", who);
+    MIO_REQUIRE(sp.repeat_penalty > 0.0f, MIO_ERR_INVALID, "%s: repeat_penalty %g must be > 0", who,
+                (double)sp.repeat_penalty);
+    MIO_REQUIRE(sp.repeat_last_n >= 0 && sp.repeat_last_n <= mio::kChainHistMax, MIO_ERR_INVALID,
+                "%s: repeat_last_n %d outside 0..%d", who, sp.repeat_last_n, mio::kChainHistMax);
+    return MIO_OK;
+}
+
+// every launch of a step in order: the layers', then lm_head, then the sampler chain where the
+// handle's sampling settings (mio_hip_llm_set_sampling) turn it on
 std::vector<mio::StepKind> step_kinds(const mio_hip_llm *m) {
     std::vector<mio::StepKind> k;
     mio::StepKind w[kLayerKindsMax];
     for (int il = 0; il < m->n_layer; ++il) k.insert(k.end(), w, w + layer_kinds(m, il, w));
     k.push_back(mio::kLmHead);
+    if (chain_on(m->sampling)) k.push_back(mio::kSampleChain);
     return k;
 }
 
-// One decode step on m->d->stream (tl: optional step timeline, diagnostic).
-int issue_step(mio_hip_llm *m, unsigned long long *tl) {
+// One decode step on m->d->stream (tl: optional step timeline, diagnostic; chain: with the
+// sampler chain launch behind lm_head).
+int issue_step(mio_hip_llm *m, unsigned long long *tl, bool chain) {
     hipStream_t s = m->d->stream;
     int seq = 0;
     auto bufs = [&]() {
@@ -132,6 +151,7 @@ int issue_step(mio_hip_llm *m, unsigned long long *tl) {
     for (int il = 0; il < m->n_layer; ++il)
         for (int i = 0, n = layer_kinds(m, il, w); i < n; ++i) mio::launch_step_kernel(w[i], m->ctx(), il, bufs(), s);
     mio::launch_step_kernel(mio::kLmHead, m->ctx(), 0, bufs(), s);
+    if (chain) mio::launch_step_kernel(mio::kSampleChain, m->ctx(), 0, m->buf, s);
     return MIO_OK;
 }
 
@@ -143,17 +163,25 @@ int flush_sample(mio_hip_llm *m) {
     return MIO_OK;
 }
 
-int ensure_graph(mio_hip_llm *m) {
-    auto steps = [m](int n) {
-        return [m, n] {
+// The step graphs: the plain pair always; chain: also the pair whose steps carry the sampler
+// chain launch (captured on the first generate that needs it, beside the plain pair, so
+// toggling the chain never re-captures either).
+int ensure_graph(mio_hip_llm *m, bool chain) {
+    auto steps = [m](int n, bool ch) {
+        return [m, n, ch] {
             int rc = MIO_OK;
-            for (int i = 0; i < n && !rc; ++i) rc = issue_step(m);
+            for (int i = 0; i < n && !rc; ++i) rc = issue_step(m, nullptr, ch);
             return rc;
         };
     };
     int rc;
-    if (!m->graph && (rc = mio::capture_graph(m->d->stream, steps(1), m->graph.put()))) return rc;
-    if (!m->graph_n && (rc = mio::capture_graph(m->d->stream, steps(graph_steps()), m->graph_n.put()))) return rc;
+    if (!m->graph && (rc = mio::capture_graph(m->d->stream, steps(1, false), m->graph.put()))) return rc;
+    if (!m->graph_n && (rc = mio::capture_graph(m->d->stream, steps(graph_steps(), false), m->graph_n.put())))
+        return rc;
+    if (!chain) return MIO_OK;
+    if (!m->graph_c && (rc = mio::capture_graph(m->d->stream, steps(1, true), m->graph_c.put()))) return rc;
+    if (!m->graph_cn && (rc = mio::capture_graph(m->d->stream, steps(graph_steps(), true), m->graph_cn.put())))
+        return rc;
     return MIO_OK;
 }
 
@@ -172,7 +200,7 @@ mio::SampleCfg greedy_cfg(const mio_hip_llm *m) {
     return c;
 }
 
-// A generate's sampler (sp.seed is not read: a batch has one seed per stream): tokens to
+// A generate's sampler with sp's chain knobs (sp.seed is not read: a batch has one seed per stream): tokens to
 // out_tokens, the end token's host word host_done (device address). force / n_force stay
 // null / 0: the single-stream generate sets its own.
 mio::SampleCfg sample_cfg(const mio_hip_llm *m, const mio::SamplingParams &sp, uint64_t seed, int *out_tokens,
@@ -186,6 +214,10 @@ mio::SampleCfg sample_cfg(const mio_hip_llm *m, const mio::SamplingParams &sp, u
     c.force = nullptr, c.n_force = 0;
     c.out_tokens = out_tokens, c.max_steps = max_steps;
     c.host_done = host_done;
+    c.top_k = sp.top_k, c.top_p = sp.top_p, c.min_p = sp.min_p;
+    c.repeat_penalty = sp.repeat_penalty, c.frequency_penalty = sp.frequency_penalty;
+    c.presence_penalty = sp.presence_penalty, c.repeat_last_n = sp.repeat_last_n;
+    c.first_step = 0;  // the caller's: the first step whose token is sampled
     return c;
 }
 
@@ -309,11 +341,12 @@ int snap_push(mio_hip_llm *m) {
 int run_steps(mio_hip_llm *m, int n) {
     if (no_graph()) {
         for (int i = 0; i < n; ++i)
-            if (int rc = issue_step(m)) return rc;
+            if (int rc = issue_step(m, nullptr, m->chain)) return rc;
         return MIO_OK;
     }
-    for (const int gs = graph_steps(); n >= gs; n -= gs) MIO_HIP_CHECK(hipGraphLaunch(m->graph_n, m->d->stream));
-    for (; n > 0; --n) MIO_HIP_CHECK(hipGraphLaunch(m->graph, m->d->stream));
+    hipGraphExec_t g1 = m->chain ? m->graph_c : m->graph, gn = m->chain ? m->graph_cn : m->graph_n;
+    for (const int gs = graph_steps(); n >= gs; n -= gs) MIO_HIP_CHECK(hipGraphLaunch(gn, m->d->stream));
+    for (; n > 0; --n) MIO_HIP_CHECK(hipGraphLaunch(g1, m->d->stream));
     return MIO_OK;
 }
 
@@ -378,12 +411,14 @@ int llm_begin(mio_hip_llm *m, const int32_t *prompt, int n_prompt, int max_new, 
     for (int i = 0; i < n_prompt; ++i)
         MIO_REQUIRE(prompt[i] >= 0 && prompt[i] < m->dims.n_vocab, MIO_ERR_INVALID,
                     "llm_begin: token %d out of vocab", prompt[i]);
-    int rc = mio::bind(m->d);
-    if (rc || (rc = snaps_drain(m)) || (rc = upload_force(m, prompt, n_prompt))) return rc;
+    int rc = check_chain(sp, "llm_begin");
+    if (rc || (rc = mio::bind(m->d)) || (rc = snaps_drain(m)) || (rc = upload_force(m, prompt, n_prompt))) return rc;
     __atomic_store_n(m->host_done.get(), 0, __ATOMIC_SEQ_CST);  // the cfg copy below is stream-ordered behind it
     SampleCfg c = sample_cfg(m, sp, sp.seed, m->d_tokens, m->host_done_dev, m->max_steps);
     c.force = m->d_force, c.n_force = m->max_steps;
-    if ((rc = put_cfg(m, c)) || (rc = ensure_graph(m))) return rc;
+    c.first_step = n_prompt - 1;  // the prompt's forced steps are no history
+    m->chain = chain_on(sp);
+    if ((rc = put_cfg(m, c)) || (rc = ensure_graph(m, m->chain))) return rc;
     m->n_prompt = n_prompt;
     m->max_new = max_new;
     m->steps_total = n_prompt - 1 + max_new;
@@ -463,6 +498,27 @@ int llm_poll(mio_hip_llm *m, std::vector<int32_t> &out, bool *done) {
 }
 
 }  // namespace mio
+
+extern "C" int mio_hip_llm_set_sampling(mio_hip_llm *m, const mio_sampling *s) {
+    MIO_REQUIRE(m, MIO_ERR_INVALID, "llm_set_sampling: null handle");
+    mio::SamplingParams sp;  // neutral
+    if (s) {
+        sp.top_k = s->top_k, sp.top_p = s->top_p, sp.min_p = s->min_p, sp.repeat_penalty = s->repeat_penalty;
+        sp.frequency_penalty = s->frequency_penalty, sp.presence_penalty = s->presence_penalty;
+        sp.repeat_last_n = s->repeat_last_n;
+    }
+    if (int rc = check_chain(sp, "llm_set_sampling")) return rc;
+    m->sampling = sp;
+    return MIO_OK;
+}
+
+extern "C" int mio_hip_llm_get_sampling(const mio_hip_llm *m, mio_sampling *s) {
+    MIO_REQUIRE(m && s, MIO_ERR_INVALID, "llm_get_sampling: null");
+    const mio::SamplingParams &sp = m->sampling;
+    *s = mio_sampling{sp.top_k, sp.top_p, sp.min_p, sp.repeat_penalty, sp.frequency_penalty, sp.presence_penalty,
+                      sp.repeat_last_n};
+    return MIO_OK;
+}
 
 extern "C" int mio_hip_llm_load_ms(const mio_hip_llm *m, double *ms) {
     MIO_REQUIRE(m && ms, MIO_ERR_INVALID, "llm_load_ms: null");
@@ -553,7 +609,7 @@ extern "C" int mio_hip_llm_generate(mio_hip_llm *m, const int32_t *prompt, int n
                                     int32_t eos0, int32_t eos1, int32_t check_interval, int32_t *out_tokens,
                                     int *n_out) {
     MIO_REQUIRE(m && out_tokens && n_out, MIO_ERR_INVALID, "llm_generate: null argument");
-    mio::SamplingParams sp;
+    mio::SamplingParams sp = m->sampling;  // the chain knobs (mio_hip_llm_set_sampling)
     sp.temperature = temperature, sp.seed = seed, sp.allow_lo = allow_lo, sp.allow_hi = allow_hi;
     sp.eos0 = eos0, sp.eos1 = eos1;
     int rc = mio::llm_begin(m, prompt, n_prompt, max_tokens, sp);

@@ -20,6 +20,11 @@ struct SamplingParams {
     uint64_t seed = 42;      // llama_sampler_init_dist(42), test-to-speech.cpp:130
     int allow_lo = 0, allow_hi = -1;  // restrict sampling to [lo, hi) (-1 = n_vocab)
     int eos0 = -1, eos1 = -1;
+    // the sampler chain (include/mio_hip.h mio_sampling; these defaults are the neutral values:
+    // no chain launch)
+    int top_k = 0;
+    float top_p = 1.0f, min_p = 0.0f, repeat_penalty = 1.0f, frequency_penalty = 0.0f, presence_penalty = 0.0f;
+    int repeat_last_n = 64;
 };
 
 // Incremental generation on the device: begin() seeds the prompt, run() enqueues decode
@@ -45,5 +50,12 @@ int llm_set_kv_rows(mio_hip_llm *m, int il, int p0, int n_pos, const uint16_t *k
 // which = 1 (k_attention) or 10 (k_att_o); att[H hd] receives LlmBuffers.att. Leaves the decode
 // state at pos and cache row pos written.
 int llm_debug_attention(mio_hip_llm *m, int il, int pos, int which, const float *qkv, float *att);
+// One sampler chain launch (k_sample_chain) + the flush sampler on the injected row
+// logits[n_vocab], with history[n_history] as the tokens sampled before `step` and sp's
+// temperature, seed, window and chain knobs: the token, the kept count, the id at the cut and
+// (not null) the penalised row.
+int llm_debug_sample_chain(mio_hip_llm *m, const float *logits, const int32_t *history, int n_history,
+                           const SamplingParams &sp, int step, int32_t *token, int32_t *kept, int32_t *cut_id,
+                           float *penalised);
 
 }  // namespace mio

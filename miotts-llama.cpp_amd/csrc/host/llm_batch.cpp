@@ -14,7 +14,7 @@ size_t batch_seq_ring(const mio_hip_llm *m) { return (size_t)m->n_layer * mio::k
 int batch_ensure(mio_hip_llm *m, int B) {
     auto &bt = m->bt;
     if (bt.B == B) return MIO_OK;
-    bt.graph.reset(), bt.graph_n.reset();
+    bt.graph.reset(), bt.graph_n.reset(), bt.graph_c.reset(), bt.graph_cn.reset();
     for (void *p : bt.allocs) hipFree(p);
     bt.allocs.clear();
     bt.B = 0;
@@ -70,30 +70,32 @@ mio::PrefillBuffers step_pb(mio_hip_llm *m) {
 
 mio::BatchBuffers batch_bb(mio_hip_llm *m) { return mio::BatchBuffers{m->bt.st, m->bt.cfg, m->bt.logits, m->bt.smp}; }
 
-int issue_batch_steps(mio_hip_llm *m, int n) {
+int issue_batch_steps(mio_hip_llm *m, int n, bool chain) {
     for (int i = 0; i < n; ++i)
         mio::launch_batch_step(m->dims, m->layers.data(), m->n_layer, m->bt.kc, m->bt.vc, m->out_norm, m->lm, m->tok,
-                               step_pb(m), batch_bb(m), m->bt.B, m->d->stream);
+                               step_pb(m), batch_bb(m), m->bt.B, chain, m->d->stream);
     return MIO_OK;
 }
 
 // n batched steps: the first ever step for this B runs eagerly (its launches set the
 // kernels' LDS attributes outside any capture), then 1- and graph_steps()-step graphs replay.
-int run_batch(mio_hip_llm *m, int n) {
+// chain: the steps carry the sampler chain launch; they have a graph pair of their own.
+int run_batch(mio_hip_llm *m, int n, bool chain) {
     auto &bt = m->bt;
     hipStream_t s = m->d->stream;
-    if (n > 0 && (no_graph() || !bt.graph)) {
-        issue_batch_steps(m, no_graph() ? n : 1);
+    mio::GraphExec &g1 = chain ? bt.graph_c : bt.graph, &gn = chain ? bt.graph_cn : bt.graph_n;
+    if (n > 0 && (no_graph() || !g1)) {
+        issue_batch_steps(m, no_graph() ? n : 1, chain);
         MIO_HIP_CHECK(hipGetLastError());
         if (no_graph()) return MIO_OK;
         --n;
         int rc;
-        if ((rc = mio::capture_graph(s, [m] { return issue_batch_steps(m, 1); }, bt.graph.put())) ||
-            (rc = mio::capture_graph(s, [m] { return issue_batch_steps(m, graph_steps()); }, bt.graph_n.put())))
+        if ((rc = mio::capture_graph(s, [m, chain] { return issue_batch_steps(m, 1, chain); }, g1.put())) ||
+            (rc = mio::capture_graph(s, [m, chain] { return issue_batch_steps(m, graph_steps(), chain); }, gn.put())))
             return rc;
     }
-    for (const int gs = graph_steps(); n >= gs; n -= gs) MIO_HIP_CHECK(hipGraphLaunch(bt.graph_n, s));
-    for (; n > 0; --n) MIO_HIP_CHECK(hipGraphLaunch(bt.graph, s));
+    for (const int gs = graph_steps(); n >= gs; n -= gs) MIO_HIP_CHECK(hipGraphLaunch(gn, s));
+    for (; n > 0; --n) MIO_HIP_CHECK(hipGraphLaunch(g1, s));
     return MIO_OK;
 }
 
@@ -156,8 +158,9 @@ extern "C" int mio_hip_llm_generate_batch(mio_hip_llm *m, const int32_t *prompts
     }
     // per-stream state: decoding starts at position P_b = len_b - 1 with the step counter at
     // P_b (the single-stream generate's sampler stream)
-    mio::SamplingParams sp;
+    mio::SamplingParams sp = m->sampling;  // the chain knobs, shared by every stream
     sp.temperature = temperature, sp.allow_lo = allow_lo, sp.allow_hi = allow_hi, sp.eos0 = eos0, sp.eos1 = eos1;
+    const bool chain = chain_on(sp);
     std::vector<mio::StepState> st(B);
     std::vector<mio::SampleCfg> cf(B);
     std::vector<int> budget(B);
@@ -167,6 +170,7 @@ extern "C" int mio_hip_llm_generate_batch(mio_hip_llm *m, const int32_t *prompts
         // as llm_begin: a full context ends the stream after n_ctx - len + 1 tokens
         budget[b] = std::min(max_tokens, D.n_ctx - prompt_lens[b] + 1);
         cf[b] = sample_cfg(m, sp, seeds[b], bt.tokens + (size_t)b * D.n_ctx, m->host_done_dev + 1 + b, P + budget[b]);
+        cf[b].first_step = P;  // each stream's own history: the tokens it sampled
         __atomic_store_n(m->host_done + 1 + b, 0, __ATOMIC_SEQ_CST);
     }
     MIO_HIP_CHECK(hipMemcpyAsync(bt.st, st.data(), B * sizeof(mio::StepState), hipMemcpyHostToDevice, s));
@@ -184,7 +188,7 @@ extern "C" int mio_hip_llm_generate_batch(mio_hip_llm *m, const int32_t *prompts
             all = issued >= budget[b] || __atomic_load_n(m->host_done + 1 + b, __ATOMIC_ACQUIRE);
         if (all) break;
         const int n = std::min(graph_steps(), max_tokens - issued);
-        if ((rc = run_batch(m, n))) return rc;
+        if ((rc = run_batch(m, n, chain))) return rc;
         issued += n;
         if ((rc = run_mark(m, k))) return rc;
     }

@@ -141,6 +141,60 @@ int mio::llm_debug_attention(mio_hip_llm *m, int il, int pos, int which, const f
     return check_handoff(m);
 }
 
+// One sampler chain launch on an injected logits row (parity tests): the row replaces
+// buf.logits, `history` (the tokens the run is taken to have sampled so far, oldest first)
+// fills the token ring in front of `step`, the lm_head partials are set to "no id", the chain
+// launch and the flush sampler run, and the state's token comes back with the launch's kept
+// count and cut id (0 / -1 where the launch left the step to the plain sampler: empty window).
+int mio::llm_debug_sample_chain(mio_hip_llm *m, const float *logits, const int32_t *history, int n_history,
+                                const SamplingParams &sp, int step, int32_t *token, int32_t *kept, int32_t *cut_id,
+                                float *penalised) {
+    MIO_REQUIRE(m && logits && token && n_history >= 0 && (history || !n_history), MIO_ERR_INVALID,
+                "llm_debug_sample_chain: null argument");
+    MIO_REQUIRE(step >= n_history && step < m->max_steps, MIO_ERR_INVALID,
+                "llm_debug_sample_chain: step %d outside [n_history %d, %d)", step, n_history, m->max_steps);
+    int rc = check_chain(sp, "llm_debug_sample_chain");
+    if (rc || (rc = mio::bind(m->d))) return rc;
+    hipStream_t s = m->d->stream;
+    const size_t V = (size_t)m->dims.n_vocab;
+    const int nblk = mio::lm_head_blocks(m->dims);
+    mio::SampleCfg c = sample_cfg(m, sp, sp.seed, m->d_tokens, nullptr, m->max_steps);
+    c.first_step = step - n_history;
+    if ((rc = put_cfg(m, c))) return rc;
+    const mio::StepState st{0, step, 0, 0, 1};
+    std::vector<float> none((size_t)nblk * 2);
+    const int imax = INT_MAX;
+    for (int i = 0; i < nblk; ++i) none[2 * i] = -INFINITY, std::memcpy(&none[2 * i + 1], &imax, 4);
+    int *dbg = nullptr;
+    MIO_HIP_CHECK(hipMalloc(&dbg, 3 * sizeof(int)));
+    auto run = [&]() -> int {
+        MIO_HIP_CHECK(hipMemsetAsync(dbg, 0, 3 * sizeof(int), s));
+        MIO_HIP_CHECK(hipMemcpyAsync(m->buf.st, &st, sizeof(st), hipMemcpyHostToDevice, s));
+        MIO_HIP_CHECK(hipMemcpyAsync(m->buf.logits, logits, V * 4, hipMemcpyHostToDevice, s));
+        MIO_HIP_CHECK(hipMemcpyAsync(m->buf.smp, none.data(), none.size() * 4, hipMemcpyHostToDevice, s));
+        if (n_history)
+            MIO_HIP_CHECK(hipMemcpyAsync(m->d_tokens + c.first_step, history, (size_t)n_history * 4,
+                                         hipMemcpyHostToDevice, s));
+        mio::launch_sample_chain(mio::ChainArgs{m->buf.logits, 0, m->buf.st, m->d_cfg, m->buf.smp, nblk, dbg,
+                                                penalised ? 1 : 0}, 1, s);
+        MIO_HIP_CHECK(hipGetLastError());
+        if (penalised) MIO_HIP_CHECK(hipMemcpyAsync(penalised, m->buf.logits, V * 4, hipMemcpyDeviceToHost, s));
+        if ((rc = flush_sample(m))) return rc;
+        int d3[3] = {0, 0, 0};
+        mio::StepState out{};
+        MIO_HIP_CHECK(hipMemcpyAsync(d3, dbg, sizeof(d3), hipMemcpyDeviceToHost, s));
+        MIO_HIP_CHECK(hipMemcpyAsync(&out, m->buf.st, sizeof(out), hipMemcpyDeviceToHost, s));
+        MIO_HIP_CHECK(hipStreamSynchronize(s));
+        *token = out.token;
+        if (kept) *kept = d3[2] ? d3[0] : 0;
+        if (cut_id) *cut_id = d3[2] ? d3[1] : -1;
+        return MIO_OK;
+    };
+    rc = run();
+    hipFree(dbg);
+    return rc;
+}
+
 namespace {
 
 // The layer a diagnostic launch of `kind` runs on: the first layer at or after n_layer / 2
@@ -158,6 +212,8 @@ int kernel_layer(const mio_hip_llm *m, mio::StepKind kind) {
 int diag_prepare(mio_hip_llm *m, int which, const char *who, int *il) {
     MIO_REQUIRE(m && m->graph, MIO_ERR_INVALID, "%s: run generate/eval first", who);
     MIO_REQUIRE(which >= 0 && which < mio::kStepKindEnd, MIO_ERR_INVALID, "%s: which %d", who, which);
+    MIO_REQUIRE(which != mio::kSampleChain, MIO_ERR_INVALID,
+                "%s: the sampler chain (kind %d) is not a launch the diagnostics run", who, which);
     *il = kernel_layer(m, (mio::StepKind)which);
     MIO_REQUIRE(*il >= 0, MIO_ERR_INVALID, "%s: the model has no layer with kernel %d", who, which);
     return mio::bind(m->d);
@@ -357,7 +413,9 @@ extern "C" int mio_hip_llm_timeline(mio_hip_llm *m, uint64_t *out, int max_launc
     MIO_REQUIRE(m && out && n_launches && m->graph, MIO_ERR_INVALID, "llm_timeline: run generate/eval first");
     int rc = mio::bind(m->d);
     if (rc) return rc;
-    const int nl = (int)step_kinds(m).size();
+    // the timeline replays the plain step (issue_step without the chain launch, which records no
+    // marks), whatever the handle's sampling settings: the count leaves kind 14 out
+    const int nl = (int)step_kinds(m).size() - (chain_on(m->sampling) ? 1 : 0);
     MIO_REQUIRE(max_launches >= nl, MIO_ERR_INVALID, "llm_timeline: need %d launch slots", nl);
     hipStream_t s = m->d->stream;
     const size_t nslot = (size_t)nl * mio::kTlSlots * 8;  // MIO_TL_SLOT: kTlSlots workgroup slots per launch

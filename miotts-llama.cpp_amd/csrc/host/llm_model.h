@@ -60,6 +60,7 @@ struct mio_hip_llm {
         int *ppos = nullptr, *pseq = nullptr, *ptok = nullptr;  // flattened prompt prefill lists
         float *ring = nullptr;  // lfm2: [B][n_layer][kConvSlots][n_embd] short-conv rings
         mio::GraphExec graph, graph_n;
+        mio::GraphExec graph_c, graph_cn;  // with the sampler chain launch
         std::vector<void *> allocs;
     } bt;
     int max_steps = 0;
@@ -78,6 +79,13 @@ struct mio_hip_llm {
     // decode-step graphs, captured once (the sampling config is device-resident):
     // one step, and graph_steps() steps back to back (fewer graph launches per token)
     mio::GraphExec graph, graph_n;
+    // the same pair with the sampler chain launch in every step (captured when a generate first
+    // runs with a chain knob on; the pair above is never re-captured)
+    mio::GraphExec graph_c, graph_cn;
+    // the chain knobs later generates run with (mio_hip_llm_set_sampling; the other fields are
+    // unused), and whether the generate in progress has the chain launch in its steps
+    mio::SamplingParams sampling;
+    bool chain = false;
     // prompt prefills replayed as graphs, by prompt length (the first prefill of a length runs
     // eagerly and is captured: ~280 launches that eager issue makes host-bound)
     std::map<int, mio::GraphExec> prefill_graphs;
@@ -152,9 +160,11 @@ constexpr int kLayerKindsMax = 5;
 int layer_kinds(const mio_hip_llm *m, int il, mio::StepKind *w);  // layer il's launches in order; the count
 std::vector<mio::StepKind> step_kinds(const mio_hip_llm *m);      // every launch of a step in order
 // llm.cpp: the decode runtime
-int issue_step(mio_hip_llm *m, unsigned long long *tl = nullptr);
+int issue_step(mio_hip_llm *m, unsigned long long *tl = nullptr, bool chain = false);
 int flush_sample(mio_hip_llm *m);
-int ensure_graph(mio_hip_llm *m);
+int ensure_graph(mio_hip_llm *m, bool chain = false);
+bool chain_on(const mio::SamplingParams &sp);                     // a chain knob is off its neutral value
+int check_chain(const mio::SamplingParams &sp, const char *who);  // MIO_ERR_INVALID for values no chain takes
 int put_cfg(mio_hip_llm *m, mio::SampleCfg c);
 mio::SampleCfg greedy_cfg(const mio_hip_llm *m);
 mio::SampleCfg sample_cfg(const mio_hip_llm *m, const mio::SamplingParams &sp, uint64_t seed, int *out_tokens,

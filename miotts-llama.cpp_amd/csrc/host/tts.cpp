@@ -271,12 +271,24 @@ struct TestToSpeech::Impl {
     }
 
     // benchmark-harness options (flagged deviations): speech ids only / no stop
-    void harness(const Options &o, mio::SamplingParams &sp) const {
+    // and the sampler chain's knobs: into sp (llm_begin) and onto the runner (the C-ABI
+    // generates read them there); false where the runner refuses a value
+    bool harness(const Options &o, mio::SamplingParams &sp) const {
         if (o.speech_only) {
             const int32_t a = tok.special_id("<|s_0|>"), z = tok.special_id("<|s_12799|>");
             if (a >= 0 && z == a + 12799) sp.allow_lo = a, sp.allow_hi = z + 1;
         }
         if (o.ignore_eos) sp.eos0 = sp.eos1 = -1;
+        sp.top_k = o.top_k, sp.top_p = o.top_p, sp.min_p = o.min_p, sp.repeat_penalty = o.repeat_penalty;
+        sp.repeat_last_n = o.repeat_last_n, sp.frequency_penalty = o.frequency_penalty;
+        sp.presence_penalty = o.presence_penalty;
+        const mio_sampling s{sp.top_k, sp.top_p, sp.min_p, sp.repeat_penalty, sp.frequency_penalty,
+                             sp.presence_penalty, sp.repeat_last_n};
+        if (mio_hip_llm_set_sampling(llm, &s) != MIO_OK) {
+            fprintf(stderr, "TestToSpeech: sampling options refused: %s\n", mio_hip_last_error());
+            return false;
+        }
+        return true;
     }
 
     // codes -> PCM in HBM (d_pcm, *len samples): codec + fused iSTFT, stage seconds from GPU
@@ -416,7 +428,7 @@ bool TestToSpeech::generate_token_text(const std::string &text, const Options &o
     }
     mio::SamplingParams sp;
     sp.temperature = temp, sp.seed = 42, sp.eos0 = I.eos, sp.eos1 = I.im_end;
-    I.harness(options, sp);
+    if (!I.harness(options, sp)) return false;
     std::vector<int32_t> toks((size_t)max_tokens);
     int n = 0;
     if (mio_hip_llm_generate(I.llm, prompt.data(), (int)prompt.size(), max_tokens, temp, sp.seed, sp.allow_lo,
@@ -511,7 +523,7 @@ bool TestToSpeech::synthesize_batch_to_files(const VoiceModel &voice, const std:
     const int max_tokens = options.max_tokens > 0 ? options.max_tokens : config_.max_tokens;
     mio::SamplingParams sp;
     sp.temperature = temp, sp.seed = 42, sp.eos0 = I.eos, sp.eos1 = I.im_end;
-    I.harness(options, sp);
+    if (!I.harness(options, sp)) return false;
     constexpr size_t kGroup = 16;
     for (size_t g0 = 0; g0 < texts.size(); g0 += kGroup) {
         const int B = (int)std::min(kGroup, texts.size() - g0);
@@ -703,7 +715,7 @@ bool TestToSpeech::synthesize_stream_profiled(const VoiceModel &voice, const std
 
     mio::SamplingParams sp;
     sp.temperature = temp, sp.seed = 42, sp.eos0 = I.eos, sp.eos1 = I.im_end;
-    I.harness(options, sp);
+    if (!I.harness(options, sp)) return false;
     const auto tl0 = clk::now();
     if (mio::llm_begin(I.llm, prompt.data(), (int)prompt.size(), max_tokens, sp)) {
         fprintf(stderr, "TestToSpeech: initial decode failed: %s\n", mio::last_error());
@@ -754,3 +766,86 @@ bool TestToSpeech::synthesize_stream_profiled(const VoiceModel &voice, const std
     profile.total_sec = secs(t0, clk::now());
     return ok;
 }
+
+// ------------------------------------------------------------------ earlier entry points
+// Before the sampler chain TestToSpeech::Options had 12 bytes and no ABI tag, and the member
+// functions that take one had these mangled names. A program compiled against that header and run
+// with this library still finds them here: each copies the 12 bytes it was given (and no more)
+// into today's Options, whose chain fields keep their neutral defaults, and calls today's
+// member. (`this` is the first argument of a member function in the Itanium C++ ABI.)
+namespace {
+
+struct OptionsV1 {
+    float temperature;
+    int max_tokens;
+    bool skip_llm, apply_peak_normalization, speech_only, ignore_eos;
+};
+static_assert(sizeof(OptionsV1) == 12, "the earlier TestToSpeech::Options");
+
+TestToSpeech::Options widen(const OptionsV1 &o) {
+    TestToSpeech::Options n;
+    n.temperature = o.temperature, n.max_tokens = o.max_tokens, n.skip_llm = o.skip_llm;
+    n.apply_peak_normalization = o.apply_peak_normalization, n.speech_only = o.speech_only;
+    n.ignore_eos = o.ignore_eos;
+    return n;
+}
+
+}  // namespace
+
+#define MIO_V1 extern "C" __attribute__((visibility("default"))) bool
+#define MIO_STR "RKNSt7__cxx1112basic_stringIcSt11char_traitsIcESaIcEEE"
+#define MIO_CB "RKSt8functionIFbPKfmibEE"
+
+MIO_V1 mio_v1_generate_token_text(TestToSpeech *t, const std::string &text, const OptionsV1 &o, std::string &out)
+    asm("_ZN12TestToSpeech19generate_token_textE" MIO_STR "RKNS_7OptionsERS5_");
+MIO_V1 mio_v1_generate_token_text(TestToSpeech *t, const std::string &text, const OptionsV1 &o, std::string &out) {
+    return t->generate_token_text(text, widen(o), out);
+}
+
+MIO_V1 mio_v1_synthesize_to_vector(TestToSpeech *t, const VoiceModel &v, const std::string &text,
+                                   std::vector<float> &out, const OptionsV1 &o)
+    asm("_ZN12TestToSpeech20synthesize_to_vectorERK10VoiceModel" MIO_STR "RSt6vectorIfSaIfEERKNS_7OptionsE");
+MIO_V1 mio_v1_synthesize_to_vector(TestToSpeech *t, const VoiceModel &v, const std::string &text,
+                                   std::vector<float> &out, const OptionsV1 &o) {
+    return t->synthesize_to_vector(v, text, out, widen(o));
+}
+
+MIO_V1 mio_v1_synthesize_to_file(TestToSpeech *t, const VoiceModel &v, const std::string &text,
+                                 const std::string &path, const OptionsV1 &o)
+    asm("_ZN12TestToSpeech18synthesize_to_fileERK10VoiceModel" MIO_STR "SA_RKNS_7OptionsE");
+MIO_V1 mio_v1_synthesize_to_file(TestToSpeech *t, const VoiceModel &v, const std::string &text,
+                                 const std::string &path, const OptionsV1 &o) {
+    return t->synthesize_to_file(v, text, path, widen(o));
+}
+
+MIO_V1 mio_v1_synthesize_batch_to_files(TestToSpeech *t, const VoiceModel &v, const std::vector<std::string> &texts,
+                                        const std::vector<std::string> &paths, const OptionsV1 &o)
+    asm("_ZN12TestToSpeech25synthesize_batch_to_filesERK10VoiceModelRKSt6vectorINSt7__cxx1112basic_stringIcSt11char_"
+        "traitsIcESaIcEEESaIS9_EESD_RKNS_7OptionsE");
+MIO_V1 mio_v1_synthesize_batch_to_files(TestToSpeech *t, const VoiceModel &v, const std::vector<std::string> &texts,
+                                        const std::vector<std::string> &paths, const OptionsV1 &o) {
+    return t->synthesize_batch_to_files(v, texts, paths, widen(o));
+}
+
+MIO_V1 mio_v1_synthesize_stream(TestToSpeech *t, const VoiceModel &v, const std::string &text,
+                                const TestToSpeech::StreamCallback &cb, size_t chunk, const OptionsV1 &o)
+    asm("_ZN12TestToSpeech17synthesize_streamERK10VoiceModel" MIO_STR MIO_CB "mRKNS_7OptionsE");
+MIO_V1 mio_v1_synthesize_stream(TestToSpeech *t, const VoiceModel &v, const std::string &text,
+                                const TestToSpeech::StreamCallback &cb, size_t chunk, const OptionsV1 &o) {
+    return t->synthesize_stream(v, text, cb, chunk, widen(o));
+}
+
+MIO_V1 mio_v1_synthesize_stream_profiled(TestToSpeech *t, const VoiceModel &v, const std::string &text,
+                                         const TestToSpeech::StreamCallback &cb, size_t chunk, const OptionsV1 &o,
+                                         TestToSpeech::StreamProfile &p)
+    asm("_ZN12TestToSpeech26synthesize_stream_profiledERK10VoiceModel" MIO_STR MIO_CB
+        "mRKNS_7OptionsERNS_13StreamProfileE");
+MIO_V1 mio_v1_synthesize_stream_profiled(TestToSpeech *t, const VoiceModel &v, const std::string &text,
+                                         const TestToSpeech::StreamCallback &cb, size_t chunk, const OptionsV1 &o,
+                                         TestToSpeech::StreamProfile &p) {
+    return t->synthesize_stream_profiled(v, text, cb, chunk, widen(o), p);
+}
+
+#undef MIO_V1
+#undef MIO_STR
+#undef MIO_CB

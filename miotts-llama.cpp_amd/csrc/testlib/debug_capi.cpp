@@ -99,6 +99,23 @@ extern "C" int mio_hip_llm_debug_attention(mio_hip_llm *m, int il, int pos, int 
     return mio::llm_debug_attention(m, il, pos, which, qkv, att);
 }
 
+extern "C" int mio_hip_llm_debug_sample_chain(mio_hip_llm *m, const float *logits, const int32_t *history,
+                                              int n_history, const mio_sampling *s, float temperature, uint64_t seed,
+                                              int step, int32_t lo, int32_t hi, int32_t *token, int32_t *kept,
+                                              int32_t *cut_id, float *penalised) {
+    MIO_REQUIRE(m && s, MIO_ERR_INVALID, "llm_debug_sample_chain: null argument");
+    int info[8];
+    if (int rc = mio_hip_llm_info(m, info)) return rc;
+    MIO_REQUIRE(lo >= 0 && lo < info[0] && hi <= info[0], MIO_ERR_INVALID,
+                "llm_debug_sample_chain: window [%d, %d) outside the %d-id vocabulary", lo, hi, info[0]);
+    mio::SamplingParams sp;
+    sp.temperature = temperature, sp.seed = seed, sp.allow_lo = lo, sp.allow_hi = hi < 0 ? 0 : hi;
+    sp.top_k = s->top_k, sp.top_p = s->top_p, sp.min_p = s->min_p, sp.repeat_penalty = s->repeat_penalty;
+    sp.frequency_penalty = s->frequency_penalty, sp.presence_penalty = s->presence_penalty;
+    sp.repeat_last_n = s->repeat_last_n;
+    return mio::llm_debug_sample_chain(m, logits, history, n_history, sp, step, token, kept, cut_id, penalised);
+}
+
 extern "C" int mio_quantize_rows(uint32_t type, const float *x, int rows, int k, void *out) {
     MIO_REQUIRE(x && out && rows > 0 && k > 0, MIO_ERR_INVALID, "quantize_rows: bad args");
     const size_t rb = mio::ggml_row_bytes(type, k);

@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <functional>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -21,7 +22,24 @@ struct CliArgs {
     int max_tokens = 700, n_threads = 4, n_gpu_layers = 0, device = -1;
     size_t chunk_samples = 4096;
     bool skip_llm = false, dump_tensors = false, speech_only = false, ignore_eos = false;
+    // the on-device sampler chain (TestToSpeech::Options; neutral by default)
+    int top_k = 0, repeat_last_n = 64;
+    float top_p = 1.0f, min_p = 0.0f, repeat_penalty = 1.0f, frequency_penalty = 0.0f, presence_penalty = 0.0f;
 };
+
+// The whole of v as a number (std::stof / std::stoi alone accept "0.9x"); throws as they do.
+inline float cli_float(const std::string &v) {
+    size_t n = 0;
+    const float f = std::stof(v, &n);
+    if (n != v.size()) throw std::invalid_argument(v);
+    return f;
+}
+inline int cli_int(const std::string &v) {
+    size_t n = 0;
+    const int i = std::stoi(v, &n);
+    if (n != v.size()) throw std::invalid_argument(v);
+    return i;
+}
 
 struct CliFlag {
     std::vector<std::string> names;
@@ -56,6 +74,20 @@ inline std::vector<CliFlag> cli_common_flags() {
          [](CliArgs &a, const std::string &) { a.speech_only = true; }},
         {{"--ignore-eos"}, false, "Benchmark harness: do not stop at <|endoftext|> / <|im_end|>",
          [](CliArgs &a, const std::string &) { a.ignore_eos = true; }},
+        {{"--top-k"}, true, "Sample among the k most likely ids (default: 0 = off)",
+         [](CliArgs &a, const std::string &v) { a.top_k = cli_int(v); }},
+        {{"--top-p"}, true, "Sample among the most likely ids that reach this probability mass (default: 1 = off)",
+         [](CliArgs &a, const std::string &v) { a.top_p = cli_float(v); }},
+        {{"--min-p"}, true, "Drop ids less likely than this fraction of the most likely one (default: 0 = off)",
+         [](CliArgs &a, const std::string &v) { a.min_p = cli_float(v); }},
+        {{"--repeat-penalty"}, true, "Penalty on the logits of recently sampled ids (default: 1 = off)",
+         [](CliArgs &a, const std::string &v) { a.repeat_penalty = cli_float(v); }},
+        {{"--repeat-last-n"}, true, "Sampled tokens the penalties look back on, 0..256 (default: 64)",
+         [](CliArgs &a, const std::string &v) { a.repeat_last_n = cli_int(v); }},
+        {{"--frequency-penalty"}, true, "Subtracted per recent occurrence of an id (default: 0 = off)",
+         [](CliArgs &a, const std::string &v) { a.frequency_penalty = cli_float(v); }},
+        {{"--presence-penalty"}, true, "Subtracted once from a recently sampled id (default: 0 = off)",
+         [](CliArgs &a, const std::string &v) { a.presence_penalty = cli_float(v); }},
     };
 }
 
@@ -87,7 +119,12 @@ inline bool cli_parse(int argc, char **argv, const std::vector<CliFlag> &flags, 
             return false;
         }
         if (hit->takes_value && ++i >= argc) return false;
-        hit->set(a, hit->takes_value ? std::string(argv[i]) : std::string());
+        try {
+            hit->set(a, hit->takes_value ? std::string(argv[i]) : std::string());
+        } catch (const std::exception &) {  // std::stof / std::stoi: not a number, or out of range
+            std::fprintf(stderr, "Invalid value for %s: %s\n", arg.c_str(), argv[i]);
+            return false;
+        }
     }
     return true;
 }
@@ -101,6 +138,11 @@ inline std::string cli_check(const CliArgs &a, bool path_words = false) {
     if (a.codec_path.empty()) return "--codec" + p + " is required";
     if (a.voice_path.empty()) return "--voice" + p + " is required";
     if (!a.skip_llm && a.model_path.empty()) return "--model" + p + " is required (or use --skip-llm)";
+    // what the runner would refuse (mio_hip_llm_set_sampling), said before any model is loaded
+    for (float v : {a.top_p, a.min_p, a.repeat_penalty, a.frequency_penalty, a.presence_penalty})
+        if (v != v) return "a sampling option is NaN";
+    if (!(a.repeat_penalty > 0.0f)) return "--repeat-penalty must be > 0";
+    if (a.repeat_last_n < 0 || a.repeat_last_n > 256) return "--repeat-last-n must be in 0..256";
     return "";
 }
 
@@ -123,5 +165,8 @@ inline TestToSpeech::Options cli_options(const CliArgs &a) {
     o.skip_llm = a.skip_llm;
     o.speech_only = a.speech_only;
     o.ignore_eos = a.ignore_eos;
+    o.top_k = a.top_k, o.top_p = a.top_p, o.min_p = a.min_p;
+    o.repeat_penalty = a.repeat_penalty, o.repeat_last_n = a.repeat_last_n;
+    o.frequency_penalty = a.frequency_penalty, o.presence_penalty = a.presence_penalty;
     return o;
 }

@@ -36,6 +36,21 @@ class HipError(RuntimeError):
     pass
 
 
+class Sampling(ctypes.Structure):
+    """mio_sampling (include/mio_hip.h): the sampler chain's knobs; the defaults are the neutral
+    values (no chain launch)."""
+    _fields_ = [("top_k", ctypes.c_int32), ("top_p", ctypes.c_float), ("min_p", ctypes.c_float),
+                ("repeat_penalty", ctypes.c_float), ("frequency_penalty", ctypes.c_float),
+                ("presence_penalty", ctypes.c_float), ("repeat_last_n", ctypes.c_int32)]
+
+    def __init__(self, top_k=0, top_p=1.0, min_p=0.0, repeat_penalty=1.0, frequency_penalty=0.0,
+                 presence_penalty=0.0, repeat_last_n=64):
+        super().__init__(top_k, top_p, min_p, repeat_penalty, frequency_penalty, presence_penalty, repeat_last_n)
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class _Libs:
     """The product library and, behind it, the test-support library: an entry point is looked
     up in libmiotts.so first, then in libmiotts_test.so."""
@@ -132,6 +147,11 @@ def _declare(L: ctypes.CDLL) -> None:
         "mio_hip_llm_kv_rows": (c_int, [_vp, c_int, c_int, _vp, _vp]),
         "mio_hip_llm_set_kv_rows": (c_int, [_vp, c_int, c_int, c_int, _vp, _vp]),
         "mio_hip_llm_debug_attention": (c_int, [_vp, c_int, c_int, c_int, _vp, _vp]),
+        "mio_hip_llm_set_sampling": (c_int, [_vp, ctypes.POINTER(Sampling)]),
+        "mio_hip_llm_get_sampling": (c_int, [_vp, ctypes.POINTER(Sampling)]),
+        "mio_hip_llm_debug_sample_chain": (c_int, [_vp, _vp, _vp, c_int, ctypes.POINTER(Sampling), ctypes.c_float,
+                                                   ctypes.c_uint64, c_int, ctypes.c_int32, ctypes.c_int32, _i32p,
+                                                   _i32p, _i32p, _vp]),
         "mio_hip_debug_matvec": (c_int, [_vp, ctypes.c_uint32, _vp, c_int, c_int, _vp, _vp]),
         "mio_quantize_rows": (c_int, [ctypes.c_uint32, _vp, c_int, c_int, _vp]),
         "mio_dequantize_rows": (c_int, [ctypes.c_uint32, _vp, c_int, c_int, _vp]),
@@ -470,7 +490,8 @@ SYNTH_EOT = 259
 # The decode step's launch kinds (enum StepKind, csrc/hip/llm_kernels.h): what step_kinds()
 # returns and time_kernel / trace_kernel take. 7 is the flush sampler (after the last step).
 STEP_KIND_NAMES = {0: "attn_in", 1: "attention", 2: "attn_out", 3: "ffn_in", 4: "ffn_down", 6: "lm_head",
-                   7: "sample", 8: "conv_in", 9: "conv_out", 10: "att_o", 11: "layer_att", 12: "ffn", 13: "layer"}
+                   7: "sample", 8: "conv_in", 9: "conv_out", 10: "att_o", 11: "layer_att", 12: "ffn", 13: "layer",
+                   14: "sample_chain"}
 
 
 def synth_llm(path: str, preset: int = 0, seed: int = 1) -> str:
@@ -600,6 +621,36 @@ class Llm:
         att = np.empty((self.n_head, self.head_dim), np.float32)
         check(lib().mio_hip_llm_debug_attention(self.h, il, pos, which, _ptr(qkv), _ptr(att)))
         return att
+
+    def set_sampling(self, sampling=None, **knobs) -> None:
+        """The sampler chain's knobs for later generate / generate_batch calls
+        (mio_hip_llm_set_sampling): a Sampling, or its fields as keywords (top_k, top_p, min_p,
+        repeat_penalty, frequency_penalty, presence_penalty, repeat_last_n); neither = neutral
+        (passed as NULL). Invalid values raise HipError."""
+        assert sampling is None or not knobs
+        s = Sampling(**knobs) if knobs else sampling
+        check(lib().mio_hip_llm_set_sampling(self.h, ctypes.byref(s) if s is not None else None))
+
+    def get_sampling(self) -> dict:
+        s = Sampling()
+        check(lib().mio_hip_llm_get_sampling(self.h, ctypes.byref(s)))
+        return s.as_dict()
+
+    def debug_sample_chain(self, logits, history, sampling: Sampling, temperature: float, seed: int, step: int,
+                           lo: int, hi: int, penalised: bool = False):
+        """One launch of the sampler chain kernel + the flush sampler on an injected logits row
+        [n_vocab] with `history` as the tokens sampled before `step` (test-support library):
+        (token, kept count, cut id) and, with penalised, the row after the penalties."""
+        logits = np.ascontiguousarray(logits, np.float32).reshape(-1)
+        assert logits.size == self.n_vocab, logits.size
+        history = np.ascontiguousarray(history, np.int32).reshape(-1)
+        tok, kept, cut = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
+        pen = np.empty(self.n_vocab, np.float32) if penalised else None
+        check(lib().mio_hip_llm_debug_sample_chain(self.h, _ptr(logits), _ptr(history) if history.size else None,
+                                                   history.size, ctypes.byref(sampling), temperature, seed, step, lo,
+                                                   hi, ctypes.byref(tok), ctypes.byref(kept), ctypes.byref(cut),
+                                                   _ptr(pen) if penalised else None))
+        return (tok.value, kept.value, cut.value, pen) if penalised else (tok.value, kept.value, cut.value)
 
     def step_kinds(self) -> list:
         """The decode step's launches in order, as time_kernel's `which` (STEP_KIND_NAMES)."""
