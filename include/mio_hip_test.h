@@ -15,10 +15,21 @@ extern "C" {
  * the host quantizer used to build synthetic models (ggml block layout out). */
 int mio_hip_debug_matvec(mio_hip_device *d, uint32_t type, const void *gguf_rows, int rows, int k,
                          const float *x, float *y);
+/* The same with the gate|up launch's row pairs and epilogue: y = silu(Wgate x) * (Wup x). */
+int mio_hip_debug_matvec_swiglu(mio_hip_device *d, uint32_t type, const void *gguf_gate, const void *gguf_up, int rows,
+                                int k, const float *x, float *y);
 int mio_quantize_rows(uint32_t type, const float *x, int rows, int k, void *out);
 /* The host dequantizer (ggml dequantize_row_* expression order) on rows of ggml blocks:
  * out[rows][k] f32. */
 int mio_dequantize_rows(uint32_t type, const void *rows_bytes, int rows, int k, float *out);
+/* The decode step's activation quantizer (one 512-thread workgroup, the kernels' own prologue
+ * code) on x[k]: type 12 -> Q8_K, 8 -> Q8_0, 30 -> bf16 rounding; w != NULL: RMSNorm(x, eps) * w
+ * first; sc1 != 0: the activation loaded the way an in-launch hand-off loads it. Out, the
+ * workgroup's LDS record: qs[2k] bytes (int8 codes in the first k, or k bf16 values), d[k/32 + 8]
+ * (one per superblock / block), bs[k/16 + 8] (Q8_K bsums); entries the kind does not write are
+ * undefined. */
+int mio_hip_debug_act_quant(mio_hip_device *d, uint32_t type, const float *x, const float *w, int k, float eps,
+                            int sc1, int8_t *qs, float *dd, int16_t *bs);
 /* Parity helper: y[t][rows] = W x[t] for nt activation rows x[t][k] on the batched-prefill
  * matmul (int8 MFMA, csrc/hip/llm_mmq.hip); each row equals mio_hip_debug_matvec of x[t].
  * mode 0: y = W x; 1: y = W x + y (y in/out, the residual epilogue); 2: y = silu(W x) *

@@ -211,14 +211,12 @@ __device__ __forceinline__ void o_consumer(const LlmDims &d, const QMat &wo, con
     MIO_TL_MARK1(b);
     plain_quant(xr, K, akind(T), s, MIO_TL_DIAGSLOT(b));
     MIO_TL_MARK(b, 2);
-    stream_rows<T, NP, 1, SU, MIO_SMALL_AUX>(wo, wo, lo, hi, ga, gb, s.a, [&](int row, float v, float) {
-        const float r = lane_value(xres, row - lo);
-        if ((threadIdx.x & 63) == 0) {
-            if constexpr (XS)
-                st1_sc1(b.x, (uint32_t)row * 4u, v + r);
-            else
-                b.x[row] = v + r;
-        }
+    stream_rows_lanes<T, NP, 1, SU, MIO_SMALL_AUX>(wo, wo, lo, hi, ga, gb, s.a, [&](int row, float v, float) {
+        // lane i: row lo + i, its residual value
+        if constexpr (XS)
+            st1_sc1(b.x, (uint32_t)row * 4u, v + xres);
+        else
+            b.x[row] = v + xres;
     });
     if constexpr (XS) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

@@ -68,9 +68,7 @@ __global__ __launch_bounds__(MT) void k_attn_in(LlmDims d, const float *norm_w, 
         }
         return false;
     };
-    auto put = [&](int row, float v) {
-        if ((threadIdx.x & 63) == 0) b.qkv[row] = v;
-    };
+    auto put = [&](int row, float v) { b.qkv[row] = v; };
     Frag ga[Cfg<NP, SU>::U], gb[Cfg<NP, SU>::U];
     int lo, hi;
     if ((int)blockIdx.x < g_qk) {
@@ -84,7 +82,7 @@ __global__ __launch_bounds__(MT) void k_attn_in(LlmDims d, const float *norm_w, 
         rmsnorm_quant(xr, K, d.eps, akind(TQ), s, MIO_TL_DIAGSLOT(b));
         MIO_TRACE(b, 2);
         MIO_TL_MARK(b, 2);
-        stream_rows<TQ, NP, 1, SU, MIO_SMALL_AUX>(wq, wk, lo, hi, ga, gb, s.a, [&](int row, float v, float) {
+        stream_rows_lanes<TQ, NP, 1, SU, MIO_SMALL_AUX>(wq, wk, lo, hi, ga, gb, s.a, [&](int row, float v, float) {
             put(row, v);
         }, o1);
         MIO_TL_END(b);
@@ -97,7 +95,7 @@ __global__ __launch_bounds__(MT) void k_attn_in(LlmDims d, const float *norm_w, 
         x_after_weights(xr);
         if (!FS && done_now(dn)) return;
         rmsnorm_quant(xr, K, d.eps, akind(TV), s, MIO_TL_DIAGSLOT(b));
-        stream_rows<TV, NP, 1, SU, MIO_SMALL_AUX>(wv, wv, lo, hi, ga, gb, s.a, [&](int row, float v, float) {
+        stream_rows_lanes<TV, NP, 1, SU, MIO_SMALL_AUX>(wv, wv, lo, hi, ga, gb, s.a, [&](int row, float v, float) {
             put(o2 + row, v);
         });
         MIO_TL_END(b);

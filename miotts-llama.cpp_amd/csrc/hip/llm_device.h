@@ -273,6 +273,85 @@ __device__ __forceinline__ float abs_max4(const float (&v)[4]) {
     return wave_max_f(fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))), 0.0f);
 }
 
+// Wave-wide maximum of non-negative, non-NaN float bit patterns (they order as unsigned
+// integers): row_shr prefix within rows, then row_bcast, returned wave-uniform. An integer max
+// takes its DPP operand directly (one instruction per step); fmaxf on a DPP result first has to
+// quiet it (a v_mov_dpp, a canonicalizing v_max and the v_max itself).
+__device__ __forceinline__ uint32_t wave_max_u(uint32_t v) {
+    v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, ROW_SHR1, 0xF, 0xF, false));
+    v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, ROW_SHR2, 0xF, 0xF, false));
+    v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, ROW_SHR4, 0xF, 0xF, false));
+    v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, ROW_SHR8, 0xF, 0xF, false));
+    v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, ROW_BCAST15, 0xA, 0xF, false));
+    v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, ROW_BCAST31, 0xC, 0xF, false));
+    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+}
+
+// quantize_row_q8_K_ref semantics for the wave's superblocks b = wave + MW j (j < XV, b < K /
+// 256), each held as 4 values per lane (lane l: elements 4l .. 4l+3 of v[j]): iscale =
+// -127/max_signed with max_signed the first element of largest |x| (the lowest lane holding it,
+// the lowest of its 4 values), codes (int)rintf(iscale x) (nearest-even) clamped to 127, the
+// 16-wide bsums, d = 1/iscale; an all-zero superblock gets zero codes and d = 0. The XV
+// superblocks run as independent chains with no branch between them, so their cross-lane maxima
+// interleave; the two divisions are done ONCE, superblock j's in lane j, and the record's d is
+// stored from there after the codes and bsums.
+// Non-finite inputs: a NaN never counts towards the maximum and its code is 0 (the hardware
+// conversion of NaN); a superblock of NaNs and zeros only is an all-zero superblock. With an
+// infinite maximum iscale is a zero, every code 0 and d an infinity. With a subnormal maximum
+// iscale overflows to an infinity: the codes are the low bytes of the saturated conversions (0
+// for -inf and for the NaN of inf * 0, 127 for +inf), the bsums their sums, d a zero.
+template <int XV>
+__device__ __forceinline__ void q8k_regs(const float4 (&v)[XV], int K, const ActL &a) {
+    const int lane = MIO_TIDX & 63, wave = __builtin_amdgcn_readfirstlane(MIO_TIDX >> 6);
+    const int nsb = K >> 8;
+    float mx[XV];
+#pragma unroll
+    for (int j = 0; j < XV; ++j) {
+        const float vv[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
+        const float m = fmaxf(fmaxf(fabsf(vv[0]), fabsf(vv[1])), fmaxf(fabsf(vv[2]), fabsf(vv[3])));
+        const float am = __uint_as_float(wave_max_u(m == m ? __float_as_uint(m) : 0u));
+        float sel = 0.0f;
+        bool has = false;
+#pragma unroll
+        for (int i = 3; i >= 0; --i)
+            if (fabsf(vv[i]) == am) sel = vv[i], has = true;
+        // no lane holds it only where every value is a NaN: lane 63's sel = 0, all-zero superblock
+        const int src = __builtin_ctzll(__ballot(has) | (1ull << 63));
+        mx[j] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sel), src));
+    }
+    float mxl = mx[0];
+#pragma unroll
+    for (int j = 1; j < XV; ++j) mxl = lane == j ? mx[j] : mxl;
+    const float isl = -127.f / mxl;
+#pragma unroll
+    for (int j = 0; j < XV; ++j) {
+        const int b = wave + MW * j;
+        // an all-zero superblock (max_signed a zero): scale 0, so every code is 0
+        const float is = XV == 1 ? isl : __int_as_float(__builtin_amdgcn_readlane(__float_as_int(isl), j));
+        const float iscale = fabsf(mx[j]) > 0.0f ? is : 0.0f;
+        const float vv[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
+        int q[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int t = (int)rintf(iscale * vv[i]);
+            q[i] = t < 127 ? t : 127;
+        }
+        // the codes' low bytes: {q1, q0} and {q3, q2} byte 0 each, then the two halves
+        const uint32_t p01 = __builtin_amdgcn_perm((uint32_t)q[1], (uint32_t)q[0], 0x0c0c0400u);
+        const uint32_t p23 = __builtin_amdgcn_perm((uint32_t)q[3], (uint32_t)q[2], 0x0c0c0400u);
+        const int packed = (int)__builtin_amdgcn_perm(p23, p01, 0x05040100u);
+        // a code is within +-127 or INT_MIN (a saturated -inf, low 16 bits 0): the sum of the four
+        // signed bytes equals the sum of the codes in the 16 bits that are stored
+        const int sm = quad_sum_i(sdot4(packed, 0x01010101, 0));
+        if (b < nsb) {
+            *reinterpret_cast<int *>(a.qs + b * 256 + 4 * lane) = packed;
+            if ((lane & 3) == 0) a.bs[b * 16 + (lane >> 2)] = (int16_t)sm;
+        }
+    }
+    const float dd = fabsf(mxl) > 0.0f ? 1.0f / isl : 0.0f;
+    if (lane < XV && wave + MW * lane < nsb) a.d[wave + MW * lane] = dd;
+}
+
 // quantize_row_q8_0_ref semantics (d = amax/127 stored as f16, q = roundf(x * 1/d)) of
 // block b held by the 8-lane group of this lane (4 values per lane, lane & 7 = position)
 __device__ __forceinline__ void q80_store(const float (&v)[4], int b, bool ok, const ActL &a) {
@@ -367,14 +446,7 @@ template <int XV>
 __device__ __forceinline__ void quant_regs(const float4 (&v)[XV], int K, int ak, const ActL &a) {
     const int lane = MIO_TIDX & 63, wave = __builtin_amdgcn_readfirstlane(MIO_TIDX >> 6);
     if (ak == 1) {
-        const int nsb = K >> 8;
-#pragma unroll
-        for (int j = 0; j < XV; ++j) {
-            const int b = wave + MW * j;
-            if (b >= nsb) break;
-            const float vv[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
-            q8k_store(vv, abs_max4(vv), b, a);
-        }
+        q8k_regs<XV>(v, K, a);
     } else if (ak == 2) {
 #pragma unroll
         for (int j = 0; j < XV; ++j) {
@@ -396,9 +468,10 @@ __device__ __forceinline__ void quant_regs(const float4 (&v)[XV], int K, int ak,
     lds_barrier();
 }
 
-// ggml: mean = sum / ne00 in double; a power-of-two K divides exactly by a multiply
+// ggml: mean = sum / ne00 in double; a power-of-two K divides exactly by scaling the exponent
+// (one instruction; 1.0 / K was a double division at run time)
 __device__ __forceinline__ float rms_scale(double tot, int K, float eps) {
-    const float mean = (float)((K & (K - 1)) == 0 ? tot * (1.0 / K) : tot / K);
+    const float mean = (float)((K & (K - 1)) == 0 ? __builtin_ldexp(tot, -__builtin_ctz(K)) : tot / K);
     return 1.0f / sqrtf(mean + eps);
 }
 
@@ -939,6 +1012,38 @@ __device__ __forceinline__ void stream_rows(const QMat W0, const QMat W1, int lo
         if (u0 >= n) break;
         load_group<T, NP, NM, SU, AUX>(W0, W1, lo, n, u0 + U, B, split);
     }
+}
+
+// stream_rows with the row epilogue run once per wave instead of once per row: each finished
+// row's dot(s) are parked in lane (row - lo) & 63, and fin(row, dot0, dot1) is called with
+// per-lane values by the lanes that hold a row - after the last unit, and before that whenever
+// 64 rows are parked (only a wave whose share is not one register group, SU == 0, can own more
+// than 64). The epilogue's arithmetic is per lane what it was per row on wave-uniform values
+// (the same instructions, the same bits), and its store is one instruction for all the rows.
+template <int T, int NP, int NM, int SU = 0, int AUX = MIO_WEIGHT_AUX, class Fin>
+__device__ __forceinline__ void stream_rows_lanes(const QMat W0, const QMat W1, int lo, int hi,
+                                                  Frag (&A)[Cfg<NP, SU>::U], Frag (&B)[Cfg<NP, SU>::U], const ActL &a,
+                                                  Fin &&fin, int split = INT_MAX, unsigned long long *trace = nullptr) {
+    const int lane = MIO_TIDX & 63;
+    // a share of one register group holds at most SU / (NM NP) rows: with one row there is
+    // nothing to gather, lane 0 (row lo, its own residual value) runs the epilogue as it comes
+    if constexpr (SU != 0 && SU / (NM * NP) == 1) {
+        stream_rows<T, NP, NM, SU, AUX>(W0, W1, lo, hi, A, B, a, [&](int row, float v0, float v1) {
+            if (lane == 0) fin(row, v0, v1);
+        }, split, trace);
+        return;
+    }
+    float p0 = 0.0f, p1 = 0.0f;
+    stream_rows<T, NP, NM, SU, AUX>(W0, W1, lo, hi, A, B, a, [&](int row, float v0, float v1) {
+        const int k = (row - lo) & 63;
+        p0 = lane == k ? v0 : p0;
+        if constexpr (NM == 2) p1 = lane == k ? v1 : p1;
+        if constexpr (SU == 0) {
+            if (k == 63) fin(row - 63 + lane, p0, p1);
+        }
+    }, split, trace);
+    const int rest = SU == 0 ? (hi - lo) & 63 : hi - lo;
+    if (lane < rest) fin(hi - rest + lane, p0, p1);
 }
 
 // The first group(s) of a wave's stream (before the prologue).

@@ -308,8 +308,14 @@ int pick_su(int units, int np);
 // previous step's sampler).
 void launch_attn_in(const LlmDims &d, const LayerW &L, int il, const QMat &tok_embd, const LlmBuffers &b, bool dg,
                     hipStream_t s);
-// y = W x with x re-quantized to the vec_dot_type (parity test of the matvec kernels).
-void launch_debug_matvec(const QMat &W, const float *x, float *y, int n_wg, hipStream_t s);
+// y = W x with x re-quantized to the vec_dot_type (parity test of the matvec kernels); with
+// up: y = silu(W x) * (up x), the gate|up launch's row pairs and epilogue.
+void launch_debug_matvec(const QMat &W, const QMat *up, const float *x, float *y, int n_wg, hipStream_t s);
+// The decode prologue's activation quantizer for weight type `type` on x[K] (RMSNorm with w when
+// given; sc1: the hand-off load path): the LDS record, debug_act_record_bytes(K) bytes, to out.
+size_t debug_act_record_bytes(int K);
+void launch_debug_act_quant(int type, const float *x, const float *w, int K, float eps, bool sc1, void *out,
+                            hipStream_t s);
 // y[t][rows] = W x[t] for nt tokens on the int8-MFMA multi-token matmul (act: scratch of
 // nt * debug_act_bytes(W.k) bytes); mode 0 store, 1 y += W x, 2 y = silu(W x) * (up x).
 size_t debug_act_bytes(int K);

@@ -69,9 +69,8 @@ __global__ __launch_bounds__(MT) void k_attn_out(LlmDims d, QMat wo, LlmBuffers 
     plain_quant(xr, K, akind(T), s, MIO_TL_DIAGSLOT(b));
     MIO_TRACE(b, 2);
     MIO_TL_MARK(b, 2);
-    stream_rows<T, NP, 1, SU, MIO_SMALL_AUX>(wo, wo, lo, hi, ga, gb, s.a, [&](int row, float v, float) {
-        const float r = lane_value(xres, row - lo);
-        if ((threadIdx.x & 63) == 0) b.x[row] = v + r;
+    stream_rows_lanes<T, NP, 1, SU, MIO_SMALL_AUX>(wo, wo, lo, hi, ga, gb, s.a, [&](int row, float v, float) {
+        b.x[row] = v + xres;  // lane i: row lo + i, its residual value
     });
     MIO_TL_END(b);
     MIO_TRACE(b, 15);
@@ -110,9 +109,8 @@ __global__ __launch_bounds__(MT) void k_conv_out(LlmDims d, QMat wo, const float
                MIO_TL_DIAGSLOT(b));
     MIO_TRACE(b, 2);
     MIO_TL_MARK(b, 2);
-    stream_rows<T, NP, 1, SU>(wo, wo, lo, hi, ga, gb, s.a, [&](int row, float v, float) {
-        const float r = lane_value(xres, row - lo);
-        if ((threadIdx.x & 63) == 0) b.x[row] = v + r;
+    stream_rows_lanes<T, NP, 1, SU>(wo, wo, lo, hi, ga, gb, s.a, [&](int row, float v, float) {
+        b.x[row] = v + xres;  // lane i: row lo + i, its residual value
     });
     MIO_TL_END(b);
     MIO_TRACE(b, 15);
@@ -175,8 +173,8 @@ __global__ __launch_bounds__(MT) void k_ffn_in(LlmDims d, const float *norm_w, Q
     rmsnorm_quant(xr, K, d.eps, akind(T), s, MIO_TL_DIAGSLOT(b));
     MIO_TRACE(b, 2);
     MIO_TL_MARK(b, 2);
-    stream_rows<T, NP, 2, SU>(gate, up, lo, hi, ga, gb, s.a, [&](int row, float g, float u) {
-        if ((threadIdx.x & 63) == 0) b.h[row] = silu_f(g) * u;
+    stream_rows_lanes<T, NP, 2, SU>(gate, up, lo, hi, ga, gb, s.a, [&](int row, float g, float u) {
+        b.h[row] = silu_f(g) * u;
     }, INT_MAX, DG ? b.trace : nullptr);
     if (adv && blockIdx.x == 0 && MIO_TIDX == 0) advance_state(b.st, d);
     MIO_TL_END(b);
@@ -207,9 +205,8 @@ __global__ __launch_bounds__(MT) void k_ffn_down(LlmDims d, QMat down, LlmBuffer
     plain_quant(xr, K, akind(T), s, MIO_TL_DIAGSLOT(b));
     MIO_TRACE(b, 2);
     MIO_TL_MARK(b, 2);
-    stream_rows<T, NP, 1, SU>(down, down, lo, hi, ga, gb, s.a, [&](int row, float v, float) {
-        const float r = lane_value(xres, row - lo);
-        if ((threadIdx.x & 63) == 0) b.x[row] = v + r;
+    stream_rows_lanes<T, NP, 1, SU>(down, down, lo, hi, ga, gb, s.a, [&](int row, float v, float) {
+        b.x[row] = v + xres;  // lane i: row lo + i, its residual value
     }, INT_MAX, DG ? b.trace : nullptr);
     MIO_TL_END(b);
     MIO_TRACE(b, 15);
@@ -266,8 +263,8 @@ __global__ __launch_bounds__(MT) void k_ffn(LlmDims d, const float *norm_w, QMat
         MIO_TL_MARK1(b);
         rmsnorm_quant(xr, K, d.eps, akind(T), s, MIO_TL_DIAGSLOT(b));
         MIO_TL_MARK(b, 2);
-        stream_rows<T, NP, 2, SU>(gate, up, lo, hi, ga, gb, s.a, [&](int row, float g, float u) {
-            if ((threadIdx.x & 63) == 0) st1_sc1(b.h, (uint32_t)row * 4u, silu_f(g) * u);
+        stream_rows_lanes<T, NP, 2, SU>(gate, up, lo, hi, ga, gb, s.a, [&](int row, float g, float u) {
+            st1_sc1(b.h, (uint32_t)row * 4u, silu_f(g) * u);
         });
         if (adv && blockIdx.x == 0 && MIO_TIDX == 0) advance_state(b.st, d);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -306,9 +303,8 @@ __global__ __launch_bounds__(MT) void k_ffn(LlmDims d, const float *norm_w, QMat
         MIO_TL_MARK1(b);
         plain_quant(xr, K, akind(TD), s, MIO_TL_DIAGSLOT(b));
         MIO_TL_MARK(b, 2);
-        stream_rows<TD, NPD, 1, SUD>(down, down, lo, hi, ga, gb, s.a, [&](int row, float v, float) {
-            const float r = lane_value(xres, row - lo);
-            if ((threadIdx.x & 63) == 0) b.x[row] = v + r;
+        stream_rows_lanes<TD, NPD, 1, SUD>(down, down, lo, hi, ga, gb, s.a, [&](int row, float v, float) {
+            b.x[row] = v + xres;  // lane i: row lo + i, its residual value
         });
     }
     MIO_TL_END(b);

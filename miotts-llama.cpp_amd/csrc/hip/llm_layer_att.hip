@@ -36,9 +36,7 @@ __device__ __forceinline__ void qkv_producer(const LlmDims &d, const float *norm
     XRegs<NP> xr;
     load_x(b.x, norm_w, K, xr);
     x_gate();
-    auto put = [&](int row, float v) {
-        if ((threadIdx.x & 63) == 0) st1_sc1(b.qkv, (uint32_t)row * 4, v);
-    };
+    auto put = [&](int row, float v) { st1_sc1(b.qkv, (uint32_t)row * 4, v); };
     Frag ga[Cfg<NP, SU>::U], gb[Cfg<NP, SU>::U];
     int lo, hi, ra, rb;
     const int bid = blockIdx.x;
@@ -51,7 +49,7 @@ __device__ __forceinline__ void qkv_producer(const LlmDims &d, const float *norm
         MIO_TL_MARK1(b);
         rmsnorm_quant(xr, K, d.eps, akind(TQ), s, MIO_TL_DIAGSLOT(b));
         MIO_TL_MARK(b, 2);
-        stream_rows<TQ, NP, 1, SU, MIO_SMALL_AUX>(wq, wk, lo, hi, ga, gb, s.a, [&](int row, float v, float) {
+        stream_rows_lanes<TQ, NP, 1, SU, MIO_SMALL_AUX>(wq, wk, lo, hi, ga, gb, s.a, [&](int row, float v, float) {
             put(row, v);
         }, o1);
     } else {
@@ -64,7 +62,7 @@ __device__ __forceinline__ void qkv_producer(const LlmDims &d, const float *norm
         MIO_TL_MARK1(b);
         rmsnorm_quant(xr, K, d.eps, akind(TV), s, MIO_TL_DIAGSLOT(b));
         MIO_TL_MARK(b, 2);
-        stream_rows<TV, NP, 1, SU, MIO_SMALL_AUX>(wv, wv, lo, hi, ga, gb, s.a, [&](int row, float v, float) {
+        stream_rows_lanes<TV, NP, 1, SU, MIO_SMALL_AUX>(wv, wv, lo, hi, ga, gb, s.a, [&](int row, float v, float) {
             put(o2 + row, v);
         });
     }
@@ -175,8 +173,8 @@ __device__ __forceinline__ void gate_up_role(const LlmDims &d, const float *norm
     MIO_TL_MARK1(b);
     rmsnorm_quant(xr, K, d.eps, akind(T), s, MIO_TL_DIAGSLOT(b));
     MIO_TL_MARK(b, 2);
-    stream_rows<T, NP, 2, SU>(gate, up, lo, hi, ga, gb, s.a, [&](int row, float g, float u) {
-        if ((threadIdx.x & 63) == 0) st1_sc1(b.h, (uint32_t)row * 4u, silu_f(g) * u);
+    stream_rows_lanes<T, NP, 2, SU>(gate, up, lo, hi, ga, gb, s.a, [&](int row, float g, float u) {
+        st1_sc1(b.h, (uint32_t)row * 4u, silu_f(g) * u);
     });
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -211,9 +209,8 @@ __device__ __forceinline__ void down_role(const LlmDims &d, const QMat &down, co
     MIO_TL_MARK1(b);
     plain_quant(xr, K, akind(T), s, MIO_TL_DIAGSLOT(b));
     MIO_TL_MARK(b, 2);
-    stream_rows<T, NP, 1, SU>(down, down, lo, hi, ga, gb, s.a, [&](int row, float v, float) {
-        const float rr = lane_value(xres, row - lo);
-        if ((threadIdx.x & 63) == 0) b.x[row] = v + rr;
+    stream_rows_lanes<T, NP, 1, SU>(down, down, lo, hi, ga, gb, s.a, [&](int row, float v, float) {
+        b.x[row] = v + xres;  // lane i: row lo + i, its residual value
     });
 }
 

@@ -1,6 +1,7 @@
 // Test-support C-ABI (libmiotts_test.so, include/mio_hip_test.h): parity entry points of the
 // matvec / batched-matmul kernels on raw GGUF rows, and the host quantizer the synthetic
 // models are built with. Not part of the product library.
+#include <cstring>
 #include <vector>
 
 #include "common.h"
@@ -10,11 +11,13 @@
 #include "mio_hip_test.h"
 #include "quant.h"
 
-extern "C" int mio_hip_debug_matvec(mio_hip_device *d, uint32_t type, const void *gguf_rows, int rows, int k,
-                                    const float *x, float *y) {
+namespace {
+// y = W x, or with gguf_up y = silu(W x) * (up x), on the decode step's streaming matvec engine
+int debug_matvec(mio_hip_device *d, uint32_t type, const void *gguf_rows, const void *gguf_up, int rows, int k,
+                 const float *x, float *y) {
     MIO_REQUIRE(d && gguf_rows && x && y && rows > 0 && k > 0, MIO_ERR_INVALID, "debug_matvec: bad args");
     MIO_REQUIRE(type == mio::GGML_Q8_0 || type == mio::GGML_Q4_K || type == mio::GGML_Q5_K ||
-                    type == mio::GGML_Q6_K || type == mio::GGML_BF16 || mio::repacks_to_q8_0(type),
+                    type == mio::GGML_Q6_K || type == mio::GGML_BF16 || (!gguf_up && mio::repacks_to_q8_0(type)),
                 MIO_ERR_UNSUPPORTED, "debug_matvec: type %u", type);
     const bool k32 = type == mio::GGML_Q8_0 || type == mio::GGML_BF16 || mio::repacks_to_q8_0(type);
     MIO_REQUIRE(k % (k32 ? 32 : 256) == 0, MIO_ERR_INVALID, "debug_matvec: k %d", k);
@@ -29,21 +32,69 @@ extern "C" int mio_hip_debug_matvec(mio_hip_device *d, uint32_t type, const void
         type = mio::GGML_Q8_0;
     }
     const mio::SplitLayout L = mio::split_layout(type, rows, k);
-    std::vector<uint8_t> host(L.bytes);
+    const int nm = gguf_up ? 2 : 1;
+    std::vector<uint8_t> host(L.bytes * nm);
     mio::to_split(type, gguf_rows, rows, k, host.data());
+    if (gguf_up) mio::to_split(type, gguf_up, rows, k, host.data() + L.bytes);
     uint8_t *dw = nullptr;
     float *dx = nullptr, *dy = nullptr;
-    MIO_HIP_CHECK(hipMalloc(&dw, L.bytes));
+    MIO_HIP_CHECK(hipMalloc(&dw, L.bytes * nm));
     MIO_HIP_CHECK(hipMalloc(&dx, (size_t)k * 4));
     MIO_HIP_CHECK(hipMalloc(&dy, (size_t)rows * 4));
-    hipMemcpy(dw, host.data(), L.bytes, hipMemcpyHostToDevice);
+    hipMemcpy(dw, host.data(), L.bytes * nm, hipMemcpyHostToDevice);
     hipMemcpy(dx, x, (size_t)k * 4, hipMemcpyHostToDevice);
-    mio::QMat q{(int)type, rows, k, dw + L.off[0], dw + L.off[1], dw + L.off[2], dw + L.off[3]};
-    mio::launch_debug_matvec(q, dx, dy, d->n_cu > 0 ? d->n_cu : 256, d->stream);
+    auto qm = [&](uint8_t *base) {
+        return mio::QMat{(int)type, rows, k, base + L.off[0], base + L.off[1], base + L.off[2], base + L.off[3]};
+    };
+    const mio::QMat q = qm(dw), up = qm(dw + (gguf_up ? L.bytes : 0));
+    mio::launch_debug_matvec(q, gguf_up ? &up : nullptr, dx, dy, d->n_cu > 0 ? d->n_cu : 256, d->stream);
     hipError_t e = hipStreamSynchronize(d->stream);
     if (e == hipSuccess) e = hipMemcpy(y, dy, (size_t)rows * 4, hipMemcpyDeviceToHost);
     hipFree(dw), hipFree(dx), hipFree(dy);
     MIO_HIP_CHECK(e);
+    return MIO_OK;
+}
+}  // namespace
+
+extern "C" int mio_hip_debug_matvec(mio_hip_device *d, uint32_t type, const void *gguf_rows, int rows, int k,
+                                    const float *x, float *y) {
+    return debug_matvec(d, type, gguf_rows, nullptr, rows, k, x, y);
+}
+
+extern "C" int mio_hip_debug_matvec_swiglu(mio_hip_device *d, uint32_t type, const void *gguf_gate,
+                                           const void *gguf_up, int rows, int k, const float *x, float *y) {
+    MIO_REQUIRE(gguf_up, MIO_ERR_INVALID, "debug_matvec_swiglu: bad args");
+    return debug_matvec(d, type, gguf_gate, gguf_up, rows, k, x, y);
+}
+
+extern "C" int mio_hip_debug_act_quant(mio_hip_device *d, uint32_t type, const float *x, const float *w, int k,
+                                       float eps, int sc1, int8_t *qs, float *dd, int16_t *bs) {
+    MIO_REQUIRE(d && x && qs && dd && bs && k > 0, MIO_ERR_INVALID, "debug_act_quant: bad args");
+    MIO_REQUIRE(type == mio::GGML_Q8_0 || type == mio::GGML_Q4_K || type == mio::GGML_BF16, MIO_ERR_UNSUPPORTED,
+                "debug_act_quant: type %u", type);
+    MIO_REQUIRE(k % (type == mio::GGML_Q4_K ? 256 : 32) == 0 && k <= 12288, MIO_ERR_INVALID,
+                "debug_act_quant: k %d", k);
+    int rc = mio::bind(d);
+    if (rc) return rc;
+    const size_t nb = mio::debug_act_record_bytes(k);
+    float *dx = nullptr, *dw = nullptr;
+    char *dr = nullptr;
+    MIO_HIP_CHECK(hipMalloc(&dx, (size_t)k * 4));
+    MIO_HIP_CHECK(hipMalloc(&dw, (size_t)k * 4));
+    MIO_HIP_CHECK(hipMalloc(&dr, nb));
+    hipMemcpy(dx, x, (size_t)k * 4, hipMemcpyHostToDevice);
+    if (w) hipMemcpy(dw, w, (size_t)k * 4, hipMemcpyHostToDevice);
+    mio::launch_debug_act_quant((int)type, dx, w ? dw : nullptr, k, eps, sc1 != 0, dr, d->stream);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
+    std::vector<char> rec(nb);
+    if (e == hipSuccess) e = hipMemcpy(rec.data(), dr, nb, hipMemcpyDeviceToHost);
+    hipFree(dx), hipFree(dw), hipFree(dr);
+    MIO_HIP_CHECK(e);
+    // the record's layout (llm_device.h carve): qs [2k] | d f32[k/32 + 8] | bs i16[k/16 + 8]
+    memcpy(qs, rec.data(), (size_t)k * 2);
+    memcpy(dd, rec.data() + (size_t)k * 2, (size_t)(k / 32 + 8) * 4);
+    memcpy(bs, rec.data() + (size_t)k * 2 + (size_t)(k / 32 + 8) * 4, (size_t)(k / 16 + 8) * 2);
     return MIO_OK;
 }
 

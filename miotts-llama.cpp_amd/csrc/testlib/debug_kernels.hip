@@ -1,14 +1,17 @@
 // Test-support kernel (libmiotts_test.so): y = W x with x re-quantized to the vec_dot_type
 // in the decode prologue's way, on the decode step's streaming matvec engine (llm_device.h),
-// for mio_hip_debug_matvec's parity tests of every weight type.
+// for mio_hip_debug_matvec's parity tests of every weight type, and the decode prologue's
+// activation quantizer on its own (mio_hip_debug_act_quant).
 #include "llm_device.h"
 
 #pragma clang fp contract(off)
 
 namespace mio {
 namespace {
-template <int NP, int T>
-__global__ __launch_bounds__(MT) void k_debug_matvec(QMat W, const float *x, float *y) {
+// NM == 2: U is the up matrix beside the gate W, y = silu(W x) * (U x) (the gate|up launch's
+// stream of row pairs and its SwiGLU epilogue)
+template <int NP, int T, int NM>
+__global__ __launch_bounds__(MT) void k_debug_matvec(QMat W, QMat U, const float *x, float *y) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int K = W.k;
     const Smem s = carve(smem, K);
@@ -17,20 +20,56 @@ __global__ __launch_bounds__(MT) void k_debug_matvec(QMat W, const float *x, flo
     int lo, hi;
     wave_range(W.rows, lo, hi, blockIdx.x, gridDim.x);
     Frag ga[Cfg<NP>::U], gb[Cfg<NP>::U];
-    load_first<T, NP, 1>(W, W, lo, hi, ga, gb);
+    load_first<T, NP, NM>(W, U, lo, hi, ga, gb);
     plain_quant(xr, K, akind(T), s);
-    stream_rows<T, NP, 1>(W, W, lo, hi, ga, gb, s.a, [&](int row, float v, float) {
-        if ((threadIdx.x & 63) == 0) y[row] = v;
+    stream_rows_lanes<T, NP, NM>(W, U, lo, hi, ga, gb, s.a, [&](int row, float v, float u) {
+        y[row] = NM == 2 ? silu_f(v) * u : v;
     });
+}
+
+// One workgroup runs the decode prologue's quantizer (rmsnorm_quant when w is given, else
+// plain_quant; SC1: the sc1 activation loads of the in-launch hand-offs) on x[K] and copies the
+// LDS record {qs | d | bs} (smem_bytes(K) - 128 bytes, the unwritten parts undefined) to out.
+template <int NP, int T, int XAUX>
+__global__ __launch_bounds__(MT) void k_debug_act_quant(const float *x, const float *w, int K, float eps,
+                                                        uint32_t *out) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const Smem s = carve(smem, K);
+    XRegs<NP> xr;
+    load_x<NP, XAUX>(x, w, K, xr);
+    if (w)
+        rmsnorm_quant(xr, K, eps, akind(T), s);
+    else
+        plain_quant(xr, K, akind(T), s);
+    const int n = (int)((smem_bytes(K) - 128) / 4);
+    for (int i = MIO_TIDX; i < n; i += MT) out[i] = reinterpret_cast<const uint32_t *>(smem)[i];
 }
 }  // namespace
 
-void launch_debug_matvec(const QMat &W, const float *x, float *y, int n_wg, hipStream_t s) {
+size_t debug_act_record_bytes(int K) { return smem_bytes(K) - 128; }
+
+void launch_debug_act_quant(int type, const float *x, const float *w, int K, float eps, bool sc1, void *out,
+                            hipStream_t s) {
+    dispatch_nt(K, type, [&]<int NP, int T>() {
+        if (sc1)
+            hipLaunchKernelGGL((k_debug_act_quant<NP, T, 16>), dim3(1), dim3(MT), matvec_lds(K), s, x, w, K, eps,
+                               (uint32_t *)out);
+        else
+            hipLaunchKernelGGL((k_debug_act_quant<NP, T, 0>), dim3(1), dim3(MT), matvec_lds(K), s, x, w, K, eps,
+                               (uint32_t *)out);
+    });
+}
+
+void launch_debug_matvec(const QMat &W, const QMat *up, const float *x, float *y, int n_wg, hipStream_t s) {
     LlmDims d{};
     d.n_wg = n_wg;
     dispatch_nt(W.k, W.type, [&]<int NP, int T>() {
-        hipLaunchKernelGGL((k_debug_matvec<NP, T>), dim3(matvec_grid(d, W.rows)), dim3(MT), matvec_lds(W.k), s, W, x,
-                           y);
+        if (up)
+            hipLaunchKernelGGL((k_debug_matvec<NP, T, 2>), dim3(matvec_grid(d, W.rows)), dim3(MT), matvec_lds(W.k), s,
+                               W, *up, x, y);
+        else
+            hipLaunchKernelGGL((k_debug_matvec<NP, T, 1>), dim3(matvec_grid(d, W.rows)), dim3(MT), matvec_lds(W.k), s,
+                               W, W, x, y);
     });
 }
 

@@ -153,6 +153,9 @@ def _declare(L: ctypes.CDLL) -> None:
                                                    ctypes.c_uint64, c_int, ctypes.c_int32, ctypes.c_int32, _i32p,
                                                    _i32p, _i32p, _vp]),
         "mio_hip_debug_matvec": (c_int, [_vp, ctypes.c_uint32, _vp, c_int, c_int, _vp, _vp]),
+        "mio_hip_debug_matvec_swiglu": (c_int, [_vp, ctypes.c_uint32, _vp, _vp, c_int, c_int, _vp, _vp]),
+        "mio_hip_debug_act_quant": (c_int, [_vp, ctypes.c_uint32, _vp, _vp, c_int, ctypes.c_float, c_int, _vp, _vp,
+                                            _vp]),
         "mio_quantize_rows": (c_int, [ctypes.c_uint32, _vp, c_int, c_int, _vp]),
         "mio_dequantize_rows": (c_int, [ctypes.c_uint32, _vp, c_int, c_int, _vp]),
         "mio_hip_debug_mmq": (c_int, [_vp, ctypes.c_uint32, _vp, c_int, c_int, _vp, c_int, c_int, _vp, _vp]),
@@ -728,6 +731,30 @@ def debug_matvec(dev: Device, qtype: int, w_rows: np.ndarray, k: int, x: np.ndar
     y = np.empty(w_rows.shape[0], np.float32)
     check(lib().mio_hip_debug_matvec(dev.h, qtype, _ptr(w_rows), w_rows.shape[0], k, _ptr(x), _ptr(y)))
     return y
+
+
+def debug_matvec_swiglu(dev: Device, qtype: int, gate_rows: np.ndarray, up_rows: np.ndarray, k: int,
+                        x: np.ndarray) -> np.ndarray:
+    """silu(gate x) * (up x) on the decode step's gate|up stream (mio_hip_debug_matvec_swiglu)."""
+    gate_rows, up_rows = np.ascontiguousarray(gate_rows), np.ascontiguousarray(up_rows)
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    y = np.empty(gate_rows.shape[0], np.float32)
+    check(lib().mio_hip_debug_matvec_swiglu(dev.h, qtype, _ptr(gate_rows), _ptr(up_rows), gate_rows.shape[0], k,
+                                            _ptr(x), _ptr(y)))
+    return y
+
+
+def debug_act_quant(dev: Device, qtype: int, x: np.ndarray, w: Optional[np.ndarray] = None, eps: float = 1e-6,
+                    sc1: bool = False):
+    """The decode prologue's activation quantizer on x[k] (mio_hip_debug_act_quant): returns the
+    LDS record (qs int8[2k], d float32[k/32 + 8], bs int16[k/16 + 8])."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    k = x.shape[0]
+    wv = np.ascontiguousarray(w, dtype=np.float32) if w is not None else None
+    qs, d, bs = np.empty(2 * k, np.int8), np.empty(k // 32 + 8, np.float32), np.empty(k // 16 + 8, np.int16)
+    check(lib().mio_hip_debug_act_quant(dev.h, qtype, _ptr(x), _ptr(wv) if wv is not None else None, k, eps,
+                                        int(sc1), _ptr(qs), _ptr(d), _ptr(bs)))
+    return qs, d, bs
 
 
 def debug_mmq(dev: Device, qtype: int, w_rows: np.ndarray, k: int, x: np.ndarray, mode: int = 0,
