@@ -26,20 +26,15 @@ template <int HD, int G, bool DG, bool WQ = false>
 __device__ __forceinline__ bool attention_wg(const LlmDims &d, const float *q_norm, const float *k_norm,
                                              const float *bqkv, _Float16 *kc, _Float16 *vc, const LlmBuffers &b,
                                              int ch, int kvh, int pos, int *rdy) {
-    static_assert(!WQ || MIO_ATT_MFMA, "the q|k|v wait is on the MFMA attention path");
     constexpr bool kDiag = DG;
     using C = AttCfg<HD>;
     constexpr int PER = HD / 64;
     __shared__ float qs[G][HD];
     __shared__ float knew[HD], vnew[HD];
-#if MIO_ATT_MFMA
     using A = AttM<HD>;
     static_assert(C::NT == A::NT, "attention workgroup size");
     __shared__ __attribute__((aligned(16))) char img[2 * A::IMG];
     __shared__ __attribute__((aligned(16))) _Float16 qh[G][HD];
-#else
-    __shared__ float wres[C::NW][G][HD + 2];
-#endif
 
     const int t0 = ch * ATT_CHUNK;
     if (t0 > pos || b.st->done) return false;
@@ -57,7 +52,6 @@ __device__ __forceinline__ bool attention_wg(const LlmDims &d, const float *q_no
                                    isk ? b.qkv + vo : nullptr, isk && bqkv ? bqkv + vo : nullptr);
     };
     HeadIn<HD> hin;
-#if MIO_ATT_MFMA
     h8 kr[A::VI], vr[A::VI];
     if constexpr (WQ) {
         kv_issue<HD>(kc + (size_t)kvh * d.n_ctx * HD, vc + (size_t)kvh * d.n_ctx * HD, t0, pos, kr, vr);
@@ -72,11 +66,6 @@ __device__ __forceinline__ bool attention_wg(const LlmDims &d, const float *q_no
         if (wave < G + (owner ? 1 : 0)) head_src(wave, hin);
         kv_issue<HD>(kc + (size_t)kvh * d.n_ctx * HD, vc + (size_t)kvh * d.n_ctx * HD, t0, pos, kr, vr);
     }
-#else
-    if (wave < G + (owner ? 1 : 0)) head_src(wave, hin);
-    h8 kr[C::IT], vr[C::IT];
-    load_kv_rows<HD>(kc + (size_t)kvh * d.n_ctx * HD, vc + (size_t)kvh * d.n_ctx * HD, t0, pos, kr, vr);
-#endif
     MIO_TRACE(b, 1);
     MIO_TL_MARK1(b);
     for (int hh = wave; hh < G + (owner ? 1 : 0); hh += C::NW) {
@@ -94,19 +83,13 @@ __device__ __forceinline__ bool attention_wg(const LlmDims &d, const float *q_no
                 kd[p] = (_Float16)knew[p];
                 vd[p] = (_Float16)vr16;
             }
-#if MIO_ATT_MFMA
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
             kv_stage_row<HD>(knew, vnew, pos - t0, img, img + A::IMG);
-#endif
-        }
-#if MIO_ATT_MFMA
-        else {
+        } else {
             q_to_f16<HD>(qs[hh], qh[hh]);
         }
-#endif
     }
-#if MIO_ATT_MFMA
     MIO_TRACE(b, 6);  // this wave's head prepared
     if constexpr (!WQ) kv_stage<HD>(kr, vr, owner ? pos - t0 : -1, img, img + A::IMG);
     MIO_TRACE(b, 7);  // this thread's K / V rows arrived and staged
@@ -116,26 +99,6 @@ __device__ __forceinline__ bool attention_wg(const LlmDims &d, const float *q_no
     const uint32_t gs = (uint32_t)(d.max_splits * C::REC), head0 = (uint32_t)(kvh * G) * gs;
     attend_chunk_mfma<HD, G>(qh, img, img + A::IMG, t0, pos, d.scale, b.part + head0 + (uint32_t)ch * C::REC, gs,
                              DG ? b.trace : nullptr);
-#else
-    lds_barrier();
-    MIO_TRACE(b, 2);
-    MIO_TL_MARK(b, 2);
-    // the slot owning row `pos` takes it from LDS (exact f16 values, the cache row's bits)
-    if (owner) {
-        const int sl = threadIdx.x / C::LP, lp = lane % C::LP, r = pos - t0;
-        if (sl == r % C::NS) {
-            h8 kn, vn;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) kn[i] = (_Float16)knew[lp * 8 + i], vn[i] = (_Float16)vnew[lp * 8 + i];
-#pragma unroll
-            for (int it = 0; it < C::IT; ++it)
-                if (it == r / C::NS) kr[it] = kn, vr[it] = vn;
-        }
-    }
-    const uint32_t gs = (uint32_t)(d.max_splits * C::REC), head0 = (uint32_t)(kvh * G) * gs;
-    attend_chunk<HD, G>(qs, kr, vr, t0, pos, d.scale, wres, b.part + head0 + (uint32_t)ch * C::REC, gs,
-                        DG ? b.trace : nullptr, MIO_TL_DIAGSLOT(b));
-#endif
     attn_merge_last<HD, G>(b.part, head0, gs, pos / ATT_CHUNK + 1, b.att_cnt + kvh, b.att + (size_t)kvh * G * HD, -1,
                            {}, 0, rdy, (kDiag && b.tl) ? MIO_TL_SLOT(b) : nullptr);
     return true;
@@ -155,42 +118,7 @@ __device__ __forceinline__ bool attention_wg(const LlmDims &d, const float *q_no
 // order: every producer has a lower workgroup index than every consumer and never waits, so
 // it is dispatched (and finishes) whatever the residency. The counter is zeroed by the next
 // launch, k_ffn_in (kernel boundary ordered), and by reset_tickets.
-// Two-level arrival counter of an in-launch hand-off with n signalling workgroups (r = the
-// signaller's index among them; first wave, after every wave's stores drained and a workgroup
-// barrier): one add to arrival shard r % 8 (<= n / 8 adds per word); the workgroup whose add
-// returns its shard's last count adds 1 to each of the 8 ready replicas (one instruction, 8
-// lanes), where a consumer polls replica r' % 8 until min(n, 8) (MI355X_MICROARCH hand-off
-// rows 1-2; k_ffn's h counter).
-__device__ __forceinline__ void signal_two_level(int *arr, int *rdy, int r, int n) {
-    if (MIO_TIDX < 64) {
-        int last = 0;
-        if (MIO_TIDX == 0) {
-            const int sh = r & (kFfnShards - 1), n_sh = (n - sh + kFfnShards - 1) / kFfnShards;
-            last = __hip_atomic_fetch_add((__attribute__((address_space(1))) int *)(arr + kFfnStride * sh), 1,
-                                          __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == n_sh - 1;
-        }
-        if (__builtin_amdgcn_readfirstlane(last) && MIO_TIDX < kFfnShards)
-            __hip_atomic_fetch_add((__attribute__((address_space(1))) int *)(rdy + kFfnStride * MIO_TIDX), 1,
-                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-__device__ __forceinline__ void wait_two_level(int *rdy, int r, int n, int *flag) {
-    if (MIO_TIDX == 0) wait_count(rdy + kFfnStride * (r & (kFfnShards - 1)), min(n, kFfnShards), flag);
-    asm volatile("s_barrier" ::: "memory");
-}
-
-// residual rows [lo, hi) of this wave, lane i holding x[lo + i], by sc1 loads (x was stored
-// write-through by other workgroups of the launch); lanes past hi read 0 (out of range)
-__device__ __forceinline__ float load_resid_sc1(const float *x, int lo, int hi) {
-    const int lane = threadIdx.x & 63;
-    return __uint_as_float(
-        __builtin_amdgcn_raw_buffer_load_b32(rsrc(x, (uint32_t)hi * 4u), (uint32_t)(lo + lane) * 4u, 0, 16));
-}
-
-// XS (the whole-layer launch, k_layer): the x rows are stored write-through and, once every
-// wave's stores drained, the workgroup signals the two-level x counter (kXOff / kXRdy of
-// b.att_cnt) for the launch's gate|up workgroups
-template <int NP, int T, int SU, bool DG, bool XS = false>
+template <int NP, int T, int SU, bool DG>
 __device__ __forceinline__ void o_consumer(const LlmDims &d, const QMat &wo, const LlmBuffers &b, int ob, int no) {
     constexpr bool kDiag = DG;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -212,18 +140,8 @@ __device__ __forceinline__ void o_consumer(const LlmDims &d, const QMat &wo, con
     plain_quant(xr, K, akind(T), s, MIO_TL_DIAGSLOT(b));
     MIO_TL_MARK(b, 2);
     stream_rows_lanes<T, NP, 1, SU, MIO_SMALL_AUX>(wo, wo, lo, hi, ga, gb, s.a, [&](int row, float v, float) {
-        // lane i: row lo + i, its residual value
-        if constexpr (XS)
-            st1_sc1(b.x, (uint32_t)row * 4u, v + xres);
-        else
-            b.x[row] = v + xres;
+        b.x[row] = v + xres;  // lane i: row lo + i, its residual value
     });
-    if constexpr (XS) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        MIO_TL_MARK(b, 6);  // x rows written through
-        signal_two_level(b.att_cnt + kXOff, b.att_cnt + kXRdy, ob, no);
-    }
 }
 
 }  // namespace

@@ -43,7 +43,6 @@ __global__ __launch_bounds__(MT) void k_attn_in(LlmDims d, const float *norm_w, 
     if constexpr (!FS) dn = done_issue(b);
     XRegs<NP> xr;
     load_x(pend ? nullptr : b.x, norm_w, K, xr);
-    x_gate();
     // returns true when the sampled token ends generation (the rest of the step is skipped)
     auto sample_prologue = [&]() -> bool {
         if constexpr (FS) {

@@ -372,23 +372,6 @@ __device__ __forceinline__ void q80_store(const float (&v)[4], int b, bool ok, c
     }
 }
 
-// MIO_X_FIRST=1: a matvec launch waits for its activation loads before issuing any weight
-// load (the activation is the critical path; queued behind the chip's first weight burst it
-// arrives late). Memory clobber: no load moves across it.
-#ifndef MIO_X_FIRST
-#define MIO_X_FIRST 0
-#endif
-// MIO_X_FIRST=2: every wave issues its activation loads before any wave issues weights (a
-// bare s_barrier, no waitcnt): the CU's memory queue then holds all activation requests
-// ahead of the weight burst, so no wave's activation waits behind other waves' weights.
-__device__ __forceinline__ void x_gate() {
-#if MIO_X_FIRST == 1
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#elif MIO_X_FIRST == 2
-    asm volatile("s_barrier" ::: "memory");
-#endif
-}
-
 // ------------------------------------------------------------------ prologue registers
 // x (and the norm weight) as float4 per thread, loaded before any weight load.
 template <int XV>
@@ -1139,17 +1122,6 @@ inline void attn_in_grid(const LlmDims &d, const LayerW &L, int &G, int &g_qk) {
 
 
 // ------------------------------------------------------------------ attention helpers
-// all-reduce over aligned groups of LP (8 or 16) lanes, by DPP; every lane of a group gets
-// the bitwise-same sum
-template <int LP>
-__device__ __forceinline__ float group_sum(float v) {
-    v += dpp_f<0xB1>(v);   // quad_perm [1,0,3,2]
-    v += dpp_f<0x4E>(v);   // quad_perm [2,3,0,1]
-    v += dpp_f<0x141>(v);  // row_half_mirror
-    if constexpr (LP == 16) v += dpp_f<0x140>(v);  // row_mirror
-    return v;
-}
-
 __device__ inline float silu_f(float x) { return x / (1.0f + expf(-x)); }
 
 __device__ inline uint64_t mix64(uint64_t x) {
@@ -1284,9 +1256,9 @@ void dispatch_v(int tv, F &&f) {
 // prefill (k_pf_attention), so all three produce bit-identical partial records and outputs.
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 
-// One workgroup per (ATT_CHUNK positions, kv head [, token]): a position slot is LP lanes
-// holding 8 dims each; NT = ATT_CHUNK * LP threads (at most MIO_ATT_NT), IT positions per
-// slot, and the K/V rows of a chunk arrive in one load round trip per lane.
+// One workgroup per (ATT_CHUNK positions, kv head [, token]): NT = ATT_CHUNK * LP threads (LP
+// = a row's 16-byte pieces; at most MIO_ATT_NT), and the K/V rows of a chunk arrive in one
+// load round trip per lane.
 // MIO_ATT_NT: threads per attention chunk workgroup at most. 256 (4 positions per slot at
 // 64-position chunks): 0.763-0.766 vs 0.775 ms per token with 512 (profiles/r04_att_nt_ab.txt);
 // 128 would need the merge to cover more than one float4 of outputs per thread at G * hd = 1024
@@ -1295,11 +1267,9 @@ typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 #endif
 template <int HD>
 struct AttCfg {
-    static constexpr int LP = HD / 8;                                        // lanes per slot
+    static constexpr int LP = HD / 8;                                        // 8-dim pieces per row
     static constexpr int NT = ATT_CHUNK * LP < MIO_ATT_NT ? ATT_CHUNK * LP : MIO_ATT_NT;  // threads
     static constexpr int NW = NT / 64;                                       // waves
-    static constexpr int NS = NT / LP;                                       // position slots
-    static constexpr int IT = ATT_CHUNK / NS;                                // positions per slot
     static constexpr int REC = part_rec(HD);
 };
 
@@ -1507,153 +1477,8 @@ __device__ void prep_head(const float *src, const float *bias, const float *nw, 
     head_prep<HD>(in, d, row);
 }
 
-// K/V rows of this thread's slot (positions t0 + sl + NS*it, clamped to pos), issued early.
-template <int HD>
-__device__ __forceinline__ void load_kv_rows(const _Float16 *kbase, const _Float16 *vbase, int t0, int pos,
-                                             h8 (&kr)[AttCfg<HD>::IT], h8 (&vr)[AttCfg<HD>::IT]) {
-    constexpr int LP = AttCfg<HD>::LP, NS = AttCfg<HD>::NS;
-    const int lp = (MIO_TIDX & 63) % LP, sl = MIO_TIDX / LP;
-#pragma unroll
-    for (int it = 0; it < AttCfg<HD>::IT; ++it) {
-        const int t = min(t0 + sl + NS * it, pos);
-        kr[it] = *reinterpret_cast<const h8 *>(kbase + (size_t)t * HD + lp * 8);
-        vr[it] = *reinterpret_cast<const h8 *>(vbase + (size_t)t * HD + lp * 8);
-    }
-}
-
-// Softmax attention of the G query heads qs (LDS, prepared) over the chunk's positions
-// [t0, min(t0 + ATT_CHUNK, pos + 1)) whose K/V rows are in kr/vr, in two passes like ggml's
-// soft_max (scores, chunk max, exp, sums; summation order aside): every slot's scores are
-// independent dot products, the max is exchanged once (lanes by butterflies, waves by LDS),
-// and the slots' sums then merge by plain adds (no online rescaling). Writes the chunk's
-// partial record {O[HD] = sum_t p_t v_t, m = chunk max, l = sum_t p_t} of head g to
-// dst + g * g_stride (p_t = exp(s_t - m)).
-template <int HD, int G>
-__device__ void attend_chunk(const float (*qs)[HD], const h8 (&kr)[AttCfg<HD>::IT], const h8 (&vr)[AttCfg<HD>::IT],
-                             int t0, int pos, float scale, float (*wres)[G][HD + 2], float *dst, size_t g_stride,
-                             unsigned long long *trace = nullptr, unsigned long long *diag = nullptr) {
-    constexpr int LP = AttCfg<HD>::LP, NS = AttCfg<HD>::NS, IT = AttCfg<HD>::IT, NT = AttCfg<HD>::NT,
-                  NW = AttCfg<HD>::NW;
-    __shared__ float wmax[NW][G];
-    const int tid = MIO_TIDX, lane = tid & 63, wave = tid >> 6;
-    const int lp = lane % LP, sl = tid / LP;
-    auto mark = [&](int k) {  // checkpoints of mio_hip_llm_trace_kernel (diagnostic)
-        if (trace && blockIdx.x == 0 && blockIdx.y == 0 && MIO_TIDX == 0) {
-            asm volatile("" ::: "memory");
-            trace[k] = __builtin_readcyclecounter();
-        }
-    };
-    float qv[G][8];
-#pragma unroll
-    for (int g = 0; g < G; ++g)
-#pragma unroll
-        for (int i = 0; i < 8; ++i) qv[g][i] = qs[g][lp * 8 + i];
-    // pass 1: scores (valid positions <= pos) and this thread's running max per head
-    float sc[IT][G], mx[G];
-#pragma unroll
-    for (int g = 0; g < G; ++g) mx[g] = -INFINITY;
-#pragma unroll
-    for (int it = 0; it < IT; ++it) {
-        const bool valid = t0 + sl + NS * it <= pos;
-        float kf[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) kf[i] = (float)kr[it][i];
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-            float sdot = 0.0f;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) sdot = fmaf(qv[g][i], kf[i], sdot);
-            sdot = group_sum<LP>(sdot);
-            sc[it][g] = valid ? sdot * scale : -INFINITY;
-            mx[g] = fmaxf(mx[g], sc[it][g]);
-        }
-    }
-    // chunk max: slots of the wave (butterflies), then the waves (LDS)
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-        if constexpr (LP <= 8) mx[g] = fmaxf(mx[g], xor_lane<8>(mx[g]));
-        mx[g] = fmaxf(mx[g], xor_lane<16>(mx[g]));
-        mx[g] = fmaxf(mx[g], xor_lane<32>(mx[g]));
-    }
-    if (lane == 0)
-#pragma unroll
-        for (int g = 0; g < G; ++g) wmax[wave][g] = mx[g];
-    lds_barrier();
-    float M[G];
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-        M[g] = wmax[0][g];
-#pragma unroll
-        for (int w = 1; w < NW; ++w) M[g] = fmaxf(M[g], wmax[w][g]);
-    }
-    mark(3);
-    MIO_DIAG_STAMP(diag, 3, M[0]);  // scores and chunk max done
-    // pass 2: p = exp(s - M), sums of p and of p * v (the chunk holds position t0 <= pos,
-    // so M is finite)
-    float l[G], acc[G][8];
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-        l[g] = 0.0f;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) acc[g][i] = 0.0f;
-    }
-#pragma unroll
-    for (int it = 0; it < IT; ++it) {
-        float vf[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) vf[i] = (float)vr[it][i];
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-            const float p = sc[it][g] == -INFINITY ? 0.0f : expf(sc[it][g] - M[g]);
-            l[g] += p;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) acc[g][i] = fmaf(p, vf[i], acc[g][i]);
-        }
-    }
-    // slots of the wave: plain sums (every lane of a butterfly pair ends bitwise equal)
-    auto sum_step = [&](auto xl) {
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-            l[g] += xl(l[g]);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) acc[g][i] += xl(acc[g][i]);
-        }
-    };
-    if constexpr (LP <= 8) sum_step([](float v) { return xor_lane<8>(v); });
-    sum_step([](float v) { return xor_lane<16>(v); });
-    sum_step([](float v) { return xor_lane<32>(v); });
-    mark(4);
-    MIO_DIAG_STAMP(diag, 4, acc[0][0]);  // wave sums done
-    if (lane < LP) {
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) wres[wave][g][lp * 8 + i] = acc[g][i];
-            if (lp == 0) wres[wave][g][HD] = l[g];
-        }
-    }
-    lds_barrier();
-    mark(5);
-    MIO_DIAG_STAMP(diag, 5, 0);  // wave results in LDS
-    // the waves -> this chunk's partial record per q head, stored write-through (sc1) for
-    // the workgroup of this launch that merges the chunks (attn_merge_last)
-    for (int e = tid; e < G * HD; e += NT) {
-        const int g = e / HD, dd = e - g * HD;
-        float O = 0.0f, L = 0.0f;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) {
-            O += wres[w][g][dd];
-            L += wres[w][g][HD];
-        }
-        const uint32_t o = (uint32_t)(g * g_stride) * 4u;
-        st1_sc1(dst, o + 4u * dd, O);
-        if (dd == 0) st1_sc1(dst, o + 4u * HD, M[g]), st1_sc1(dst, o + 4u * (HD + 1), L);
-    }
-}
-
 // ------------------------------------------------------------------ attention chunk on the matrix cores
-// MIO_ATT_MFMA (default 1; 0 = the VALU attend_chunk above, for A/B builds): the chunk's
-// Q.K^T and P.V on v_mfma_f32_16x16x32_f16, shared by the decode step, the batched decode and
+// The chunk's Q.K^T and P.V on v_mfma_f32_16x16x32_f16, shared by the decode step, the batched decode and
 // the prefill, so their outputs stay equal bit for bit.
 //  * K and V rows are staged once per workgroup into two LDS images (one 16-B chunk per lane
 //    and load; a chunk's physical slot is XOR-swizzled per row, AttM::fk / fv, so the
@@ -1669,16 +1494,9 @@ __device__ void attend_chunk(const float (*qs)[HD], const h8 (&kr)[AttCfg<HD>::I
 //    h: cdna_hip_programming.md §3 "An accumulator tile as the next MFMA's operand");
 //  * wave w owns output dims [HD / 4 * w, HD / 4 * (w + 1)): DTW tiles of 16.
 // Numerics: q and the cache rows are f16-exact, so every product is exact and only the f32
-// summation order differs from the VALU sweep (scores by 32-dim MFMA k-steps, p.v by 32
-// positions); records {O[hd] = sum p v, m, l = sum p} as attend_chunk's.
-#ifndef MIO_ATT_MFMA
-#define MIO_ATT_MFMA 1
-#endif
-// MIO_ATT_FASTEXP (default 1): p by the hardware exp (v_exp_f32 of x log2 e) instead of expf
-// (0 for A/B: 0.764 vs 0.754-0.758 ms per 1.7B token, profiles/r05_att_ab.txt)
-#ifndef MIO_ATT_FASTEXP
-#define MIO_ATT_FASTEXP 1
-#endif
+// summation order differs from a VALU sweep's (scores by 32-dim MFMA k-steps, p.v by 32
+// positions). The chunk's partial record of head g, at dst + g * g_stride: {O[hd] = sum_t p_t
+// v_t, m = chunk max, l = sum_t p_t} with p_t = exp(s_t - m).
 typedef _Float16 h4v __attribute__((ext_vector_type(4)));
 typedef short s4v __attribute__((ext_vector_type(4)));
 typedef float f4v __attribute__((ext_vector_type(4)));
@@ -1856,12 +1674,9 @@ __device__ __forceinline__ void attend_chunk_mfma(const _Float16 (*qh)[HD], cons
     for (int tau = 0; tau < A::PT; ++tau)
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-#if MIO_ATT_FASTEXP
-            // exp(x) = 2^(x log2 e) on v_exp_f32 (relative error ~ |x| 2^-24 + 1 ulp)
+            // exp(x) = 2^(x log2 e) on v_exp_f32 (relative error ~ |x| 2^-24 + 1 ulp); libm expf
+            // measured 0.764 vs 0.754-0.758 ms per 1.7B token (profiles/r05_att_ab.txt)
             const float p = __builtin_amdgcn_exp2f((s[tau][e] - M) * 1.44269504088896341f);
-#else
-            const float p = expf(s[tau][e] - M);
-#endif
             L += p;
             const _Float16 hi = (_Float16)p;
             ph[tau >> 1][(tau & 1) * 4 + e] = hi;
@@ -1907,10 +1722,10 @@ __device__ __forceinline__ void q_to_f16(const float *src, _Float16 *dst) {
     for (int e = lane; e < HD; e += 64) dst[e] = (_Float16)src[e];
 }
 
-// After attend_chunk: the chunk workgroups of one (kv head [, token]) take arrival tickets;
+// After attend_chunk_mfma: the chunk workgroups of one (kv head [, token]) take arrival tickets;
 // the last of the nch arrivals merges every chunk's records (merge_out4) into the G heads'
 // outputs out[G][HD] (plain stores: read by the next launch). Hand-off (MI355X_MICROARCH
-// "Valid forms", first row): every record byte was stored sc1 (attend_chunk), each wave
+// "Valid forms", first row): every record byte was stored sc1 (attend_chunk_mfma), each wave
 // drains its stores (vmcnt(0)) before the workgroup barrier, then ONE lane adds to the
 // unsharded ticket with an agent-scope atomic; the workgroup whose add returned nch - 1 loads
 // the records only after that add returned (its other waves after the barrier that follows),

@@ -15,7 +15,7 @@ namespace mio {
 #define MIO_ATT_CHUNK 64
 #endif
 constexpr int kAttChunk = MIO_ATT_CHUNK;
-// step timeline (diagnostic): workgroup slots per launch (k_layer grids reach ~1,300)
+// step timeline (diagnostic): workgroup slots per launch (larger grids wrap)
 constexpr int kTlSlots = 2048;
 static_assert(kAttChunk == 32 || kAttChunk == 64 || kAttChunk == 128, "attention chunk");
 
@@ -212,7 +212,7 @@ enum StepKind : int {
     kAttO = 10,       // k_att_o: 1 + 2
     kLayerAtt = 11,   // k_layer_att: 0 + 1 + 2
     kFfn = 12,        // k_ffn: 3 + 4
-    kLayer = 13,      // k_layer: 11 + 12
+                      // 13 is unused (it was the whole layer as one launch, removed)
     kSampleChain = 14,  // k_sample_chain: penalties + top-k / top-p / min-p + draw (after 6, chain on only)
     kStepKindEnd = 15,
 };
@@ -238,8 +238,6 @@ struct ChainArgs {
     int keep;
 };
 void launch_sample_chain(const ChainArgs &a, int B, hipStream_t s);
-// an empty one-workgroup launch (the timing reference of mio_hip_llm_time_kernel)
-void launch_nop(hipStream_t s);
 // Launch kernel `which` of a decode step (of layer il where it is a layer's) on stream s.
 void launch_step_kernel(StepKind which, const StepCtx &c, int il, const LlmBuffers &b, hipStream_t s);
 // Embedding of `token` (row of token_embd) -> b.x, and state reset to (pos, token).
@@ -264,14 +262,6 @@ bool layer_att_supported(const LlmDims &d, const LayerW &L);
 bool ffn_fused_supported(const LlmDims &d, const LayerW &L);
 void launch_layer_att(const LlmDims &d, const LayerW &L, _Float16 *kc, _Float16 *vc, const LlmBuffers &b, bool dg,
                       hipStream_t s);
-// the whole decoder layer L (attention block + FFN pair) as one launch (k_layer, which = 13)
-// exists for its shapes and weight types; launch_layer runs it for layer il (counter set il & 1)
-bool layer_fused_supported(const LlmDims &d, const LayerW &L);
-void launch_layer(const LlmDims &d, const LayerW &L, int il, _Float16 *kc, _Float16 *vc, const LlmBuffers &b,
-                  bool dg, hipStream_t s);
-// MIO_LAYER_GATE (k_layer): 1 = the FFN workgroups issue their weights only once their kv head's
-// q|k|v rows are in (the producers' stream goes first), 0 = at dispatch
-int layer_ffn_gate();
 // k_att_o's merge counters in LlmBuffers.att_cnt: kRdyShards words kRdyStride ints (256 B)
 // apart from int kRdyOff on (one per XCD: an O workgroup polls shard blockIdx % 8, so no word
 // has more than 1/8 of the pollers; MI355X_MICROARCH "dequeue": one word saturates near 88
@@ -288,16 +278,7 @@ constexpr int kQkvOff = kRdyFlag + 64, kQkvStride = 64, kQkvMax = 64;
 // per word). Zeroed by the launch after k_ffn (the next layer's attn_in / layer_att, lm_head).
 constexpr int kFfnOff = kQkvOff + kQkvStride * kQkvMax, kFfnShards = 8, kFfnStride = 64;
 constexpr int kFfnRdy = kFfnOff + kFfnShards * kFfnStride;
-// The whole-layer launch (k_layer, which = 13) hands the O projection's x rows to its gate|up
-// workgroups through one more two-level counter (arrival shards kXOff, ready replicas kXRdy),
-// laid out after the counters above. k_layer runs with LlmBuffers.att_cnt pointing at counter
-// SET il & 1 (kLaySet ints each, from kLayOff on; every offset above is the same inside a set):
-// each k_layer zeroes the other set at entry (used by the previous k_layer: kernel boundary), so
-// no counter of a set is reset while a launch may still poll it; lm_head zeroes both.
-constexpr int kXOff = kFfnRdy + kFfnShards * kFfnStride, kXRdy = kXOff + kFfnShards * kFfnStride;
-constexpr int kLaySet = kXRdy + kFfnShards * kFfnStride;
-constexpr int kLayOff = kLaySet;  // the plain counters occupy [0, kLaySet) too
-constexpr int kAttCntInts = kLayOff + 2 * kLaySet;
+constexpr int kAttCntInts = kFfnRdy + kFfnShards * kFfnStride;
 int pick_np(int K);
 size_t matvec_lds(int K);
 // units (row passes) of the busiest wave of a matvec over `rows` rows on `grid` workgroups,

@@ -59,7 +59,6 @@ __global__ __launch_bounds__(MT) void k_attn_out(LlmDims d, QMat wo, LlmBuffers 
     XRegs<NP> xr;
     load_x(b.att, nullptr, K, xr);
     const float xres = load_resid(b.x, lo, hi);
-    x_gate();
     Frag ga[Cfg<NP, SU>::U], gb[Cfg<NP, SU>::U];
     load_first<T, NP, 1, SU, MIO_SMALL_AUX>(wo, wo, lo, hi, ga, gb);
     x_after_weights(xr);
@@ -98,7 +97,6 @@ __global__ __launch_bounds__(MT) void k_conv_out(LlmDims d, QMat wo, const float
     int lo, hi;
     wave_range(d, wo.rows, lo, hi);
     const float xres = load_resid(b.x, lo, hi);
-    x_gate();
     Frag ga[Cfg<NP, SU>::U], gb[Cfg<NP, SU>::U];
     load_first<T, NP, 1, SU>(wo, wo, lo, hi, ga, gb);
     conv_after_weights(cr);
@@ -124,20 +122,6 @@ __device__ __forceinline__ void advance_state(StepState *st, const LlmDims &d) {
     st->pending = 0;
 }
 
-// Both k_layer counter sets (every counter but the timeout flag; the chunk tickets reset
-// themselves): lm_head, after the step's last k_layer (kernel boundary ordered).
-__device__ __forceinline__ void zero_layer_sets(int *cnt) {
-    constexpr int n = kRdyShards + kQkvMax + 4 * kFfnShards;
-    for (int i = MIO_TIDX; i < 2 * n; i += MT) {
-        const int j = i % n;
-        const int o = j < kRdyShards ? kRdyOff + kRdyStride * j
-                    : j < kRdyShards + kQkvMax ? kQkvOff + kQkvStride * (j - kRdyShards)
-                                               : kFfnOff + kFfnStride * (j - kRdyShards - kQkvMax);
-        __hip_atomic_store((__attribute__((address_space(1))) int *)(cnt + kLayOff + (i / n) * kLaySet + o), 0,
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-
 template <int NP, int T, int SU, bool DG>
 __global__ __launch_bounds__(MT) void k_ffn_in(LlmDims d, const float *norm_w, QMat gate, QMat up,
                                                LlmBuffers b, int adv) {
@@ -150,7 +134,6 @@ __global__ __launch_bounds__(MT) void k_ffn_in(LlmDims d, const float *norm_w, Q
     const uint32_t dn = done_issue(b);
     XRegs<NP> xr;
     load_x(b.x, norm_w, K, xr);
-    x_gate();
     // k_att_o / k_layer_att's merge and q|k|v counters: zero again for the next layer's
     // launch (kernel boundary)
     if (blockIdx.x == 0 && MIO_TIDX < kRdyShards)
@@ -195,7 +178,6 @@ __global__ __launch_bounds__(MT) void k_ffn_down(LlmDims d, QMat down, LlmBuffer
     int lo, hi;
     wave_range(d, down.rows, lo, hi);
     const float xres = load_resid(b.x, lo, hi);
-    x_gate();
     Frag ga[Cfg<NP, SU>::U], gb[Cfg<NP, SU>::U];
     load_first<T, NP, 1, SU>(down, down, lo, hi, ga, gb);
     x_after_weights(xr);
@@ -244,7 +226,6 @@ __global__ __launch_bounds__(MT) void k_ffn(LlmDims d, const float *norm_w, QMat
         const Smem s = carve(smem, K);
         XRegs<NP> xr;
         load_x(b.x, norm_w, K, xr);
-        x_gate();
         if (blockIdx.x == 0 && MIO_TIDX < kRdyShards)
             __hip_atomic_store((__attribute__((address_space(1))) int *)(b.att_cnt + kRdyOff + kRdyStride * MIO_TIDX),
                                0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -368,11 +349,9 @@ __global__ __launch_bounds__(MT) void k_lm_head(LlmDims d, const float *norm_w, 
     if (blockIdx.x == 2 && MIO_TIDX < 2 * kFfnShards)  // the previous k_ffn's h counters (kernel boundary ordered)
         __hip_atomic_store((__attribute__((address_space(1))) int *)(b.att_cnt + kFfnOff + kFfnStride * MIO_TIDX), 0,
                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (blockIdx.x == 3) zero_layer_sets(b.att_cnt);  // the k_layer counter sets (the last layer's is in use)
     const Smem s = carve(smem, K);
     XRegs<NP> xr;
     load_x(b.x, norm_w, K, xr);
-    x_gate();
     int lo, hi;
     wave_range(d, lm.rows, lo, hi);
     Frag ga[Cfg<NP>::U], gb[Cfg<NP>::U];
@@ -577,28 +556,11 @@ int lm_head_blocks(const LlmDims &d) { const LlmDims l = lm_dims(d); return matv
 
 size_t matvec_lds(int K) { return smem_bytes(K); }
 
-
-// An empty one-workgroup launch: the reference of mio_hip_llm_time_kernel's launch timing (what
-// a launch costs the stream besides its own work)
-__global__ void k_nop() {}
-void launch_nop(hipStream_t s) { hipLaunchKernelGGL(k_nop, dim3(1), dim3(64), 0, s); }
-
 void launch_embed_token(const LlmDims &d, const QMat &tok_embd, const LlmBuffers &b, hipStream_t s) {
     hipLaunchKernelGGL(k_embed, dim3(1), dim3(ST), 0, s, d, tok_embd, b);
 }
 
 inline size_t mv_lds(int K) { return smem_bytes(K); }
-// lm_head dynamic LDS, optionally padded (MIO_LM_LDS_KB, A/B knob) so that no more than
-// 160 KB / size of its workgroups fit on one CU: the dispatcher then has to spread them
-size_t lm_lds(int K) {
-    static const size_t kb = [] {
-        const char *e = getenv("MIO_LM_LDS_KB");
-        return e ? (size_t)atoi(e) : (size_t)0;
-    }();
-    const size_t b = smem_bytes(K);
-    return kb * 1024 > b ? std::min(kb * 1024, (size_t)64 * 1024) : b;
-}
-
 // Units (row passes) of the busiest wave of a matvec over `rows` rows on `grid` workgroups
 // (wave_range), and the single-group size that covers them (0 = streaming groups).
 int max_wave_units(int rows, int grid, int np, int nm) {
@@ -688,9 +650,6 @@ void launch_step_kernel(StepKind which, const StepCtx &c, int il, const LlmBuffe
         case kFfn:  // the FFN pair in one launch (k_ffn)
             launch_ffn<DG>(d, layers[il], b, il == 0 ? 1 : 0, s, false);
             break;
-        case kLayer:  // the whole layer in one launch (k_layer, layers >= 1)
-            launch_layer(d, layers[il], il, kcache + il * layer_kv, vcache + il * layer_kv, b, DG, s);
-            break;
         case kConvIn: {  // lfm2 conv_in: RMSNorm + in_proj as the attn_in launch (B | C rows, X rows)
             const LayerW &L = layers[il];
             const int n = d.n_embd;
@@ -717,7 +676,7 @@ void launch_step_kernel(StepKind which, const StepCtx &c, int il, const LlmBuffe
         case kLmHead: {
             const LlmDims dl = lm_dims(d);
             dispatch_nt(d.n_embd, lm.type, [&]<int NP, int T>() {
-                hipLaunchKernelGGL((k_lm_head<NP, T, DG>), dim3(lm_head_blocks(d)), dim3(MT), lm_lds(d.n_embd), s, dl,
+                hipLaunchKernelGGL((k_lm_head<NP, T, DG>), dim3(lm_head_blocks(d)), dim3(MT), smem_bytes(d.n_embd), s, dl,
                                    out_norm, lm, b);
             });
             break;

@@ -981,11 +981,6 @@ __device__ __forceinline__ void mmq_quant_producer(const MmqArgs &a, const MmqQu
                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// MIO_MMQ_XPRE (A/B builds; default 1): k_mmq16's residual epilogue adds values loaded at the
-// tile's start instead of loading them behind the reduction
-#ifndef MIO_MMQ_XPRE
-#define MIO_MMQ_XPRE 1
-#endif
 // MIO_LOOP_D (A/B builds; default 4): tiles whose weights a tile-walking workgroup
 // (k_mmq16_loop, k_mmq16_loop_kq) holds: D - 1 in flight while one is reduced (2 = the
 // ping-pong of rounds 4-5; 4 holds every tile of the 1.7B / 2.6B gate|up walks, <= 4 per
@@ -997,11 +992,6 @@ __device__ __forceinline__ void mmq_quant_producer(const MmqArgs &a, const MmqQu
 // workgroup; 4 Q8_0 W | U sets exceed 256 VGPRs)
 #ifndef MIO_LOOP_DQ8
 #define MIO_LOOP_DQ8 3
-#endif
-// MIO_MMQ_ACT1 (A/B builds; default 1): the K-quant tiles issue their weights, then their
-// activation codes, then the scales' staging (one activation round trip instead of two)
-#ifndef MIO_MMQ_ACT1
-#define MIO_MMQ_ACT1 1
 #endif
 // QNP > 0 (k_mmq16q): the first a.nt workgroups are quantization producers (MmqQuant, XRegs
 // of QNP passes, QM = its mode), the tiles follow and wait before their activation reads.
@@ -1045,7 +1035,7 @@ __global__ __launch_bounds__(MMQ_NT) void k_mmq16(MmqSeg s0, MmqSeg s1, MmqSeg s
         // (the launch before this one wrote them; read at the end they were a dependent
         // round trip behind the reduction)
         float xres[4] = {0.f, 0.f, 0.f, 0.f};
-        if constexpr (MODE == MMQ_RESID && MIO_MMQ_XPRE) {
+        if constexpr (MODE == MMQ_RESID) {
             if (wave == 0 && row0 + (lane & 15) < sg.w.rows) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
@@ -1090,10 +1080,10 @@ __global__ __launch_bounds__(MMQ_NT) void k_mmq16(MmqSeg s0, MmqSeg s1, MmqSeg s
             slot16_store(y, red);
             if constexpr (NV == 2) slot16_store(u, red + MMQ_NT * 4);
         } else {
-            if constexpr (NV == 1 && (T == 12 || T == 13 || T == 14) && (QF || MIO_MMQ_ACT1)) {
+            if constexpr (NV == 1 && (T == 12 || T == 13 || T == 14)) {
                 // up to three passes' weights (K <= 6144, the 1.7B down) are in flight before
                 // the activations are read (with in-launch quantization: while the producers
-                // quantize); then slot16_kq's arithmetic. MIO_MMQ_ACT1: the activation codes of
+                // quantize); then slot16_kq's arithmetic. The activation codes of
                 // every pass are issued before the scales' staging, so codes and scales arrive
                 // in one round trip (and the launches without producers, the O, take this path
                 // too)
@@ -1108,29 +1098,20 @@ __global__ __launch_bounds__(MMQ_NT) void k_mmq16(MmqSeg s0, MmqSeg s1, MmqSeg s
                     for (int p = 0; p < NPX; ++p)
                         if (p < np) kqp_load<T>(sg.w, row, min(p * 8 + k, nsb - 1), ps[p]);
                     wait_act();
-#if MIO_MMQ_ACT1
                     const auto aq = act16_codes<QF>(a, t0);
                     v4i xs[NPX][4];
 #pragma unroll
                     for (int p = 0; p < NPX; ++p)
                         if (p < np) kq_act_ld(aq, min(p * 8 + k, nsb - 1), xs[p]);
                     stage_act16<T, QF>(a, t0, a.K, da);
-#else
-                    const auto aq = stage_act16<T, QF>(a, t0, a.K, da);
-#endif
                     v4f acc = {};
 #pragma unroll
                     for (int p = 0; p < NPX; ++p) {
                         if (p < np) {
                             const int s = p * 8 + k;
-#if MIO_MMQ_ACT1
                             v4i(&x)[4] = xs[p];
 #pragma unroll
                             for (int c = 0; c < 4; ++c) swap_halves(x[c]);
-#else
-                            v4i x[4];
-                            kq_act(aq, min(s, nsb - 1), x);
-#endif
                             v4f v = {};
                             if (s < nsb) v = kqp_val<T>(ps[p], x, s, da);
                             acc = acc + v;  // the decode lane's pass accumulation (0 + v0 + v1 ...)
@@ -1165,7 +1146,7 @@ __global__ __launch_bounds__(MMQ_NT) void k_mmq16(MmqSeg s0, MmqSeg s1, MmqSeg s
             if (t >= a.nt) continue;
             float *o = a.out + (size_t)t * a.ld + sg.out_off + orow;
             if constexpr (MODE == MMQ_STORE) *o = y[i];
-            else if constexpr (MODE == MMQ_RESID) *o = y[i] + (MIO_MMQ_XPRE ? xres[i] : *o);
+            else if constexpr (MODE == MMQ_RESID) *o = y[i] + xres[i];
             else *o = silu_f(y[i]) * u[i];
         }
     };
@@ -1288,11 +1269,7 @@ __global__ __launch_bounds__(MMQ_NT) void k_mmq16_loop(MmqSeg s0, MmqArgs a, Mmq
 // one is reduced. Per tile the arithmetic is k_mmq16's slot16_kq (the 0 + v pass sum,
 // slot16_sum, the same epilogue): bit-identical. QNP > 0: the first a.nt workgroups are the
 // in-launch quantization producers (as k_mmq16_loop).
-// IQ (QNP 0, RMSNorm rows, nt <= 8, K <= 2048): no producer workgroups; every walking
-// workgroup RMSNorm-quantizes the nt token rows itself, one wave per token (xpre_issue before
-// its weight loads, xpre_quant into LDS records: k_bt_quant's bits), and reads the records from
-// LDS; workgroup 0 zeroes the other counter set as a producer would.
-template <int T, int MODE, int QNP, int QM, bool IQ = false>
+template <int T, int MODE, int QNP, int QM>
 __global__ __launch_bounds__(MMQ_NT) void k_mmq16_loop_kq(MmqSeg s0, MmqArgs a, MmqQuant q, int n_tiles) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     constexpr int NV = MODE == MMQ_SWIGLU ? 2 : 1;
@@ -1314,15 +1291,6 @@ __global__ __launch_bounds__(MMQ_NT) void k_mmq16_loop_kq(MmqSeg s0, MmqArgs a, 
     const bool live = k < (a.K >> 8);  // wave-uniform: this wave's superblock exists
     const int sb = live ? k : 0;
     auto row_of = [&](int ti) { return min(ti * RT16 + (lane & 15), s0.w.rows - 1); };
-    static_assert(!IQ || (QNP == 0 && NV == 2), "in-prologue quantization: the gate|up walk");
-    char *rec = reinterpret_cast<char *>(da + (a.K >> 8) * TT16);  // IQ: the nt records
-    XPre xp;
-    if constexpr (IQ) {
-        if (blockIdx.x == 0 && threadIdx.x < 8)
-            __hip_atomic_store((__attribute__((address_space(1))) int *)(q.other + 64 * threadIdx.x), 0,
-                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        xpre_issue(q.src, q.norm_w, a.K, a.nt, xp);
-    }
     // ring of D tiles' weights: D - 1 tiles in flight while one is reduced
     constexpr int D = MIO_LOOP_D;
     KqPass<T> w[D], u[D];
@@ -1338,22 +1306,12 @@ __global__ __launch_bounds__(MMQ_NT) void k_mmq16_loop_kq(MmqSeg s0, MmqArgs a, 
         if (threadIdx.x == 0) wait_count(q.cnt + 64 * (blockIdx.x & 7), a.nt, q.flag);
         asm volatile("s_barrier" ::: "memory");
     }
-    MmqArgs al = a;
-    if constexpr (IQ) {
-        xpre_quant(xp, a.K, q.eps, true, rec, a.nt);
-        al.act = rec, al.act_stride = act_bytes(a.K);
-    }
     v4i x[4];
-#if MIO_MMQ_ACT1
     // codes issued ahead of the scales' staging: one round trip for both
-    kq_act_ld(act16_codes<QF>(al, 0), sb, x);
-    stage_act16<T, QF>(al, 0, a.K, da);
+    kq_act_ld(act16_codes<QF>(a, 0), sb, x);
+    stage_act16<T, QF>(a, 0, a.K, da);
 #pragma unroll
     for (int c = 0; c < 4; ++c) swap_halves(x[c]);
-#else
-    const auto aq = stage_act16<T, QF>(al, 0, a.K, da);
-    kq_act(aq, sb, x);
-#endif
     auto step = [&](KqPass<T> &cw, KqPass<T> &cu, KqPass<T> &nw, KqPass<T> &nu) -> bool {
         const int ahead = tile + (D - 1) * G;
         if (ahead < n_tiles) {
@@ -1580,20 +1538,10 @@ bool launch_mmq_q(const MmqSeg *seg, const int *types, int nseg, int mode, const
     if (mode == MMQ_SWIGLU && nseg == 1 && q.mode == 0 && np == 1) {
         // Q4_K / Q5_K gate|up
         auto kq_up = [&]<int T>() {
-            // MIO_BT_IQ=1 (opt-in): the walk quantizes its <= 8 tokens in its own prologue instead
-            // of behind producer workgroups. Bit-exact, but 8 streams 1.7B 1.366 vs 1.252 ms per
-            // step (profiles/r06/bt_iq_ab.txt): one wave per token quantizing 8 superblocks in a
-            // row is a longer chain than the producers' hop
-            static const bool iq = getenv("MIO_BT_IQ") && getenv("MIO_BT_IQ")[0] == '1';
-            if (T == 12 && iq && a.nt <= 8 && a.K % 256 == 0 && a.K <= 2048 && tiles > n_cu() && mmq_loop_on() &&
-                (kq_loop_mask() & 2)) {
-                auto kern = k_mmq16_loop_kq<12, MMQ_SWIGLU, 0, 0, true>;
-                const size_t l = (size_t)2 * MMQ_NT * 4 * sizeof(float) + (size_t)(a.K / 256) * TT16 * sizeof(float) +
-                                 (size_t)a.nt * act_bytes(a.K);
-                if (l > 64 * 1024) allow_lds_mmq(reinterpret_cast<const void *>(kern));
-                hipLaunchKernelGGL(kern, dim3(n_cu()), dim3(MMQ_NT), l, s, sg[0], a, q, tiles);
-                return true;
-            }
+            // the tokens are quantized behind producer workgroups: the walk quantizing its <= 8
+            // tokens in its own prologue measured 8 streams 1.7B 1.366 vs 1.252 ms per step
+            // (profiles/r06/bt_iq_ab.txt): one wave per token quantizing 8 superblocks in a row is
+            // a longer chain than the producers' hop
             const int nl = n_cu() - a.nt;  // the producers keep CUs of their own
             if (a.K % 256 == 0 && a.K <= 2048 && tiles > nl && nl > 0 && mmq_loop_on() && (kq_loop_mask() & 2)) {
                 auto kern = k_mmq16_loop_kq<T, MMQ_SWIGLU, 1, 0>;

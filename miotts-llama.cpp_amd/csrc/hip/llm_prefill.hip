@@ -176,17 +176,9 @@ struct XRedCfg {
     static constexpr int TT = NP == 1 ? 4 : (NP == 3 ? 2 : 1);
     static constexpr int TB = NP == 1 ? 8 : (NP == 3 ? 4 : 8);
 };
-// MIO_BT_MINB (compile-time A/B): workgroups per CU the one-pass batched matvecs (attn_out,
-// ffn_in) are register-budgeted for; with MIO_BT_WGM=2 at run time their grids double
-#ifndef MIO_BT_MINB
-#define MIO_BT_MINB 1
-#endif
-#ifndef MIO_BT_XRED
-#define MIO_BT_XRED 1
-#endif
 
-// epi(row, t, dot0, dot1): once per (row, token); with MIO_BT_XRED on the lane that holds
-// the totals (lane-varying values), else wave-uniform values on every lane
+// epi(row, t, dot0, dot1): once per (row, token), on the lane that holds the totals
+// (lane-varying values); stream_rows_bu passes wave-uniform values on every lane
 template <int T, int NP, int NM, class Epi>
 __device__ __forceinline__ void stream_rows_bx(const QMat W0, const QMat W1, int lo, int hi,
                                                Frag (&A)[CfgB<T, NP, NM>::U], Frag (&B)[CfgB<T, NP, NM>::U], char *smem,
@@ -338,15 +330,15 @@ __device__ __forceinline__ void stream_rows_bu(const QMat W0, const QMat W1, int
     }
 }
 
-// The multi-token streaming rows: transposed totals (MIO_BT_XRED, default) or one wave-wide
-// tree per total (A/B build). Either way epi runs once per (row, token) on one lane.
+// The multi-token streaming rows: transposed totals, or one wave-wide tree per total for
+// BF16. Either way epi runs once per (row, token) on one lane.
 template <int T, int NP, int NM, class Epi>
 __device__ __forceinline__ void stream_rows_b(const QMat W0, const QMat W1, int lo, int hi,
                                               Frag (&A)[CfgB<T, NP, NM>::U], Frag (&B)[CfgB<T, NP, NM>::U], char *smem,
                                               int nt, Epi &&epi, int split = INT_MAX) {
     // BF16: the per-total trees (its 64-B units and 16-register activation slices leave no
     // room for the transposed reduction's token groups)
-    if constexpr (MIO_BT_XRED && T != 30)
+    if constexpr (T != 30)
         stream_rows_bx<T, NP, NM>(W0, W1, lo, hi, A, B, smem, nt, epi, split);
     else
         stream_rows_bu<T, NP, NM>(W0, W1, lo, hi, A, B, smem, nt, epi, split);
@@ -601,7 +593,7 @@ __global__ __launch_bounds__(64) void k_pf_rope(LlmDims d, const float *q_norm, 
     }
 }
 
-// attend_chunk(_mfma) + attn_merge_last of token t's (kv head, chunk): records in pb.part
+// attend_chunk_mfma + attn_merge_last of token t's (kv head, chunk): records in pb.part
 // [t][H][max_splits][REC], tickets pb.att_cnt[t][Hkv], outputs pb.att[t][H * hd].
 // att_q >= 0: the merger also writes token t's O-matvec activation record (attn_merge_last).
 template <int HD, int G>
@@ -612,7 +604,6 @@ __device__ __forceinline__ void merge_token(const LlmDims &d, int pos, int t, in
                            pb.att + (size_t)t * KO + (size_t)kvh * G * HD, att_q, carve_t(pb.act, KO, t).a,
                            att_q == 1 ? kvh * G * HD / 256 : kvh * G * HD / 32);
 }
-#if MIO_ATT_MFMA
 template <int HD, int G>
 __device__ __forceinline__ void attend_and_merge(const LlmDims &d, const _Float16 (*qh)[HD], const char *img, int t0,
                                                  int pos, int ch, int t, int kvh, const PrefillBuffers &pb, int att_q) {
@@ -623,20 +614,6 @@ __device__ __forceinline__ void attend_and_merge(const LlmDims &d, const _Float1
     attend_chunk_mfma<HD, G>(qh, img, img + AttM<HD>::IMG, t0, pos, d.scale, part + head0 + (uint32_t)ch * C::REC, gs);
     merge_token<HD, G>(d, pos, t, kvh, pb, att_q, part, head0, gs);
 }
-#else
-template <int HD, int G>
-__device__ __forceinline__ void attend_and_merge(const LlmDims &d, const float (*qs)[HD],
-                                                 const h8 (&kr)[AttCfg<HD>::IT], const h8 (&vr)[AttCfg<HD>::IT],
-                                                 int t0, int pos, int ch, int t, int kvh,
-                                                 float (*wres)[G][HD + 2], const PrefillBuffers &pb, int att_q) {
-    using C = AttCfg<HD>;
-    const uint32_t gs = (uint32_t)(d.max_splits * C::REC);
-    float *part = pb.part + (size_t)t * d.n_head * gs;  // token t's records (wave-uniform)
-    const uint32_t head0 = (uint32_t)(kvh * G) * gs;
-    attend_chunk<HD, G>(qs, kr, vr, t0, pos, d.scale, wres, part + head0 + (uint32_t)ch * C::REC, gs);
-    merge_token<HD, G>(d, pos, t, kvh, pb, att_q, part, head0, gs);
-}
-#endif
 
 // One workgroup per (ATT_CHUNK-position chunk, kv head, token): causal softmax over the
 // chunk's positions <= the token's position in the token's own sequence, all rows read from
@@ -649,7 +626,6 @@ template <int HD, int G>
 __global__ __launch_bounds__(AttCfg<HD>::NT) void k_pf_attention(LlmDims d, const _Float16 *kc, const _Float16 *vc,
                                                                  PrefillBuffers pb, int att_q) {
     using C = AttCfg<HD>;
-    __shared__ float qs[G][HD];
     const int kvh = blockIdx.x % d.n_kv, t = blockIdx.x / d.n_kv, ch = blockIdx.y;
     const int pos = pb.pos[t * pb.pos_stride];
     const int t0 = ch * ATT_CHUNK;
@@ -657,7 +633,6 @@ __global__ __launch_bounds__(AttCfg<HD>::NT) void k_pf_attention(LlmDims d, cons
     const size_t kvo = (size_t)pb.seq[t * pb.seq_stride] * pb.seq_kv + (size_t)kvh * d.n_ctx * HD;
     const int QD = (d.n_head + 2 * d.n_kv) * HD;
     const float *qsrc = pb.qkv + (size_t)t * QD + (size_t)kvh * G * HD;
-#if MIO_ATT_MFMA
     using A = AttM<HD>;
     __shared__ __attribute__((aligned(16))) char img[2 * A::IMG];
     __shared__ __attribute__((aligned(16))) _Float16 qh[G][HD];
@@ -667,14 +642,6 @@ __global__ __launch_bounds__(AttCfg<HD>::NT) void k_pf_attention(LlmDims d, cons
     kv_stage<HD>(kr, vr, -1, img, img + A::IMG);
     lds_barrier();
     attend_and_merge<HD, G>(d, qh, img, t0, pos, ch, t, kvh, pb, att_q);
-#else
-    __shared__ float wres[C::NW][G][HD + 2];
-    h8 kr[C::IT], vr[C::IT];
-    load_kv_rows<HD>(kc + kvo, vc + kvo, t0, pos, kr, vr);
-    for (int e = threadIdx.x; e < G * HD; e += C::NT) qs[e / HD][e % HD] = qsrc[e];
-    lds_barrier();
-    attend_and_merge<HD, G>(d, qs, kr, vr, t0, pos, ch, t, kvh, wres, pb, att_q);
-#endif
 }
 
 // Batched decode attention (one token per sequence, so no token of the launch reads a row
@@ -692,13 +659,9 @@ __global__ __launch_bounds__(AttCfg<HD>::NT) void k_bt_attention(LlmDims d, cons
     constexpr int PER = HD / 64;
     __shared__ float qs[G][HD];
     __shared__ float knew[HD], vnew[HD];
-#if MIO_ATT_MFMA
     using A = AttM<HD>;
     __shared__ __attribute__((aligned(16))) char img[2 * A::IMG];
     __shared__ __attribute__((aligned(16))) _Float16 qh[G][HD];
-#else
-    __shared__ float wres[C::NW][G][HD + 2];
-#endif
     const int kvh = blockIdx.x % d.n_kv, t = blockIdx.x / d.n_kv, ch = blockIdx.y;
     const int pos = pb.pos[t * pb.pos_stride];
     const int t0 = ch * ATT_CHUNK;
@@ -722,13 +685,8 @@ __global__ __launch_bounds__(AttCfg<HD>::NT) void k_bt_attention(LlmDims d, cons
     };
     HeadIn<HD> hin;
     if (wave < G + (owner ? 1 : 0)) head_src(wave, hin);
-#if MIO_ATT_MFMA
     h8 kr[A::VI], vr[A::VI];
     kv_issue<HD>(kc, vc, t0, pos, kr, vr);  // row pos is staged from LDS below
-#else
-    h8 kr[C::IT], vr[C::IT];
-    load_kv_rows<HD>(kc, vc, t0, pos, kr, vr);  // row pos comes from LDS below
-#endif
     for (int hh = wave; hh < G + (owner ? 1 : 0); hh += C::NW) {
         const bool isk = hh == G;
         if (hh != wave) head_src(hh, hin);
@@ -742,41 +700,20 @@ __global__ __launch_bounds__(AttCfg<HD>::NT) void k_bt_attention(LlmDims d, cons
                 kc[(size_t)pos * HD + p] = (_Float16)knew[p];
                 vc[(size_t)pos * HD + p] = (_Float16)vr16;
             }
-#if MIO_ATT_MFMA
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
             kv_stage_row<HD>(knew, vnew, pos - t0, img, img + A::IMG);
-#endif
-        }
-#if MIO_ATT_MFMA
-        else {
+        } else {
             q_to_f16<HD>(qs[hh], qh[hh]);
         }
-#endif
     }
-#if MIO_ATT_MFMA
     kv_stage<HD>(kr, vr, owner ? pos - t0 : -1, img, img + A::IMG);
     lds_barrier();
     attend_and_merge<HD, G>(d, qh, img, t0, pos, ch, t, kvh, pb, att_q);
-#else
-    lds_barrier();
-    if (owner) {
-        const int sl = threadIdx.x / C::LP, lp = lane % C::LP, r = pos - t0;
-        if (sl == r % C::NS) {
-            h8 kn, vn;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) kn[i] = (_Float16)knew[lp * 8 + i], vn[i] = (_Float16)vnew[lp * 8 + i];
-#pragma unroll
-            for (int it = 0; it < C::IT; ++it)
-                if (it == r / C::NS) kr[it] = kn, vr[it] = vn;
-        }
-    }
-    attend_and_merge<HD, G>(d, qs, kr, vr, t0, pos, ch, t, kvh, wres, pb, att_q);
-#endif
 }
 
 template <int NP, int T>
-__global__ __launch_bounds__(MT, MIO_BT_MINB) void k_pf_attn_out(LlmDims d, QMat wo, PrefillBuffers pb, int nt, int rpw) {
+__global__ __launch_bounds__(MT, 1) void k_pf_attn_out(LlmDims d, QMat wo, PrefillBuffers pb, int nt, int rpw) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int K = wo.k, E = d.n_embd, KR = rec_k(K, T);
     int lo, hi;
@@ -797,7 +734,7 @@ __global__ __launch_bounds__(MT, MIO_BT_MINB) void k_pf_attn_out(LlmDims d, QMat
 
 // FQ = 2: RMSNorm + quantization in the launch from inputs loaded ahead of the weights (xpre)
 template <int NP, int T, int FQ = 0>
-__global__ __launch_bounds__(MT, MIO_BT_MINB) void k_pf_ffn_in(LlmDims d, const float *norm_w, QMat gate, QMat up,
+__global__ __launch_bounds__(MT, 1) void k_pf_ffn_in(LlmDims d, const float *norm_w, QMat gate, QMat up,
                                                   PrefillBuffers pb, int nt) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int K = d.n_embd, KR = rec_k(K, T);
@@ -1159,15 +1096,6 @@ void launch_quant(const LlmDims &d, int mode, const float *src, int K, const flo
 // the launch that quantizes its activations once (k_bt_quant).
 // decode: every token is its own sequence (the batched decode step): attention per token
 // with the RoPE / KV append inside (k_bt_attention).
-// MIO_BT_WGM (A/B, default 1): grid multiplier of the one-pass batched matvecs (two workgroups
-// per CU need a MIO_BT_MINB=2 build: <= 128 VGPRs, and <= 80 KB of LDS)
-static LlmDims bt_wgm(const LlmDims &d, int K) {
-    static const int m = getenv("MIO_BT_WGM") ? atoi(getenv("MIO_BT_WGM")) : 1;
-    LlmDims r = d;
-    if (m > 1 && pick_np(K) == 1) r.n_wg = d.n_wg * m;
-    return r;
-}
-
 void launch_layers(const LlmDims &d, const LayerW *layers, int n_layer, _Float16 *kcache, _Float16 *vcache,
                    const PrefillBuffers &pb, int nt, int n_chunks, bool decode, hipStream_t s) {
     const size_t layer_kv = (size_t)d.n_kv * d.n_ctx * d.hd;
@@ -1337,14 +1265,13 @@ void launch_layers(const LlmDims &d, const LayerW *layers, int n_layer, _Float16
                 launch_mmq(&sg, &L.wo.type, 1, MMQ_RESID, MmqArgs{pb.act, act_bytes(L.wo.k), L.wo.k, nt, pb.x, d.n_embd, {}},
                            s);
             } else {
-                const LlmDims dw = bt_wgm(d, L.wo.k);
-                const int grid = matvec_grid(dw, L.wo.rows), rpw = rows_per_wave(L.wo.rows, grid);
+                const int grid = matvec_grid(d, L.wo.rows), rpw = rows_per_wave(L.wo.rows, grid);
                 const int KR = rec_k(L.wo.k, L.wo.type);
                 over_tokens(KR, rpw, [&](int, int n, const PrefillBuffers &q) {
                     dispatch_nt<true>(L.wo.k, L.wo.type, [&]<int NP, int T>() {
                         allow_lds(k_pf_attn_out<NP, T>);
                         hipLaunchKernelGGL((k_pf_attn_out<NP, T>), dim3(grid), dim3(MT), pf_lds_bytes(KR, n, rpw), s,
-                                           dw, L.wo, q, n, rpw);
+                                           d, L.wo, q, n, rpw);
                     });
                 });
             }
@@ -1360,8 +1287,7 @@ void launch_layers(const LlmDims &d, const LayerW *layers, int n_layer, _Float16
         } else if (mq2) {
             launch_mmq(&sg2, &L.gate.type, 1, MMQ_SWIGLU, a2, s);
         } else {
-            const LlmDims dw = bt_wgm(d, d.n_embd);
-            const int grid = matvec_grid(dw, L.gate.rows);
+            const int grid = matvec_grid(d, L.gate.rows);
             const int KR = rec_k(d.n_embd, L.gate.type);
             over_tokens(KR, 0, [&](int, int n, const PrefillBuffers &q) {
                 dispatch_nt<true>(d.n_embd, L.gate.type, [&]<int NP, int T>() {
@@ -1369,12 +1295,12 @@ void launch_layers(const LlmDims &d, const LayerW *layers, int n_layer, _Float16
                         if (ff) {
                             allow_lds(k_pf_ffn_in<NP, T, 2>);
                             hipLaunchKernelGGL((k_pf_ffn_in<NP, T, 2>), dim3(grid), dim3(MT), pf_lds_bytes(d.n_embd, n, 0),
-                                               s, dw, L.ffn_norm, L.gate, L.up, q, n);
+                                               s, d, L.ffn_norm, L.gate, L.up, q, n);
                             return;
                         }
                     }
                     allow_lds(k_pf_ffn_in<NP, T>);
-                    hipLaunchKernelGGL((k_pf_ffn_in<NP, T>), dim3(grid), dim3(MT), pf_lds_bytes(KR, n, 0), s, dw,
+                    hipLaunchKernelGGL((k_pf_ffn_in<NP, T>), dim3(grid), dim3(MT), pf_lds_bytes(KR, n, 0), s, d,
                                        L.ffn_norm, L.gate, L.up, q, n);
                 });
             });

@@ -51,16 +51,6 @@ bool fuse_ffn(const mio_hip_llm *m, int il) {
     return env && mio::ffn_fused_supported(m->dims, m->layers[il]);
 }
 
-// MIO_LAYER_FUSE (default 0, A/B): 1 = a layer whose attention block runs as k_layer_att and
-// whose FFN pair runs as k_ffn runs both as ONE launch (k_layer, kLayer) where that is
-// instantiated (layer_fused_supported). Bit-identical, but slower on the box (r06, 1.7B Q4_K_M:
-// 0.800-0.812 vs 0.726-0.729 ms per token, profiles/r06/layer_fuse_ab.txt): the in-launch x and
-// h hand-offs cost what the boundaries did, and the FFN weight burst slows the attention chain.
-bool fuse_layer(const mio_hip_llm *m, int il) {
-    static const bool env = env_flag("MIO_LAYER_FUSE", false);
-    return env && fuse_layer_att(m, il) && fuse_ffn(m, il) && mio::layer_fused_supported(m->dims, m->layers[il]);
-}
-
 // Can this model run launch `kind` on layer il: the attention launches need an attention
 // layer, the conv launches an lfm2 short-conv layer, a fused launch its switch and its
 // instantiation. The unfused launches exist for every layer of their sort, whatever the step
@@ -76,7 +66,6 @@ bool kind_in_layer(const mio_hip_llm *m, mio::StepKind kind, int il) {
         case mio::kAttO: return !conv && fuse_att_o(m);
         case mio::kLayerAtt: return !conv && fuse_layer_att(m, il);
         case mio::kFfn: return fuse_ffn(m, il);
-        case mio::kLayer: return !conv && fuse_layer(m, il);
         case mio::kFfnIn:
         case mio::kFfnDown:
         case mio::kLmHead:
@@ -91,10 +80,6 @@ bool kind_in_layer(const mio_hip_llm *m, mio::StepKind kind, int il) {
 int layer_kinds(const mio_hip_llm *m, int il, mio::StepKind *w) {
     auto has = [&](mio::StepKind k) { return kind_in_layer(m, k, il); };
     int n = 0;
-    if (has(mio::kLayer)) {
-        w[n++] = mio::kLayer;
-        return n;
-    }
     if (has(mio::kConvIn))
         w[n++] = mio::kConvIn, w[n++] = mio::kConvOut;
     else if (has(mio::kLayerAtt))
@@ -256,16 +241,11 @@ int check_handoff(mio_hip_llm *m) {
     for (int il = 0; il < m->n_layer && !any; ++il) any = fuse_ffn(m, il);
     if (!any) return MIO_OK;
     int flag = 0;
-    // the plain counters' flag and the two k_layer counter sets' (each set has its own)
-    int *f[3] = {m->buf.att_cnt + mio::kRdyFlag, m->buf.att_cnt + mio::kLayOff + mio::kRdyFlag,
-                 m->buf.att_cnt + mio::kLayOff + mio::kLaySet + mio::kRdyFlag};
-    int fl[3] = {0, 0, 0};
-    for (int i = 0; i < 3; ++i)
-        MIO_HIP_CHECK(hipMemcpyAsync(&fl[i], f[i], sizeof(int), hipMemcpyDeviceToHost, m->d->stream));
+    int *f = m->buf.att_cnt + mio::kRdyFlag;
+    MIO_HIP_CHECK(hipMemcpyAsync(&flag, f, sizeof(int), hipMemcpyDeviceToHost, m->d->stream));
     MIO_HIP_CHECK(hipStreamSynchronize(m->d->stream));
-    flag = fl[0] | fl[1] | fl[2];
     if (flag) {
-        for (int i = 0; i < 3; ++i) MIO_HIP_CHECK(hipMemsetAsync(f[i], 0, sizeof(int), m->d->stream));
+        MIO_HIP_CHECK(hipMemsetAsync(f, 0, sizeof(int), m->d->stream));
         mio::set_error("llm decode: an in-launch hand-off wait (attention -> O, or gate|up -> down) timed out");
         return MIO_ERR_HIP;
     }

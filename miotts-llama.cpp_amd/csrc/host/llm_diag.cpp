@@ -283,7 +283,6 @@ uint64_t kind_bytes(const mio_hip_llm *m, mio::StepKind kind, const mio::LayerW 
         case mio::kFfnIn: return ffn_in_bytes;
         case mio::kFfnDown: return ffn_down_bytes;
         case mio::kFfn: return ffn_bytes;
-        case mio::kLayer: return layer_att_bytes + ffn_bytes;
         case mio::kLmHead: return lm_bytes;
         case mio::kConvIn: return conv_in_bytes;
         case mio::kConvOut: return conv_out_bytes;
@@ -295,7 +294,7 @@ uint64_t kind_bytes(const mio_hip_llm *m, mio::StepKind kind, const mio::LayerW 
 
 // Live timing of one kernel of the decode step (bench.py roofline): launches kernel `which`
 // (a StepKind other than the flush sampler) of layer kernel_layer() `iters` times on the
-// runner's stream between HIP events (MIO_TK_MODE below), with the buffers and device state
+// runner's stream between HIP events (as a replayed graph, below), with the buffers and device state
 // left by the last generate/eval. Returns the mean duration and the algorithmic HBM bytes of
 // one launch (kind_bytes, at the decode state's current pos).
 extern "C" int mio_hip_llm_time_kernel(mio_hip_llm *m, int which, int iters, float *avg_ms, uint64_t *bytes) {
@@ -316,55 +315,38 @@ extern "C" int mio_hip_llm_time_kernel(mio_hip_llm *m, int which, int iters, flo
     MIO_HIP_CHECK(hipEventCreate(e1.put()));
     hipStream_t s = m->d->stream;
     // The fused launches' hand-off counters are zeroed by the launch after them in a step: here
-    // a memset does it before every launch. MIO_TK_MODE (default 1): how the iters launches are
-    // timed with HIP events.
-    //   0: issued eagerly, minus an eager loop of the memsets alone (rounds 4-6; the host issues
-    //      a memset + launch pair in about the GPU time of one, so both loops are partly
-    //      host-paced: k_layer_att's figure moved 11.7-14.9 us between runs of one tree);
-    //   1: both loops captured as hipGraphs and replayed (GPU-paced, +-0.3 % between reps):
-    //      k_layer_att 12.1 us vs the eager rocprof mean 12.65 of a real step, k_ffn 10.65 vs
-    //      10.9, lm_head 46-48 vs 47.2 (profiles/r06/time_kernel_modes.txt);
-    //   2: as 1, with the reference loop launching an empty one-workgroup kernel (launch_nop)
-    //      after each memset: per launch = the kernel minus an empty launch (1.5-2 us below the
-    //      rocprof durations, which count a launch's dispatch).
-    static const int tk_mode = env_int("MIO_TK_MODE", 1, 0, 2);
+    // a memset does it before every launch, and a loop of the memsets alone is timed and
+    // subtracted. Both loops are captured as hipGraphs and replayed: GPU-paced, +-0.3 % between
+    // reps and within 5 % of the rocprof means of a real step, where eagerly issued loops were
+    // partly host-paced (k_layer_att moved 11.7-14.9 us between runs of one tree;
+    // profiles/r06/time_kernel_modes.txt).
     const bool fused = kind >= mio::kAttO;
-    // ref: 0 = the kernel itself, 1 = nothing (memset only), 2 = the empty launch
-    auto launch = [&](int ref) -> int {
+    auto launch = [&](bool kernel) -> int {
         if (int rc = fused ? reset_rdy(m, s) : MIO_OK) return rc;
-        if (ref == 0)
-            mio::launch_step_kernel(kind, m->ctx(), il, m->buf, s);
-        else if (ref == 2)
-            mio::launch_nop(s);
+        if (kernel) mio::launch_step_kernel(kind, m->ctx(), il, m->buf, s);
         return MIO_OK;
     };
-    auto launches = [&](int ref) -> int {
-        int rc = MIO_OK;
-        for (int i = 0; i < iters && rc == MIO_OK; ++i) rc = launch(ref);
-        return rc;
-    };
-    auto timed = [&](int ref, float &ms) -> int {
+    auto timed = [&](bool kernel, float &ms) -> int {
         mio::GraphExec ge;
-        if (tk_mode >= 1) {
-            if (int rc = mio::capture_graph(s, [&] { return launches(ref); }, ge.put())) return rc;
-            MIO_HIP_CHECK(hipGraphLaunch(ge, s));  // warm replay
-        }
-        MIO_HIP_CHECK(hipEventRecord(e0, s));
-        if (ge)
-            MIO_HIP_CHECK(hipGraphLaunch(ge, s));
-        else if (int rc = launches(ref))
+        auto launches = [&]() -> int {
+            int rc = MIO_OK;
+            for (int i = 0; i < iters && rc == MIO_OK; ++i) rc = launch(kernel);
             return rc;
+        };
+        if (int rc = mio::capture_graph(s, launches, ge.put())) return rc;
+        MIO_HIP_CHECK(hipGraphLaunch(ge, s));  // warm replay
+        MIO_HIP_CHECK(hipEventRecord(e0, s));
+        MIO_HIP_CHECK(hipGraphLaunch(ge, s));
         MIO_HIP_CHECK(hipEventRecord(e1, s));
         MIO_HIP_CHECK(hipEventSynchronize(e1));
         MIO_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
         return MIO_OK;
     };
-    if (int rc = launch(0)) return rc;  // warm
+    if (int rc = launch(true)) return rc;  // warm
     float ms = 0, ms_ref = 0;
-    if (int rc = timed(0, ms)) return rc;
-    const int ref = tk_mode == 2 ? 2 : (fused ? 1 : -1);
-    if (ref > 0) {
-        if (int rc = timed(ref, ms_ref)) return rc;
+    if (int rc = timed(true, ms)) return rc;
+    if (fused) {
+        if (int rc = timed(false, ms_ref)) return rc;
         ms = std::max(0.0f, ms - ms_ref);
     }
     *avg_ms = ms / iters;

@@ -153,7 +153,6 @@ bool no_graph();    // MIO_NO_GRAPH=1: every launch eager
 bool fuse_att_o(const mio_hip_llm *m);
 bool fuse_layer_att(const mio_hip_llm *m, int il);
 bool fuse_ffn(const mio_hip_llm *m, int il);
-bool fuse_layer(const mio_hip_llm *m, int il);
 // can this model run launch `kind` on layer il (kLmHead / kSample: on any)
 bool kind_in_layer(const mio_hip_llm *m, mio::StepKind kind, int il);
 constexpr int kLayerKindsMax = 5;

@@ -493,7 +493,7 @@ SYNTH_EOT = 259
 # The decode step's launch kinds (enum StepKind, csrc/hip/llm_kernels.h): what step_kinds()
 # returns and time_kernel / trace_kernel take. 7 is the flush sampler (after the last step).
 STEP_KIND_NAMES = {0: "attn_in", 1: "attention", 2: "attn_out", 3: "ffn_in", 4: "ffn_down", 6: "lm_head",
-                   7: "sample", 8: "conv_in", 9: "conv_out", 10: "att_o", 11: "layer_att", 12: "ffn", 13: "layer",
+                   7: "sample", 8: "conv_in", 9: "conv_out", 10: "att_o", 11: "layer_att", 12: "ffn",
                    14: "sample_chain"}
 
 

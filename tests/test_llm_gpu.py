@@ -450,12 +450,11 @@ print(k.count(11), k.count(10), k.count(12), k.count(13), h.hexdigest())
 
 @pytest.mark.parametrize("preset", [2, 3, 4])
 def test_fused_attention_launches_bit_identical(synth_llm_path, tmp_path, preset):
-    """The whole layer as one launch (k_layer, layers >= 1, r06, opt-in), the attention block as one
-    launch (k_layer_att) + the FFN pair as one launch (k_ffn), attention + O as one launch
-    (k_att_o) and the separate launches run the same arithmetic: 80 free-run tokens and the
-    logits of three later evaluations are bit-identical across MIO_LAYER_FUSE / MIO_LAYER_GATE /
+    """The attention block as one launch (k_layer_att) + the FFN pair as one launch (k_ffn),
+    attention + O as one launch (k_att_o) and the separate launches run the same arithmetic: 80
+    free-run tokens and the logits of three later evaluations are bit-identical across
     MIO_LAYER_ATT / MIO_ATT_FUSE_O / MIO_FFN_FUSE (each variant is a fresh process: the switches
-    are read once). k_layer is instantiated for the 1.7B Q4_K_M shapes (preset 3).
+    are read once). No variant's step holds launch kind 13 (the removed whole-layer launch).
     The same holds at long context on a peaked K/V state (written with set_kv_rows into every
     layer of a second load at n_ctx 32768): the logits at positions 4096 and 32767 (4096 only for
     the 1.7B model) join the digest. The single-launch attention these paths share their chunk
@@ -469,19 +468,16 @@ def test_fused_attention_launches_bit_identical(synth_llm_path, tmp_path, preset
     script.write_text(_FUSION_SCRIPT)
     pkg = os.path.dirname(os.path.dirname(m.__file__))
     outs = {}
-    for name, env in (("layer", {"MIO_LAYER_FUSE": "1"}), ("layer_gate", {"MIO_LAYER_FUSE": "1", "MIO_LAYER_GATE": "2"}),
-                      ("layer_att", {"MIO_LAYER_FUSE": "0", "MIO_LAYER_ATT": "1"}),
-                      ("att_o", {"MIO_LAYER_FUSE": "0", "MIO_LAYER_ATT": "0"}),
+    for name, env in (("layer_att", {"MIO_LAYER_ATT": "1"}),
+                      ("att_o", {"MIO_LAYER_ATT": "0"}),
                       ("separate", {"MIO_ATT_FUSE_O": "0", "MIO_FFN_FUSE": "0"})):
         p = subprocess.run([sys.executable, str(script), path, pkg, long_pos], capture_output=True, text=True, timeout=240,
                            env=dict(os.environ, **env))
         assert p.returncode == 0, p.stderr[-2000:]
         outs[name] = p.stdout.split()
     print(outs)
-    if preset == 3:
-        assert int(outs["layer"][3]) == 27 and int(outs["layer_gate"][3]) == 27  # layers 1..27 as k_layer
     assert int(outs["layer_att"][0]) > 0 and int(outs["layer_att"][3]) == 0
-    assert int(outs["att_o"][0]) == 0 and int(outs["att_o"][1]) > 0
+    assert int(outs["att_o"][0]) == 0 and int(outs["att_o"][1]) > 0 and int(outs["att_o"][3]) == 0
     assert int(outs["separate"][0]) == int(outs["separate"][1]) == int(outs["separate"][2]) == 0
     assert int(outs["separate"][3]) == 0
     assert int(outs["layer_att"][2]) > 0  # the FFN pairs ran fused

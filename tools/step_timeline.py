@@ -123,41 +123,3 @@ if jf:
           f"{med(T[:, :, 3] - base, isD):.2f} (first {firstv(T[:, :, 3] - base, isD):.2f}), h in "
           f"{med(T[:, :, 1] - base, isD):.2f}, quantized {med(T[:, :, 2] - base, isD):.2f}, end "
           f"{med(T[:, :, 7] - base, isD):.2f} (last {lastv(T[:, :, 7] - base, isD):.2f}) us after the launch's first start")
-# the whole layer in one launch (k_layer): roles by workgroup slot (1.7B: GW = no = GI = GD = 256
-# workgroups; the attention chunks are the slots with mark 4 = K/V staged)
-jl = [i for i, n in enumerate(names) if n == "layer"]
-if jl:
-    T = t[jl]
-    base = s0[jl][:, None]
-    n_act = int(np.isfinite(T[0, :, 4]).sum())
-    GW = NO = GI = GD = int(os.environ.get("TL_ROLE_WG", 256))
-    j = np.arange(T.shape[1])[None, :].repeat(T.shape[0], 0)
-    isP = j < GW
-    isA = (j >= GW) & (j < GW + n_act)
-    isO = (j >= GW + n_act) & (j < GW + n_act + NO)
-    isF = (j >= GW + n_act + NO) & (j < GW + n_act + NO + GI)
-    isD = (j >= GW + n_act + NO + GI) & (j < GW + n_act + NO + GI + GD)
-
-    def med(x, msk):
-        return float(np.nanmedian(np.where(msk, x, np.nan)))
-
-    def lastv(x, msk):
-        return float(np.nanmedian(np.nanmax(np.where(msk, x, np.nan), axis=1)))
-
-    def firstv(x, msk):
-        return -lastv(-x, msk)
-    R = T - base[:, :, None]
-    mg = isA & np.isfinite(T[:, :, 5])
-    print(f"  layer: producers end {med(R[:, :, 7], isP):.2f} (last {lastv(R[:, :, 7], isP):.2f}); {n_act} attention: "
-          f"q|k|v ready {med(R[:, :, 3], isA):.2f}, end {med(R[:, :, 7], isA):.2f}; mergers ticket "
-          f"{med(R[:, :, 5], mg):.2f}, outputs written {med(R[:, :, 6], mg):.2f}")
-    print(f"  layer: O start {med(R[:, :, 0], isO):.2f} (last {lastv(R[:, :, 0], isO):.2f}), wait done "
-          f"{med(R[:, :, 3], isO):.2f}, x written {med(R[:, :, 6], isO):.2f} (last {lastv(R[:, :, 6], isO):.2f}), end "
-          f"{med(R[:, :, 7], isO):.2f}")
-    print(f"  layer: gate|up start {med(R[:, :, 0], isF):.2f} (last {lastv(R[:, :, 0], isF):.2f}), x wait done "
-          f"{med(R[:, :, 3], isF):.2f} (first {firstv(R[:, :, 3], isF):.2f}), x in {med(R[:, :, 1], isF):.2f}, "
-          f"quantized {med(R[:, :, 2], isF):.2f}, end {med(R[:, :, 7], isF):.2f} (last {lastv(R[:, :, 7], isF):.2f})")
-    print(f"  layer: down start {med(R[:, :, 0], isD):.2f} (last {lastv(R[:, :, 0], isD):.2f}), h wait done "
-          f"{med(R[:, :, 3], isD):.2f} (first {firstv(R[:, :, 3], isD):.2f}), h in {med(R[:, :, 1], isD):.2f}, "
-          f"quantized {med(R[:, :, 2], isD):.2f}, end {med(R[:, :, 7], isD):.2f} (last {lastv(R[:, :, 7], isD):.2f}) "
-          f"us after the launch's first start")
