@@ -245,6 +245,11 @@ int mio_hip_llm_timeline(mio_hip_llm *m, uint64_t *out, int max_launches, int *n
  * replays the step without it. *n = the count; kinds may be null (count only), else it needs
  * cap >= *n entries. */
 int mio_hip_llm_step_kinds(const mio_hip_llm *m, int *kinds, int cap, int *n);
+/* Diagnostic: *n = the kernel launches one batched decode step of B streams issues without the
+ * sampler chain (the kernel nodes of the step as a captured graph). The first call for a batch
+ * size runs one decode step of B one-token streams, as mio_hip_llm_generate_batch's first step
+ * does; B as mio_hip_llm_generate_batch takes it. */
+int mio_hip_llm_batch_step_launches(mio_hip_llm *m, int B, int *n);
 /* lfm2 short-conv state of layer il: [4][n_embd] floats, slot p & 3 = the B*X row of position
  * p (parity tests). set = 0 copies it out, 1 in. Error for an attention layer. */
 int mio_hip_llm_conv_ring(mio_hip_llm *m, int il, float *ring, int set);

@@ -126,6 +126,11 @@ int mio_synth_voice_gguf(const char *path, uint64_t seed);
  * preset 0 tiny Q8_0, 1 tiny Q4_K_M, 2 "0.1B" Q8_0, 3 "1.7B" Q4_K_M, 4 "2.6B" Q8_0,
  * 5 tiny Q8_0 qwen2 with attn_{q,k,v}.bias, ... (csrc/testlib/synth.h lists all 19). */
 int mio_synth_llm_gguf(const char *path, int preset, uint64_t seed);
+/* The shape, arch and seed rule of `preset` written with the recipe `qtype`, in SynthLlmCfg's
+ * numbering: 8 Q8_0, 15 Q4_K_M, 16 Q5_K_S, 17 Q5_K_M, 18 MOSTLY_Q6_K (every matrix Q6_K; rows
+ * that are no multiple of 256 fall back to Q8_0), 2 Q4_0, 30 BF16; any other value is
+ * MIO_ERR_INVALID. With the preset's own qtype the file equals mio_synth_llm_gguf's. */
+int mio_synth_llm_gguf_as(const char *path, int preset, int qtype, uint64_t seed);
 
 #ifdef __cplusplus
 }

@@ -293,15 +293,19 @@ __global__ __launch_bounds__(MT) void k_ffn(LlmDims d, const float *norm_w, QMat
 }
 
 // the instantiated (np, gate|up type, su, down np, down type, down su): 1.7B Q4_K_M (down Q4_K
-// or Q6_K), Q5_K_M / Q5_K_S (gate|up Q5_K, down Q5_K or Q6_K) and BF16, 0.1B Q8_0, 2.6B Q8_0 (and LFM2-2.6B), the tiny test presets' shapes
+// or Q6_K), Q5_K_M / Q5_K_S (gate|up Q5_K, down Q5_K or Q6_K), Q6_K and BF16, 0.1B Q8_0 (down Q8_0,
+// or Q6_K: its Q6_K file), 2.6B Q8_0 (and LFM2-2.6B) and Q6_K, the tiny test presets' shapes
 #define MIO_FFN_SHAPES(X) \
     X(1, 12, 6, 3, 12, 3)  \
     X(1, 12, 6, 3, 14, 3)  \
     X(1, 13, 6, 3, 13, 3)  \
     X(1, 13, 6, 3, 14, 3)  \
+    X(1, 14, 6, 3, 14, 3)  \
     X(1, 30, 6, 3, 30, 3)  \
     X(1, 8, 2, 1, 8, 1)    \
-    X(1, 8, 0, 6, 8, 0)
+    X(1, 8, 2, 1, 14, 1)   \
+    X(1, 8, 0, 6, 8, 0)    \
+    X(1, 14, 0, 6, 14, 0)
 
 struct FfnShape {
     int np, t, su, npd, td, sud, GI, GD;

@@ -1292,7 +1292,9 @@ __global__ __launch_bounds__(MMQ_NT) void k_mmq16_loop_kq(MmqSeg s0, MmqArgs a, 
     const int sb = live ? k : 0;
     auto row_of = [&](int ti) { return min(ti * RT16 + (lane & 15), s0.w.rows - 1); };
     // ring of D tiles' weights: D - 1 tiles in flight while one is reduced
-    constexpr int D = MIO_LOOP_D;
+    // Q6_K W | U pairs: 3 (four Q6Pass pairs exceed 256 VGPRs: 12 B of scratch per lane; three
+    // hold the 2.6B gate|up's <= 3 tiles per workgroup, two of them before the producers' wait)
+    constexpr int D = (T == 14 && NV == 2 && MIO_LOOP_D > 3) ? 3 : MIO_LOOP_D;
     KqPass<T> w[D], u[D];
 #pragma unroll
     for (int d = 0; d < D - 1; ++d) {
@@ -1494,7 +1496,7 @@ void launch_mmq(const MmqSeg *seg, const int *types, int nseg, int mode, const M
 
 
 // The fused shapes of the batched decode (launch_layers): q|k|v of the K-quant models (three
-// segments, RMSNorm input), gate|up (Q4_K / Q5_K, or Q8_0 one-pass pairs; RMSNorm input) and the
+// segments, RMSNorm input), gate|up (Q4_K / Q5_K / Q6_K, or Q8_0 one-pass pairs; RMSNorm input) and the
 // K-quant down matmul (plain h rows of 3 passes). Anything else: false.
 bool launch_mmq_q(const MmqSeg *seg, const int *types, int nseg, int mode, const MmqArgs &a, const MmqQuant &q,
                   hipStream_t s) {
@@ -1531,12 +1533,15 @@ bool launch_mmq_q(const MmqSeg *seg, const int *types, int nseg, int mode, const
         if (types[2] == 13) return go(k_mmq16<13, 13, 13, MMQ_STORE, 0, 1, 0>);
         if (types[2] == 14) return go(k_mmq16<13, 13, 14, MMQ_STORE, 0, 1, 0>);
     }
+    // all-Q6_K files (MOSTLY_Q6_K)
+    if (mode == MMQ_STORE && nseg == 3 && q.mode == 0 && np == 1 && types[0] == 14 && types[1] == 14 && types[2] == 14)
+        return go(k_mmq16<14, 14, 14, MMQ_STORE, 0, 1, 0>);
     // Q8_0 q|k|v (one pass, K <= 2048) when MIO_BT_FQ=0 takes it off the dot4 in-launch path
     if (mode == MMQ_STORE && nseg == 3 && q.mode == 0 && np == 1 && types[0] == 8 && types[1] == 8 && types[2] == 8 &&
         a.K % 256 == 0 && a.K <= 2048)
         return go(k_mmq16<8, 8, 8, MMQ_STORE, 1, 1, 0>);
     if (mode == MMQ_SWIGLU && nseg == 1 && q.mode == 0 && np == 1) {
-        // Q4_K / Q5_K gate|up
+        // Q4_K / Q5_K / Q6_K gate|up
         auto kq_up = [&]<int T>() {
             // the tokens are quantized behind producer workgroups: the walk quantizing its <= 8
             // tokens in its own prologue measured 8 streams 1.7B 1.366 vs 1.252 ms per step
@@ -1553,6 +1558,7 @@ bool launch_mmq_q(const MmqSeg *seg, const int *types, int nseg, int mode, const
         };
         if (types[0] == 12) return kq_up.template operator()<12>();
         if (types[0] == 13) return kq_up.template operator()<13>();
+        if (types[0] == 14) return kq_up.template operator()<14>();
         if (types[0] == 8 && a.K % 256 == 0 && a.K <= 2048) {
             const int nl = n_cu() - a.nt;  // the producers keep CUs of their own
             if (tiles > nl && nl > 0 && mmq_loop_on()) {

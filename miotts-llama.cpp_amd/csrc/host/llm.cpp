@@ -46,9 +46,15 @@ bool fuse_layer_att(const mio_hip_llm *m, int il) {
 
 // MIO_FFN_FUSE (default 1): the FFN pair of a layer as one launch (k_ffn, kFfn) where it
 // is instantiated (ffn_fused_supported); 0 keeps k_ffn_in + k_ffn_down (A/B).
+// A Q8_0 gate|up beside a Q6_K down is fused where the file stores the gate|up as Q8_0 (the 0.1B
+// Q6_K file: 0.396 vs 0.412 ms per step, profiles/q6k/fused_vs_separate.txt). The use_more_bits
+// layers of a 0.1B Q4_K_M file reach the same pair of types with Q5_0 gate|up run as Q8_0: they
+// keep the two launches they always had (never measured fused).
 bool fuse_ffn(const mio_hip_llm *m, int il) {
     static const bool env = env_flag("MIO_FFN_FUSE", true);
-    return env && mio::ffn_fused_supported(m->dims, m->layers[il]);
+    const mio::LayerW &L = m->layers[il];
+    if (L.gate.type == 8 && L.down.type == 14 && m->gate_repacked[il]) return false;
+    return env && mio::ffn_fused_supported(m->dims, L);
 }
 
 // Can this model run launch `kind` on layer il: the attention launches need an attention

@@ -3,6 +3,7 @@
 // step for all of them.
 #include <algorithm>
 #include <cstring>
+#include <vector>
 
 #include "llm_model.h"
 
@@ -215,5 +216,35 @@ extern "C" int mio_hip_llm_generate_batch(mio_hip_llm *m, const int32_t *prompts
         mio::set_error("llm_generate_batch: the in-launch quantization hand-off wait timed out");
         return MIO_ERR_HIP;
     }
+    return MIO_OK;
+}
+
+// The launch structure of the batched step, observable: its kernel nodes as a captured graph.
+extern "C" int mio_hip_llm_batch_step_launches(mio_hip_llm *m, int B, int *n) {
+    MIO_REQUIRE(m && n, MIO_ERR_INVALID, "llm_batch_step_launches: null");
+    // one step of B one-token streams first: the batch state for B, and the first step's eager
+    // launches (the kernels' LDS attributes are set outside any capture, run_batch)
+    std::vector<int32_t> prompts(B > 0 ? B : 1, 0), lens(B > 0 ? B : 1, 1), toks(B > 0 ? B : 1), cnt(B > 0 ? B : 1);
+    std::vector<uint64_t> seeds(B > 0 ? B : 1, 1);
+    if (int rc = mio_hip_llm_generate_batch(m, prompts.data(), lens.data(), B, 1, 0.0f, seeds.data(), -1, -1, -1, -1,
+                                            1, toks.data(), cnt.data()))
+        return rc;
+    hipStream_t s = m->d->stream;
+    MIO_HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    issue_batch_steps(m, 1, false);
+    hipGraph_t g = nullptr;
+    hipError_t e = hipStreamEndCapture(s, &g);
+    size_t nn = 0;
+    int kernels = 0;
+    if (e == hipSuccess) e = hipGraphGetNodes(g, nullptr, &nn);
+    std::vector<hipGraphNode_t> nodes(nn);
+    if (e == hipSuccess && nn) e = hipGraphGetNodes(g, nodes.data(), &nn);
+    for (size_t i = 0; i < nn && e == hipSuccess; ++i) {
+        hipGraphNodeType ty;
+        if ((e = hipGraphNodeGetType(nodes[i], &ty)) == hipSuccess && ty == hipGraphNodeTypeKernel) ++kernels;
+    }
+    if (g) hipGraphDestroy(g);
+    MIO_HIP_CHECK(e);
+    *n = kernels;
     return MIO_OK;
 }

@@ -278,6 +278,7 @@ int upload_layer(const Load &ld, mio_hip_llm *m, int i) {
                     MIO_ERR_UNSUPPORTED, "llm_load: layer %d (short conv) shapes / quant families not supported", i);
         m->has_conv = true;
         m->layers.push_back(L);
+        m->gate_repacked.push_back(mio::repacks_to_q8_0(g.tensor(p + "ffn_gate.weight")->type));
         return MIO_OK;
     }
     if (D.qk_norm) {
@@ -319,6 +320,7 @@ int upload_layer(const Load &ld, mio_hip_llm *m, int i) {
                 "llm_load: layer %d: attn_v %s beside attn_q %s has no kernel", i, mio::ggml_type_name(L.wv.type),
                 mio::ggml_type_name(L.wq.type));
     m->layers.push_back(L);
+    m->gate_repacked.push_back(mio::repacks_to_q8_0(g.tensor(p + "ffn_gate.weight")->type));
     return MIO_OK;
 }
 

@@ -39,6 +39,8 @@ struct mio_hip_llm {
     mio::LlmDims dims{};
     int n_layer = 0;
     std::vector<mio::LayerW> layers;
+    // per layer: ffn_gate is stored as a type that runs repacked to Q8_0 (Q5_0 / Q4_0), not as Q8_0
+    std::vector<char> gate_repacked;
     mio::QMat tok{}, lm{};
     float *out_norm = nullptr;
     _Float16 *kc = nullptr, *vc = nullptr;

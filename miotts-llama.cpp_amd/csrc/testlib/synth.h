@@ -34,10 +34,12 @@ struct SynthLlmCfg {
     int n_vocab = 13312, n_ctx = 4096;
     float rope_base = 10000.f, rms_eps = 1e-6f, w_std = 0.02f;
     // 8 = all Q8_0; 15 = Q4_K_M mix (Q4_K + Q6_K); 17 = Q5_K_M mix (Q5_K + Q6_K); 16 = Q5_K_S (Q5_K,
-    // Q6_K output); 2 = Q4_0; 30 = all BF16
+    // Q6_K output); 18 = MOSTLY_Q6_K (Q6_K for every matrix, token_embd / output and the lfm2
+    // in_proj / out_proj included); 2 = Q4_0; 30 = all BF16
     int qtype = 8;
     // llama-quantize's fallback for rows whose length is not a multiple of 256: Q4_K -> Q5_0,
-    // Q6_K -> Q8_0 (llama-quant.cpp); Q4_K_M files of the 0.1B model (n_embd 576) carry them
+    // Q6_K -> Q8_0 (llama-quant.cpp); Q4_K_M files of the 0.1B model (n_embd 576) carry them, and
+    // its Q6_K file is Q8_0 but for ffn_down (K = 1536)
     bool kq_fallback = true;
     bool tied = true;
     bool qkv_bias = false;  // attn_{q,k,v}.bias tensors (qwen2)
@@ -62,6 +64,9 @@ SynthLlmCfg synth_llm_preset(int preset);
 // null, or why the writer refuses the configuration
 const char *synth_llm_check(const SynthLlmCfg &cfg);
 bool synth_write_llm(const std::string &path, const SynthLlmCfg &cfg);
+// whether `qtype` is a recipe of SynthLlmCfg::qtype (mio_synth_llm_gguf_as writes any preset's
+// shape with any of them; the presets themselves stay as numbered above)
+bool synth_llm_qtype_known(int qtype);
 // Token ids of the synthetic vocabulary.
 constexpr int kSynthTokStartOfText = 256, kSynthTokImStart = 257, kSynthTokImEnd = 258,
               kSynthTokEndOfText = 259, kSynthTokSpeech0 = 260, kSynthNumSpeech = 12800;

@@ -24,3 +24,14 @@ extern "C" int mio_synth_llm_gguf(const char *path, int preset, uint64_t seed) {
     MIO_REQUIRE(mio::synth_write_llm(path, c), MIO_ERR_IO, "synth_llm: cannot write %s", path);
     return MIO_OK;
 }
+
+extern "C" int mio_synth_llm_gguf_as(const char *path, int preset, int qtype, uint64_t seed) {
+    MIO_REQUIRE(path && preset >= 0 && preset < mio::kSynthLlmPresets, MIO_ERR_INVALID, "synth_llm_as: bad args");
+    MIO_REQUIRE(mio::synth_llm_qtype_known(qtype), MIO_ERR_INVALID, "synth_llm_as: unknown recipe %d", qtype);
+    mio::SynthLlmCfg c = mio::synth_llm_preset(preset);
+    c.qtype = qtype;
+    c.seed = seed;
+    MIO_REQUIRE(!mio::synth_llm_check(c), MIO_ERR_INVALID, "synth_llm_as: %s", mio::synth_llm_check(c));
+    MIO_REQUIRE(mio::synth_write_llm(path, c), MIO_ERR_IO, "synth_llm_as: cannot write %s", path);
+    return MIO_OK;
+}

@@ -1,7 +1,8 @@
 // Synthetic LLM GGUF writer (see synth.h). Tensor names / KV keys follow llama.cpp's
 // GGUF conventions; quant types follow llama.cpp's Q4_K_M recipe: Q4_K everywhere,
 // Q6_K for attn_v / ffn_down on "use_more_bits" layers and for the (tied) output. Q5_K_M is the
-// same recipe with Q5_K for Q4_K; Q5_K_S has Q5_K everywhere and a Q6_K output.
+// same recipe with Q5_K for Q4_K; Q5_K_S has Q5_K everywhere and a Q6_K output. MOSTLY_Q6_K is
+// Q6_K for every matrix, the embedding and the output included.
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -109,6 +110,10 @@ SynthLlmCfg synth_llm_preset(int p) {
     return c;
 }
 
+bool synth_llm_qtype_known(int q) {
+    return q == 8 || q == 15 || q == 16 || q == 17 || q == 18 || q == 2 || q == 30;
+}
+
 const char *synth_llm_check(const SynthLlmCfg &c) {
     // llama-quantize turns Q5_K rows that are not whole 256-element superblocks into Q5_1, which
     // the loader refuses: such a file would be of no use
@@ -152,9 +157,9 @@ bool synth_write_llm(const std::string &path, const SynthLlmCfg &c) {
     const bool lfm2 = a == "lfm2";
     w.kv_str("general.architecture", a);
     w.kv_str("general.name", c.name);
-    // llama_ftype: 7 MOSTLY_Q8_0, 15 MOSTLY_Q4_K_M, 16 MOSTLY_Q5_K_S, 17 MOSTLY_Q5_K_M, 2 MOSTLY_Q4_0,
-    // 32 MOSTLY_BF16
-    const bool kmix = c.qtype == 15 || c.qtype == 16 || c.qtype == 17;
+    // llama_ftype: 7 MOSTLY_Q8_0, 15 MOSTLY_Q4_K_M, 16 MOSTLY_Q5_K_S, 17 MOSTLY_Q5_K_M, 18 MOSTLY_Q6_K,
+    // 2 MOSTLY_Q4_0, 32 MOSTLY_BF16
+    const bool kmix = c.qtype == 15 || c.qtype == 16 || c.qtype == 17 || c.qtype == 18;
     w.kv_u32("general.file_type", kmix ? c.qtype : (c.qtype == 2 ? 2 : (c.qtype == 30 ? 32 : 7)));
     w.kv_u32(a + ".context_length", c.n_ctx);
     w.kv_u32(a + ".embedding_length", c.n_embd);
@@ -204,8 +209,9 @@ bool synth_write_llm(const std::string &path, const SynthLlmCfg &c) {
         return kmix ? k_mix : (c.qtype == 2 ? q4 : (c.qtype == 30 ? (uint32_t)GGML_BF16 : GGML_Q8_0));
     };
     // K-quant mixes: base everywhere, `more` for attn_v / ffn_down on use_more_bits layers (the
-    // _S mix has none), Q6_K for the output matrix (the tied embedding is one)
-    const uint32_t kbase = c.qtype == 15 ? GGML_Q4_K : GGML_Q5_K;
+    // _S mix has none), Q6_K for the output matrix (the tied embedding is one). MOSTLY_Q6_K has
+    // Q6_K as its base, so every matrix is one.
+    const uint32_t kbase = c.qtype == 15 ? GGML_Q4_K : (c.qtype == 18 ? GGML_Q6_K : GGML_Q5_K);
     const uint32_t base = pick(kbase, GGML_Q4_0), more = pick(c.qtype == 16 ? kbase : GGML_Q6_K, GGML_Q4_0);
     const uint32_t outp = pick(GGML_Q6_K, GGML_Q4_0);
     const int q_dim = c.n_head * c.head_dim, kv_dim = c.n_head_kv * c.head_dim;

@@ -121,6 +121,7 @@ def _declare(L: ctypes.CDLL) -> None:
         "mio_synth_codec_gguf": (c_int, [ctypes.c_char_p, c_int, ctypes.c_uint64]),
         "mio_synth_voice_gguf": (c_int, [ctypes.c_char_p, ctypes.c_uint64]),
         "mio_synth_llm_gguf": (c_int, [ctypes.c_char_p, c_int, ctypes.c_uint64]),
+        "mio_synth_llm_gguf_as": (c_int, [ctypes.c_char_p, c_int, c_int, ctypes.c_uint64]),
         "mio_hip_llm_load": (c_int, [_vp, ctypes.c_char_p, c_int, ctypes.POINTER(_vp)]),
         "mio_hip_llm_free": (None, [_vp]),
         "mio_normalize_tts_text": (c_int, [ctypes.c_char_p, _vp, c_int, ctypes.POINTER(c_int)]),
@@ -142,6 +143,7 @@ def _declare(L: ctypes.CDLL) -> None:
         "mio_hip_llm_steps_issued": (c_int, [_vp, ctypes.POINTER(c_int)]),
         "mio_hip_llm_tail": (c_int, [_vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_float)]),
         "mio_hip_llm_step_kinds": (c_int, [_vp, _vp, c_int, ctypes.POINTER(c_int)]),
+        "mio_hip_llm_batch_step_launches": (c_int, [_vp, c_int, ctypes.POINTER(c_int)]),
         "mio_hip_llm_conv_ring": (c_int, [_vp, c_int, _vp, c_int]),
         "mio_hip_llm_eval_layers": (c_int, [_vp, ctypes.c_int32, c_int, _vp, _vp]),
         "mio_hip_llm_kv_rows": (c_int, [_vp, c_int, c_int, _vp, _vp]),
@@ -502,6 +504,13 @@ def synth_llm(path: str, preset: int = 0, seed: int = 1) -> str:
     return path
 
 
+def synth_llm_as(path: str, preset: int, qtype: int, seed: int = 1) -> str:
+    """Preset `preset`'s shape, arch and seed rule written with the recipe `qtype` (SynthLlmCfg's
+    numbering: 8, 15, 16, 17, 18 = MOSTLY_Q6_K, 2, 30)."""
+    check(lib().mio_synth_llm_gguf_as(path.encode(), preset, qtype, seed))
+    return path
+
+
 class Llm:
     """HIP LLM decode (mirror of the llama.cpp calls in test-to-speech.cpp:44-196)."""
 
@@ -662,6 +671,12 @@ class Llm:
         k = np.zeros(n.value, np.int32)
         check(lib().mio_hip_llm_step_kinds(self.h, _ptr(k), n.value, ctypes.byref(n)))
         return [int(v) for v in k]
+
+    def batch_step_launches(self, B: int) -> int:
+        """Kernel launches one batched decode step of B streams issues (sampler chain off)."""
+        n = ctypes.c_int(0)
+        check(lib().mio_hip_llm_batch_step_launches(self.h, B, ctypes.byref(n)))
+        return n.value
 
     def conv_ring(self, il: int, ring=None):
         """lfm2 short-conv state of layer il, [4, n_embd] (slot p & 3 = B*X of position p);
