@@ -124,6 +124,17 @@ template <int CTRL, int RM = 0xF>
 __device__ __forceinline__ float dpp_f(float v) {
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, RM, 0xF, false));
 }
+// A pure lane permutation (quad_perm, row_newbcast: every source lane exists): no `old` value,
+// so no register is zeroed in front of the move.
+template <int CTRL>
+__device__ __forceinline__ int dpp_perm(int v) {
+    return __builtin_amdgcn_mov_dpp(v, CTRL, 0xF, 0xF, true);
+}
+// the value of lane J of this lane's 16-lane row (row_newbcast)
+template <int J>
+__device__ __forceinline__ float row_lane(float v) {
+    return __int_as_float(dpp_perm<0x150 + J>(__float_as_int(v)));
+}
 constexpr int ROW_SHR1 = 0x111, ROW_SHR2 = 0x112, ROW_SHR4 = 0x114, ROW_SHR8 = 0x118;
 constexpr int ROW_BCAST15 = 0x142, ROW_BCAST31 = 0x143;
 
@@ -794,10 +805,16 @@ __device__ __forceinline__ float dot_frag(const Frag &f, const ALane &al, int K,
     if constexpr (T == 12 || T == 13) {
         const int jj = (lane & 7) >> 1;
         uint4 h;  // the superblock header {d|dmin, scale/min words} from the quad's four dwords
-        h.x = (uint32_t)dpp_i<0x00>((int)f.c);
-        h.y = (uint32_t)dpp_i<0x55>((int)f.c);
-        h.z = (uint32_t)dpp_i<0xAA>((int)f.c);
-        h.w = (uint32_t)dpp_i<0xFF>((int)f.c);
+        // Q4_K: broadcasts without an `old` operand (four zeroing moves less per unit). Q5_K keeps
+        // the zeroed form: without it k_pf_ffn_in<6, 13, 0> spills one more dword.
+        auto bc = [&]<int CTRL>() {
+            if constexpr (T == 12) return (uint32_t)dpp_perm<CTRL>((int)f.c);
+            else return (uint32_t)dpp_i<CTRL>((int)f.c);
+        };
+        h.x = bc.template operator()<0x00>();
+        h.y = bc.template operator()<0x55>();
+        h.z = bc.template operator()<0xAA>();
+        h.w = bc.template operator()<0xFF>();
         const uint32_t wlo = jj < 2 ? h.y : (jj == 2 ? h.z : h.w);
         const uint32_t whi = jj < 2 ? h.z : h.w;
         const uint32_t F = __builtin_amdgcn_alignbit(whi, wlo, (24 * jj) & 31);
@@ -1303,12 +1320,15 @@ __device__ __forceinline__ void wait_count(int *c, int target, int *flag) {
     }
     __hip_atomic_store(f, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-__device__ __forceinline__ float4 ld4_sc1(const float *base, uint32_t off) {
-    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc(base, 0x7FFFFFF0u), off, 0, 16);
+// off: per-lane byte offset, soff: wave-uniform byte offset, bytes: the descriptor's size (0: every
+// lane is out of range and reads 0)
+__device__ __forceinline__ float4 ld4_sc1(const float *base, uint32_t off, uint32_t soff = 0,
+                                          uint32_t bytes = 0x7FFFFFF0u) {
+    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc(base, bytes), off, soff, 16);
     return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
 }
-__device__ __forceinline__ float2 ld2_sc1(const float *base, uint32_t off) {
-    const auto v = __builtin_amdgcn_raw_buffer_load_b64(rsrc(base, 0x7FFFFFF0u), off, 0, 16);
+__device__ __forceinline__ float2 ld2_sc1(const float *base, uint32_t off, uint32_t soff = 0) {
+    const auto v = __builtin_amdgcn_raw_buffer_load_b64(rsrc(base, 0x7FFFFFF0u), off, soff, 16);
     return make_float2(__uint_as_float(v[0]), __uint_as_float(v[1]));
 }
 
@@ -1316,42 +1336,52 @@ __device__ __forceinline__ float2 ld2_sc1(const float *base, uint32_t off) {
 // dd .. dd+3 of one head whose record array starts at element `head` of the wave-uniform base
 // `part` (sc1 loads: records other workgroups of the launch wrote): 8 chunks' loads in flight
 // per batch; a missing chunk of a batch is {m = -inf, l = 0, O = 0}, which leaves the max and
-// the sums unchanged (only real chunks are loaded: every vector load instruction costs the
-// CU's address path the same, used or not). The float order does not depend on which
+// the sums unchanged (only real chunks' records are read from memory: a missing chunk's load is
+// out of its descriptor's range). The float order does not depend on which
 // workgroup merges, so every path's outputs are the same bits.
 // (r06 A/B: issuing the next batch's loads before merging the current one doubles the
 // batch registers; k_layer_att went from 65 to 136-160 VGPRs, its roles no longer co-reside,
 // and the step lost 9 %: not kept.)
+// The instruction stream (one wave merges alone in the flagship shape): a head's outputs sit in
+// whole 16-lane rows (hd / 4 = 16 or 32 lanes, all active), and every lane of a row needs the
+// same 8 (m, l) pairs and weights per batch. Lane 8k + j fetches chunk c0 + j's pair with ONE
+// load and evaluates ONE expf(m_j - mb); the batch maximum is a DPP all-reduce (max is exact in
+// any order) and w_j, l_j reach the row's lanes by row_newbcast into the same multiply-adds in
+// the same order. The 8 record loads are branch-free: the chunk's offset (c0 + j) * rec is the
+// scalar offset (no address VALU, no address register per load), and a missing chunk's
+// descriptor has 0 bytes, so its load returns 0 without touching memory.
 __device__ __forceinline__ float4 merge_out4(const float *part, uint32_t head, int nch, int rec, int hd, int dd) {
     float M = -INFINITY, L = 0.0f;
     float4 O = make_float4(0.f, 0.f, 0.f, 0.f);
     constexpr int CB = 8;  // chunks per batch of loads
+    const int j8 = MIO_TIDX & (CB - 1);
+    const uint32_t mlo = (head + (uint32_t)(j8 * rec + hd)) * 4u, oo = (head + (uint32_t)dd) * 4u;
     for (int c0 = 0; c0 < nch; c0 += CB) {
-        float2 ml[CB];
+        const uint32_t sb = (uint32_t)(c0 * rec) * 4u;
+        const bool has = c0 + j8 < nch;
+        // past nch: an offset outside the descriptor (reads 0, no access)
+        const float2 ml = ld2_sc1(part, has ? mlo : 0x80000000u, sb);
         float4 oc[CB];
 #pragma unroll
-        for (int j = 0; j < CB; ++j) {
-            const int c = c0 + j;
-            if (c < nch) {
-                ml[j] = ld2_sc1(part, (head + (uint32_t)(c * rec + hd)) * 4u);
-                oc[j] = ld4_sc1(part, (head + (uint32_t)(c * rec + dd)) * 4u);
-            } else {
-                ml[j] = make_float2(-INFINITY, 0.0f);
-                oc[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-        }
-        float mb = M;
-#pragma unroll
-        for (int j = 0; j < CB; ++j) mb = fmaxf(mb, ml[j].x);
+        for (int j = 0; j < CB; ++j)
+            oc[j] = ld4_sc1(part, oo, sb + (uint32_t)(j * rec) * 4u, c0 + j < nch ? 0x7FFFFFF0u : 0u);
+        const float m = has ? ml.x : -INFINITY;
+        const float mb = fmaxf(M, group8_max(m));
         const float a = M == -INFINITY ? 0.0f : expf(M - mb);
+        const float wl = has ? expf(m - mb) : 0.0f;
         L *= a;
         O.x *= a, O.y *= a, O.z *= a, O.w *= a;
-#pragma unroll
-        for (int j = 0; j < CB; ++j) {
-            const float w = c0 + j < nch ? expf(ml[j].x - mb) : 0.0f;
-            L += w * ml[j].y;
-            O.x += w * oc[j].x, O.y += w * oc[j].y, O.z += w * oc[j].z, O.w += w * oc[j].w;
-        }
+        auto add = [&]<int J>() {
+            const float w = row_lane<J>(wl);
+            L += w * row_lane<J>(ml.y);
+            // keeps L out of the packed pairs: O's (x, y), (z, w) pair up in the loads' own
+            // registers, where a pair with L is assembled by register moves
+            asm("" : "+v"(L));
+            O.x += w * oc[J].x, O.y += w * oc[J].y, O.z += w * oc[J].z, O.w += w * oc[J].w;
+        };
+        [&]<int... J>(std::integer_sequence<int, J...>) {
+            (add.template operator()<J>(), ...);
+        }(std::make_integer_sequence<int, CB>{});
         M = mb;
     }
     return make_float4(O.x / L, O.y / L, O.z / L, O.w / L);
