@@ -18,6 +18,14 @@ int mio_hip_debug_matvec(mio_hip_device *d, uint32_t type, const void *gguf_rows
 /* The same with the gate|up launch's row pairs and epilogue: y = silu(Wgate x) * (Wup x). */
 int mio_hip_debug_matvec_swiglu(mio_hip_device *d, uint32_t type, const void *gguf_gate, const void *gguf_up, int rows,
                                 int k, const float *x, float *y);
+/* Either of the two on the decode step's single-group row stream: every wave's share is one
+ * register group of su units (a unit = one pass of one row of one matrix; su 2, 3, 4, 6 for
+ * k <= 2048, su even with gguf_up; su 3 for 2048 < k <= 6144 without gguf_up), rows split over
+ * `grid` workgroups of 8 waves the way the launches split them. gguf_up NULL: y = W x, else
+ * the SwiGLU form. MIO_ERR_INVALID where a wave would own more than su units or no such
+ * instantiation exists. The outputs equal mio_hip_debug_matvec / _swiglu's bit for bit. */
+int mio_hip_debug_matvec_group(mio_hip_device *d, uint32_t type, const void *gguf_gate, const void *gguf_up, int rows,
+                               int k, int su, int grid, const float *x, float *y);
 int mio_quantize_rows(uint32_t type, const float *x, int rows, int k, void *out);
 /* The host dequantizer (ggml dequantize_row_* expression order) on rows of ggml blocks:
  * out[rows][k] f32. */

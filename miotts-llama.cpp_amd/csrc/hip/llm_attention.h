@@ -134,8 +134,8 @@ __device__ __forceinline__ void o_consumer(const LlmDims &d, const QMat &wo, con
     asm volatile("s_barrier" ::: "memory");
     MIO_TL_MARK(b, 3);
     XRegs<NP> xr;
-    load_x<NP, 16>(b.att, nullptr, K, xr);
-    x_after_weights(xr);
+    load_x_plain<NP, 16>(b.att, K, xr);
+    x_after_weights_plain(xr);
     MIO_TL_MARK1(b);
     plain_quant(xr, K, akind(T), s, MIO_TL_DIAGSLOT(b));
     MIO_TL_MARK(b, 2);

@@ -418,6 +418,25 @@ __device__ inline void load_x(const float *x, const float *w, int K, XRegs<XV> &
     }
 }
 
+// The plain roles (no norm weight: O, down): x alone. load_x with w == nullptr still issues one
+// empty-range 16-B load per slice for the weight registers; here they are neither loaded nor
+// pinned (the run-time branch around them lost 4 %; this is the compile-time form).
+template <int XV, int XAUX = 0>
+__device__ inline void load_x_plain(const float *x, int K, XRegs<XV> &xr) {
+    const auto rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(x), 0, x ? K * 4 : 0, 0x00020000);
+#pragma unroll
+    for (int i = 0; i < XV; ++i) {
+        const int e = (MIO_TIDX + i * MT) * 4;
+        const u32x4 a = __builtin_amdgcn_raw_buffer_load_b128(rx, e * 4, 0, XAUX);
+        xr.v[i] = make_float4(__uint_as_float(a.x), __uint_as_float(a.y), __uint_as_float(a.z), __uint_as_float(a.w));
+    }
+}
+template <int XV>
+__device__ __forceinline__ void x_after_weights_plain(XRegs<XV> &xr) {
+#pragma unroll
+    for (int i = 0; i < XV; ++i) asm volatile("" : "+v"(xr.v[i].x), "+v"(xr.v[i].y), "+v"(xr.v[i].z), "+v"(xr.v[i].w));
+}
+
 // Activation kind of a weight type (ggml's vec_dot_type): 0 Q8_0 (Q8_0 weights), 1 Q8_K
 // (Q4_K / Q5_K / Q6_K), 2 BF16 (BF16 weights: the activation rounded to bf16, ggml_fp32_to_bf16).
 __host__ __device__ constexpr int akind(int T) { return T == 30 ? 2 : (T == 8 ? 0 : 1); }
@@ -795,13 +814,19 @@ __device__ __forceinline__ ALane load_alane(const ActL &a, int K, int pass) {
     return r;
 }
 
-// This lane's partial of the row dot for one pass. K-quants: the per-superblock integer
-// sums are reduced exactly over the superblock's 8 lanes (ggml vec_dot semantics) and the
-// superblock's float term is valid in lane 8k+7; Q8_0: every lane holds one block's term.
-// Lanes whose superblock / block lies past K have zero codes and zero scales -> 0.
+// The per-lane part of a K-quant unit's row dot: the scaled integer terms of the lane's 32
+// weights (isum; Q4_K / Q5_K also imin, the mins against the activation's bsums) and the
+// superblock's raw float factors hd (Q4_K / Q5_K: the header's d | dmin f16 pair, Q6_K: d).
+// No cross-lane sum: dot_frag reduces one unit's terms, pair_term two units' together.
+struct LaneTerms {
+    int isum, imin;
+    uint32_t hd;
+};
 template <int T>
-__device__ __forceinline__ float dot_frag(const Frag &f, const ALane &al, int K, int pass) {
+__device__ __forceinline__ LaneTerms lane_terms(const Frag &f, const ALane &al) {
+    static_assert(T == 12 || T == 13 || T == 14, "K-quants");
     const int lane = MIO_TIDX & 63;
+    LaneTerms t;
     if constexpr (T == 12 || T == 13) {
         const int jj = (lane & 7) >> 1;
         uint4 h;  // the superblock header {d|dmin, scale/min words} from the quad's four dwords
@@ -838,16 +863,10 @@ __device__ __forceinline__ float dot_frag(const Frag &f, const ALane &al, int K,
         dhi = sdot4(hi(f.a.y, f.b.y), al.hi.y, dhi);
         dhi = sdot4(hi(f.a.z, f.b.z), al.hi.z, dhi);
         dhi = sdot4(hi(f.a.w, f.b.w), al.hi.w, dhi);
-        int isum = __mul24(sc0, dlo) + __mul24(sc1, dhi);
-        int imin = __mul24(m0, al.b0) + __mul24(m1, al.b1);
-        isum = sum8_i(isum);
-        imin = sum8_i(imin);
-        const float d = h2f(h.x & 0xFFFF) * al.d;
-        const float dmin = h2f(h.x >> 16) * al.d;
-        float v = d * (float)isum;
-        v = v - dmin * (float)imin;
-        return pass * 8 + (lane >> 3) < (K >> 8) ? v : 0.0f;
-    } else if constexpr (T == 14) {
+        t.isum = __mul24(sc0, dlo) + __mul24(sc1, dhi);
+        t.imin = __mul24(m0, al.b0) + __mul24(m1, al.b1);
+        t.hd = h.x;
+    } else {
         // high 2 bits of the low-nibble codes sit at bit 2*gl of each qh byte, of the
         // high-nibble codes at bit 2*gl+4 (gl = (lane&3)>>1); move them to bits 4-5
         const int shl = 2 * ((lane & 3) >> 1);
@@ -863,10 +882,41 @@ __device__ __forceinline__ float dot_frag(const Frag &f, const ALane &al, int K,
         dhi = sdot4(hi(f.a.z, f.b.z), al.hi.z, dhi);
         dhi = sdot4(hi(f.a.w, f.b.w), al.hi.w, dhi);
         const int sa = (int)(int8_t)(f.c & 0xFF), sb = (int)(int8_t)(f.c >> 8);
-        int isum = __mul24(sa, dlo - 32 * al.b0) + __mul24(sb, dhi - 32 * al.b1);
-        isum = sum8_i(isum);
-        const float d = h2f(f.e) * al.d;
-        const float v = d * (float)isum;
+        t.isum = __mul24(sa, dlo - 32 * al.b0) + __mul24(sb, dhi - 32 * al.b1);
+        t.imin = 0;
+        t.hd = f.e;
+    }
+    return t;
+}
+
+// The float term of a superblock from its exact integer sums and raw factors (ggml vec_dot
+// semantics; every caller runs these operations in this order).
+template <int T>
+__device__ __forceinline__ float sb_term(int isum, int imin, uint32_t hd, float ad) {
+    if constexpr (T == 14) {
+        const float d = h2f(hd) * ad;
+        return d * (float)isum;
+    } else {
+        const float d = h2f(hd & 0xFFFF) * ad;
+        const float dmin = h2f(hd >> 16) * ad;
+        float v = d * (float)isum;
+        v = v - dmin * (float)imin;
+        return v;
+    }
+}
+
+// This lane's partial of the row dot for one pass. K-quants: the per-superblock integer
+// sums are reduced exactly over the superblock's 8 lanes (ggml vec_dot semantics) and the
+// superblock's float term is valid in lane 8k+7; Q8_0: every lane holds one block's term.
+// Lanes whose superblock / block lies past K have zero codes and zero scales -> 0.
+template <int T>
+__device__ __forceinline__ float dot_frag(const Frag &f, const ALane &al, int K, int pass) {
+    const int lane = MIO_TIDX & 63;
+    if constexpr (T == 12 || T == 13 || T == 14) {
+        const LaneTerms t = lane_terms<T>(f, al);
+        const int isum = sum8_i(t.isum);
+        const int imin = T == 14 ? 0 : sum8_i(t.imin);
+        const float v = sb_term<T>(isum, imin, t.hd, al.d);
         return pass * 8 + (lane >> 3) < (K >> 8) ? v : 0.0f;
     } else if constexpr (T == 30) {
         // ggml_vec_dot_bf16 on the bf16-rounded activation: products of bf16 pairs are exact
@@ -909,6 +959,110 @@ template <int T>
 __device__ __forceinline__ float row_total(float acc) {
     if constexpr (T == 8 || T == 30) acc = sum8_f(acc);
     return sum_lanes7(acc);
+}
+
+// ------------------------------------------------------------------ joint row reductions
+// A register group's rows reduced together (one-pass K-quant rows, the whole share in one group).
+// Two units share every cross-lane step: after the first step of the exact 8-lane integer sums
+// (lane l + lane 7 - l, row_half_mirror) both halves of an 8-lane group hold the same four
+// partial sums, so lanes 0-3 of the group keep unit A's and lanes 4-7 unit B's, and the two
+// quad steps, the float factors and the superblock's float term run once for both. Integer
+// sums are exact in any order; the float operations per (unit, superblock) are dot_frag's.
+__device__ __forceinline__ int pair_sum8(int a, int b, bool side_b) {
+    a += dpp_perm<0x141>(a);  // row_half_mirror
+    b += dpp_perm<0x141>(b);
+    int r = side_b ? b : a;
+    r += dpp_perm<0xB1>(r);  // quad_perm [1,0,3,2]
+    r += dpp_perm<0x4E>(r);  // quad_perm [2,3,0,1]
+    return r;
+}
+// Superblock (lane >> 3)'s float term of unit A (lanes with side_b false) and of unit B (side_b
+// true), zero past K, held by all four lanes of the half group.
+template <int T>
+__device__ __forceinline__ float pair_term(const Frag &fa, const Frag &fb, const ALane &al, bool side_b, bool in_k) {
+    const LaneTerms a = lane_terms<T>(fa, al), b = lane_terms<T>(fb, al);
+    const int isum = pair_sum8(a.isum, b.isum, side_b);
+    const int imin = T == 14 ? 0 : pair_sum8(a.imin, b.imin, side_b);
+    const float v = sb_term<T>(isum, imin, side_b ? b.hd : a.hd, al.d);
+    return in_k ? v : 0.0f;
+}
+// sum_lanes7's pairing tree over the 8 superblock terms t0 .. t7 of a row, ((t7 + t6) + (t5 +
+// t4)) + ((t3 + t2) + (t1 + t0)) with operands commuted (float addition is commutative bit for
+// bit unless both operands are NaNs), for values replicated over their half groups: step 1 adds
+// the other 8-lane group of the 16-lane row (row_ror:8), steps 2 and 3 the neighbouring row and
+// the other half wave by the gfx950 permlane swaps. A swap exchanges rows (halves) between TWO
+// registers, so one swap and one add reduce two registers into one: rows 2i, 2i + 1 of
+// swapadd16(a, b) hold a's and b's sums over rows 2i and 2i + 1, the halves of swapadd32(a, b)
+// a's and b's sums over both halves.
+__device__ __forceinline__ float ror8_add(float v) {
+    return v + __int_as_float(dpp_perm<0x128>(__float_as_int(v)));
+}
+__device__ __forceinline__ float swapadd16(float a, float b) {
+    const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+    return __uint_as_float(r[1]) + __uint_as_float(r[0]);
+}
+__device__ __forceinline__ float swapadd32(float a, float b) {
+    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+    return __uint_as_float(r[1]) + __uint_as_float(r[0]);
+}
+// which (type, passes, matrices, group size) run the joint form: Q8_0 / BF16 rows, multi-pass
+// rows and one-unit groups keep the per-unit reduction; so do Q5_K and six single rows per wave,
+// whose instantiations would lose an occupancy step to the joint form's registers (k_ffn<1, 13,
+// 6, 3, 13, 3> 80 -> 81 VGPRs, k_attn_in<1, 12, 12, 6> 64 -> 65, k_attn_out<1, 14, 6> 79 -> 84)
+template <int T, int NP, int NM, int SU>
+constexpr bool joint_rows = (T == 12 || T == 14) && NP == 1 && SU >= 2 && (NM == 2 || SU <= 4);
+
+// The rows of one group F (SU one-pass units: unit u = row lo + u / NM, matrix u % NM; units
+// past the share are clamped duplicates, computed and dropped) reduced pairwise, fin(row, dot0,
+// dot1) called once with per-lane values by the lanes that hold a row.
+//   NM == 2: a pair is a row's two matrices. The swaps merge the pairs' trees, row i's totals
+//            end in the 16-lane row i (dot0 in lanes with bit 2 clear, dot1 with it set) and
+//            lane 16 i runs the epilogue, dot1 fetched from lane 16 i + 4.
+//   NM == 1: a pair is rows 2 p, 2 p + 1. Every lane ends with the pair's totals (by bit 2); row
+//            i is parked in lane i, its epilogue lane (lane i: row lo + i).
+template <int T, int NM, int SU, class Fin>
+__device__ __forceinline__ void rows_joint(const Frag (&F)[SU], const ActL &a, int K, int lo, int hi, Fin &&fin) {
+    constexpr int NPR = (SU + 1) / 2;
+    static_assert(NM == 1 || NPR <= 4, "one 16-lane row per row pair");
+    static_assert(NM == 2 || SU <= 8, "a row's parking lane and its pair side");
+    const int lane = MIO_TIDX & 63;
+    const ALane al = load_alane<T>(a, K, 0);
+    const bool side_b = (lane & 4) != 0, in_k = (lane >> 3) < (K >> 8);
+    float x[NPR];
+#pragma unroll
+    for (int p = 0; p < NPR; ++p) {
+        float acc = 0.0f;
+        acc += pair_term<T>(F[2 * p], F[2 * p + 1 < SU ? 2 * p + 1 : 2 * p], al, side_b, in_k);
+        x[p] = ror8_add(acc);
+    }
+    if constexpr (NM == 2) {
+        float r;
+        if constexpr (NPR == 1) {
+            const float q = swapadd16(x[0], x[0]);
+            r = swapadd32(q, q);
+        } else if constexpr (NPR == 2) {
+            const float q = swapadd16(x[0], x[1]);
+            r = swapadd32(q, q);
+        } else {
+            const float q = swapadd16(x[0], x[1]), q2 = swapadd16(x[2], x[NPR - 1]);
+            r = swapadd32(q, q2);
+        }
+        const float r1 = dpp_f<0x104>(r);  // row_shl:4
+        if ((lane & 15) == 0 && (lane >> 4) < hi - lo) fin(lo + (lane >> 4), r, r1);
+    } else {
+        float p0 = 0.0f;
+#pragma unroll
+        for (int p = 0; p < NPR; ++p) {
+            const float q = swapadd16(x[p], x[p]);
+            const float r = swapadd32(q, q), rs = dpp_f<0x104>(r);  // rs: the other side's total
+#pragma unroll
+            for (int u = 2 * p; u < 2 * p + 2 && u < SU; ++u) {
+                const float v = ((u >> 2) & 1) == (u & 1) ? r : rs;  // lane u's side is bit 2 of u
+                p0 = u == 0 ? v : (lane == u ? v : p0);
+            }
+        }
+        if (lane < hi - lo) fin(lo + lane, p0, 0.0f);
+    }
 }
 
 // ------------------------------------------------------------------ streaming rows
@@ -1020,11 +1174,19 @@ __device__ __forceinline__ void stream_rows(const QMat W0, const QMat W1, int lo
 // 64 rows are parked (only a wave whose share is not one register group, SU == 0, can own more
 // than 64). The epilogue's arithmetic is per lane what it was per row on wave-uniform values
 // (the same instructions, the same bits), and its store is one instruction for all the rows.
+// One-pass Q4_K / Q6_K groups (joint_rows) reduce their rows together instead (rows_joint): a
+// row pair's epilogue lane is then lane 16 i, not lane i; a single matrix's stays lane i.
 template <int T, int NP, int NM, int SU = 0, int AUX = MIO_WEIGHT_AUX, class Fin>
 __device__ __forceinline__ void stream_rows_lanes(const QMat W0, const QMat W1, int lo, int hi,
                                                   Frag (&A)[Cfg<NP, SU>::U], Frag (&B)[Cfg<NP, SU>::U], const ActL &a,
                                                   Fin &&fin, int split = INT_MAX, unsigned long long *trace = nullptr) {
     const int lane = MIO_TIDX & 63;
+    if constexpr (joint_rows<T, NP, NM, SU>) {
+        if (hi <= lo) return;
+        rows_joint<T, NM, SU>(A, a, W0.k, lo, hi, fin);
+        if (trace && blockIdx.x == 0 && MIO_TIDX == 0) trace[3] = __builtin_readcyclecounter();
+        return;
+    }
     // a share of one register group holds at most SU / (NM NP) rows: with one row there is
     // nothing to gather, lane 0 (row lo, its own residual value) runs the epilogue as it comes
     if constexpr (SU != 0 && SU / (NM * NP) == 1) {

@@ -292,6 +292,10 @@ void launch_attn_in(const LlmDims &d, const LayerW &L, int il, const QMat &tok_e
 // y = W x with x re-quantized to the vec_dot_type (parity test of the matvec kernels); with
 // up: y = silu(W x) * (up x), the gate|up launch's row pairs and epilogue.
 void launch_debug_matvec(const QMat &W, const QMat *up, const float *x, float *y, int n_wg, hipStream_t s);
+// The same on the single-group row stream of su units per wave over `grid` workgroups (the form
+// the decode step launches); false: no such instantiation, or a wave would own more than su units.
+bool launch_debug_matvec_group(const QMat &W, const QMat *up, const float *x, float *y, int su, int grid,
+                               hipStream_t s);
 // The decode prologue's activation quantizer for weight type `type` on x[K] (RMSNorm with w when
 // given; sc1: the hand-off load path): the LDS record, debug_act_record_bytes(K) bytes, to out.
 size_t debug_act_record_bytes(int K);

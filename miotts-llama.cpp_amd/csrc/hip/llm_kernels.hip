@@ -57,11 +57,11 @@ __global__ __launch_bounds__(MT) void k_attn_out(LlmDims d, QMat wo, LlmBuffers 
     wave_range(d, wo.rows, lo, hi);
     const uint32_t dn = done_issue(b);
     XRegs<NP> xr;
-    load_x(b.att, nullptr, K, xr);
+    load_x_plain(b.att, K, xr);
     const float xres = load_resid(b.x, lo, hi);
     Frag ga[Cfg<NP, SU>::U], gb[Cfg<NP, SU>::U];
     load_first<T, NP, 1, SU, MIO_SMALL_AUX>(wo, wo, lo, hi, ga, gb);
-    x_after_weights(xr);
+    x_after_weights_plain(xr);
     if (done_now(dn)) return;
     MIO_TRACE(b, 1);
     MIO_TL_MARK1(b);
@@ -174,13 +174,13 @@ __global__ __launch_bounds__(MT) void k_ffn_down(LlmDims d, QMat down, LlmBuffer
     const Smem s = carve(smem, K);
     const uint32_t dn = done_issue(b);
     XRegs<NP> xr;
-    load_x(b.h, nullptr, K, xr);
+    load_x_plain(b.h, K, xr);
     int lo, hi;
     wave_range(d, down.rows, lo, hi);
     const float xres = load_resid(b.x, lo, hi);
     Frag ga[Cfg<NP, SU>::U], gb[Cfg<NP, SU>::U];
     load_first<T, NP, 1, SU>(down, down, lo, hi, ga, gb);
-    x_after_weights(xr);
+    x_after_weights_plain(xr);
     if (done_now(dn)) return;
     MIO_TRACE(b, 1);
     MIO_TL_MARK1(b);
@@ -279,8 +279,8 @@ __global__ __launch_bounds__(MT) void k_ffn(LlmDims d, const float *norm_w, QMat
         asm volatile("s_barrier" ::: "memory");
         MIO_TL_MARK(b, 3);
         XRegs<NPD> xr;
-        load_x<NPD, 16>(b.h, nullptr, K, xr);
-        x_after_weights(xr);
+        load_x_plain<NPD, 16>(b.h, K, xr);
+        x_after_weights_plain(xr);
         MIO_TL_MARK1(b);
         plain_quant(xr, K, akind(TD), s, MIO_TL_DIAGSLOT(b));
         MIO_TL_MARK(b, 2);

@@ -12,9 +12,10 @@
 #include "quant.h"
 
 namespace {
-// y = W x, or with gguf_up y = silu(W x) * (up x), on the decode step's streaming matvec engine
+// y = W x, or with gguf_up y = silu(W x) * (up x), on the decode step's streaming matvec engine;
+// su > 0: on its single-group row stream of su units per wave over `grid` workgroups
 int debug_matvec(mio_hip_device *d, uint32_t type, const void *gguf_rows, const void *gguf_up, int rows, int k,
-                 const float *x, float *y) {
+                 const float *x, float *y, int su = 0, int grid = 0) {
     MIO_REQUIRE(d && gguf_rows && x && y && rows > 0 && k > 0, MIO_ERR_INVALID, "debug_matvec: bad args");
     MIO_REQUIRE(type == mio::GGML_Q8_0 || type == mio::GGML_Q4_K || type == mio::GGML_Q5_K ||
                     type == mio::GGML_Q6_K || type == mio::GGML_BF16 || (!gguf_up && mio::repacks_to_q8_0(type)),
@@ -47,7 +48,15 @@ int debug_matvec(mio_hip_device *d, uint32_t type, const void *gguf_rows, const 
         return mio::QMat{(int)type, rows, k, base + L.off[0], base + L.off[1], base + L.off[2], base + L.off[3]};
     };
     const mio::QMat q = qm(dw), up = qm(dw + (gguf_up ? L.bytes : 0));
-    mio::launch_debug_matvec(q, gguf_up ? &up : nullptr, dx, dy, d->n_cu > 0 ? d->n_cu : 256, d->stream);
+    bool launched = true;
+    if (su > 0)
+        launched = mio::launch_debug_matvec_group(q, gguf_up ? &up : nullptr, dx, dy, su, grid, d->stream);
+    else
+        mio::launch_debug_matvec(q, gguf_up ? &up : nullptr, dx, dy, d->n_cu > 0 ? d->n_cu : 256, d->stream);
+    if (!launched) {
+        hipFree(dw), hipFree(dx), hipFree(dy);
+        MIO_REQUIRE(false, MIO_ERR_INVALID, "debug_matvec_group: su %d / grid %d for %d rows, k %d", su, grid, rows, k);
+    }
     hipError_t e = hipStreamSynchronize(d->stream);
     if (e == hipSuccess) e = hipMemcpy(y, dy, (size_t)rows * 4, hipMemcpyDeviceToHost);
     hipFree(dw), hipFree(dx), hipFree(dy);
@@ -65,6 +74,16 @@ extern "C" int mio_hip_debug_matvec_swiglu(mio_hip_device *d, uint32_t type, con
                                            const void *gguf_up, int rows, int k, const float *x, float *y) {
     MIO_REQUIRE(gguf_up, MIO_ERR_INVALID, "debug_matvec_swiglu: bad args");
     return debug_matvec(d, type, gguf_gate, gguf_up, rows, k, x, y);
+}
+
+extern "C" int mio_hip_debug_matvec_group(mio_hip_device *d, uint32_t type, const void *gguf_gate,
+                                          const void *gguf_up, int rows, int k, int su, int grid, const float *x,
+                                          float *y) {
+    MIO_REQUIRE(su > 0 && grid > 0 && grid <= 4096, MIO_ERR_INVALID, "debug_matvec_group: su %d / grid %d", su, grid);
+    MIO_REQUIRE(type == mio::GGML_Q8_0 || type == mio::GGML_Q4_K || type == mio::GGML_Q5_K ||
+                    type == mio::GGML_Q6_K || type == mio::GGML_BF16,
+                MIO_ERR_UNSUPPORTED, "debug_matvec_group: type %u", type);
+    return debug_matvec(d, type, gguf_gate, gguf_up, rows, k, x, y, su, grid);
 }
 
 extern "C" int mio_hip_debug_act_quant(mio_hip_device *d, uint32_t type, const float *x, const float *w, int k,

@@ -156,6 +156,7 @@ def _declare(L: ctypes.CDLL) -> None:
                                                    _i32p, _i32p, _vp]),
         "mio_hip_debug_matvec": (c_int, [_vp, ctypes.c_uint32, _vp, c_int, c_int, _vp, _vp]),
         "mio_hip_debug_matvec_swiglu": (c_int, [_vp, ctypes.c_uint32, _vp, _vp, c_int, c_int, _vp, _vp]),
+        "mio_hip_debug_matvec_group": (c_int, [_vp, ctypes.c_uint32, _vp, _vp, c_int, c_int, c_int, c_int, _vp, _vp]),
         "mio_hip_debug_act_quant": (c_int, [_vp, ctypes.c_uint32, _vp, _vp, c_int, ctypes.c_float, c_int, _vp, _vp,
                                             _vp]),
         "mio_quantize_rows": (c_int, [ctypes.c_uint32, _vp, c_int, c_int, _vp]),
@@ -756,6 +757,19 @@ def debug_matvec_swiglu(dev: Device, qtype: int, gate_rows: np.ndarray, up_rows:
     y = np.empty(gate_rows.shape[0], np.float32)
     check(lib().mio_hip_debug_matvec_swiglu(dev.h, qtype, _ptr(gate_rows), _ptr(up_rows), gate_rows.shape[0], k,
                                             _ptr(x), _ptr(y)))
+    return y
+
+
+def debug_matvec_group(dev: Device, qtype: int, gate_rows: np.ndarray, up_rows: Optional[np.ndarray], k: int,
+                       x: np.ndarray, su: int, grid: int) -> np.ndarray:
+    """W x (up_rows None) or silu(gate x) * (up x) on the decode step's single-group row stream: su
+    units per wave over `grid` workgroups (mio_hip_debug_matvec_group)."""
+    gate_rows = np.ascontiguousarray(gate_rows)
+    up = np.ascontiguousarray(up_rows) if up_rows is not None else None
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    y = np.empty(gate_rows.shape[0], np.float32)
+    check(lib().mio_hip_debug_matvec_group(dev.h, qtype, _ptr(gate_rows), _ptr(up) if up is not None else None,
+                                           gate_rows.shape[0], k, su, grid, _ptr(x), _ptr(y)))
     return y
 
 
