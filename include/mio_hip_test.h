@@ -10,9 +10,22 @@
 extern "C" {
 #endif
 
+/* What guarded outputs of the parity entry points are filled with before a launch: quiet NaNs
+ * with a payload, so an element no thread wrote is recognisable. */
+#define MIO_DEBUG_SENTINEL_F32 0x7FC5A5A5u
+#define MIO_DEBUG_SENTINEL_F16 0x7E5Au
+
 /* Parity helpers: y[rows] = W x for a GGUF-layout quantized matrix (gguf_rows, ggml type
  * 8/12/13/14) with x re-quantized to the ggml vec_dot_type, on the GPU matvec kernels; and
- * the host quantizer used to build synthetic models (ggml block layout out). */
+ * the host quantizer used to build synthetic models (ggml block layout out).
+ * mio_hip_debug_matvec, _swiglu, _group and _mmq keep their device output between two 256-byte
+ * guard zones and fill guards and output with MIO_DEBUG_SENTINEL_F32 before the launch (mmq mode
+ * 1, whose y is in/out: the caller's values between the guards): a row no wave wrote comes back
+ * as the sentinel, and a guard zone that changed is MIO_ERR_HIP with a message naming the zone
+ * ("before row 0" / "after the last row"). tests/test_rowdot_edges_gpu.py runs them on blocks
+ * built from their fields at the integer ceilings (tests/np_rowdot.py: every code, scale and min
+ * at its maximum, d / dmin negative, -0, f16-subnormal and 65504, scales and codes of -128,
+ * single sub-blocks, random bytes) against an exact integer reference with a counted bound. */
 int mio_hip_debug_matvec(mio_hip_device *d, uint32_t type, const void *gguf_rows, int rows, int k,
                          const float *x, float *y);
 /* The same with the gate|up launch's row pairs and epilogue: y = silu(Wgate x) * (Wup x). */
@@ -81,8 +94,6 @@ int mio_hip_llm_debug_sample_chain(mio_hip_llm *m, const float *logits, const in
  * (Outputs that are also inputs - the GEMM's C, an in-place row norm, a conv residual that
  * aliases Y - carry the caller's values between the guards instead.)
  * Arguments outside a kernel's documented preconditions are refused with MIO_ERR_INVALID. */
-#define MIO_DEBUG_SENTINEL_F32 0x7FC5A5A5u
-#define MIO_DEBUG_SENTINEL_F16 0x7E5Au
 
 /* GemmArgs (csrc/hip/codec_kernels.h) field for field, plus the epilogue, the K-group count
  * (0: launch_gemm_f32 picks it and the tile order; 1, 2, 4: launch_gemm_f32_cfg(.., kg, 11))

@@ -12,6 +12,37 @@
 #include "quant.h"
 
 namespace {
+// An f32 output of n values between two 256-byte guard zones, the whole allocation filled with
+// MIO_DEBUG_SENTINEL_F32 (init != nullptr: an in/out operand's values between the guards), so
+// that a row no wave wrote comes back as the sentinel and a write outside the rows is an error.
+constexpr size_t kGuardF = 256 / 4;
+struct GuardedY {
+    float *base = nullptr;
+    size_t n = 0;
+    hipError_t make(size_t count, const float *init) {
+        n = count;
+        hipError_t e = hipMalloc(&base, (n + 2 * kGuardF) * 4);
+        if (e != hipSuccess) return e;
+        std::vector<uint32_t> fill(n + 2 * kGuardF, MIO_DEBUG_SENTINEL_F32);
+        if (init) memcpy(fill.data() + kGuardF, init, n * 4);
+        return hipMemcpy(base, fill.data(), fill.size() * 4, hipMemcpyHostToDevice);
+    }
+    float *body() const { return base + kGuardF; }
+    // download: the body into y; *zone = the guard zone that no longer holds the sentinel
+    hipError_t finish(float *y, const char **zone) const {
+        std::vector<uint32_t> all(n + 2 * kGuardF);
+        const hipError_t e = hipMemcpy(all.data(), base, all.size() * 4, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return e;
+        *zone = nullptr;
+        for (size_t i = 0; i < kGuardF; ++i) {
+            if (all[kGuardF + n + i] != MIO_DEBUG_SENTINEL_F32) *zone = "after the last row";
+            if (all[i] != MIO_DEBUG_SENTINEL_F32) *zone = "before row 0";
+        }
+        memcpy(y, all.data() + kGuardF, n * 4);
+        return hipSuccess;
+    }
+};
+
 // y = W x, or with gguf_up y = silu(W x) * (up x), on the decode step's streaming matvec engine;
 // su > 0: on its single-group row stream of su units per wave over `grid` workgroups
 int debug_matvec(mio_hip_device *d, uint32_t type, const void *gguf_rows, const void *gguf_up, int rows, int k,
@@ -38,10 +69,12 @@ int debug_matvec(mio_hip_device *d, uint32_t type, const void *gguf_rows, const 
     mio::to_split(type, gguf_rows, rows, k, host.data());
     if (gguf_up) mio::to_split(type, gguf_up, rows, k, host.data() + L.bytes);
     uint8_t *dw = nullptr;
-    float *dx = nullptr, *dy = nullptr;
+    float *dx = nullptr;
+    GuardedY out;
     MIO_HIP_CHECK(hipMalloc(&dw, L.bytes * nm));
     MIO_HIP_CHECK(hipMalloc(&dx, (size_t)k * 4));
-    MIO_HIP_CHECK(hipMalloc(&dy, (size_t)rows * 4));
+    MIO_HIP_CHECK(out.make((size_t)rows, nullptr));
+    float *dy = out.body();
     hipMemcpy(dw, host.data(), L.bytes * nm, hipMemcpyHostToDevice);
     hipMemcpy(dx, x, (size_t)k * 4, hipMemcpyHostToDevice);
     auto qm = [&](uint8_t *base) {
@@ -54,13 +87,15 @@ int debug_matvec(mio_hip_device *d, uint32_t type, const void *gguf_rows, const 
     else
         mio::launch_debug_matvec(q, gguf_up ? &up : nullptr, dx, dy, d->n_cu > 0 ? d->n_cu : 256, d->stream);
     if (!launched) {
-        hipFree(dw), hipFree(dx), hipFree(dy);
+        hipFree(dw), hipFree(dx), hipFree(out.base);
         MIO_REQUIRE(false, MIO_ERR_INVALID, "debug_matvec_group: su %d / grid %d for %d rows, k %d", su, grid, rows, k);
     }
     hipError_t e = hipStreamSynchronize(d->stream);
-    if (e == hipSuccess) e = hipMemcpy(y, dy, (size_t)rows * 4, hipMemcpyDeviceToHost);
-    hipFree(dw), hipFree(dx), hipFree(dy);
+    const char *zone = nullptr;
+    if (e == hipSuccess) e = out.finish(y, &zone);
+    hipFree(dw), hipFree(dx), hipFree(out.base);
     MIO_HIP_CHECK(e);
+    MIO_REQUIRE(!zone, MIO_ERR_HIP, "debug_matvec: the guard zone %s of y[%d] was written", zone, rows);
     return MIO_OK;
 }
 }  // namespace
@@ -134,15 +169,16 @@ extern "C" int mio_hip_debug_mmq(mio_hip_device *d, uint32_t type, const void *g
     mio::to_split(type, gguf_rows, rows, k, host.data());
     if (nm == 2) mio::to_split(type, gguf_up, rows, k, host.data() + L.bytes);
     uint8_t *dw = nullptr;
-    float *dx = nullptr, *dy = nullptr;
+    float *dx = nullptr;
     char *da = nullptr;
+    GuardedY out;
     MIO_HIP_CHECK(hipMalloc(&dw, L.bytes * nm));
     MIO_HIP_CHECK(hipMalloc(&dx, (size_t)nt * k * 4));
-    MIO_HIP_CHECK(hipMalloc(&dy, (size_t)nt * rows * 4));
+    MIO_HIP_CHECK(out.make((size_t)nt * rows, mode == 1 ? y : nullptr));  // mode 1 adds to y
+    float *dy = out.body();
     MIO_HIP_CHECK(hipMalloc(&da, (size_t)nt * mio::debug_act_bytes(k)));
     hipMemcpy(dw, host.data(), L.bytes * nm, hipMemcpyHostToDevice);
     hipMemcpy(dx, x, (size_t)nt * k * 4, hipMemcpyHostToDevice);
-    hipMemcpy(dy, y, (size_t)nt * rows * 4, hipMemcpyHostToDevice);  // mode 1 adds to y
     auto qm = [&](uint8_t *base) {
         return mio::QMat{(int)type, rows, k, base + L.off[0], base + L.off[1], base + L.off[2], base + L.off[3]};
     };
@@ -150,9 +186,11 @@ extern "C" int mio_hip_debug_mmq(mio_hip_device *d, uint32_t type, const void *g
     mio::launch_debug_mmq(q, up, mode, dx, nt, da, dy, d->stream);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
-    if (e == hipSuccess) e = hipMemcpy(y, dy, (size_t)nt * rows * 4, hipMemcpyDeviceToHost);
-    hipFree(dw), hipFree(dx), hipFree(dy), hipFree(da);
+    const char *zone = nullptr;
+    if (e == hipSuccess) e = out.finish(y, &zone);
+    hipFree(dw), hipFree(dx), hipFree(out.base), hipFree(da);
     MIO_HIP_CHECK(e);
+    MIO_REQUIRE(!zone, MIO_ERR_HIP, "debug_mmq: the guard zone %s of y[%d][%d] was written", zone, nt, rows);
     return MIO_OK;
 }
 

@@ -742,6 +742,9 @@ def dequantize_rows(qtype: int, rows_bytes: np.ndarray, k: int) -> np.ndarray:
 
 
 def debug_matvec(dev: Device, qtype: int, w_rows: np.ndarray, k: int, x: np.ndarray) -> np.ndarray:
+    """W x on the decode step's row stream (mio_hip_debug_matvec). As for debug_matvec_swiglu, _group
+    and debug_mmq, a row no wave wrote comes back as SENTINEL_F32, and a write outside the rows
+    raises (the library checks the guard zones around its output)."""
     w_rows = np.ascontiguousarray(w_rows)
     x = np.ascontiguousarray(x, dtype=np.float32)
     y = np.empty(w_rows.shape[0], np.float32)
