@@ -138,7 +138,9 @@ int mio_hip_codec_decode_stage(mio_hip_codec *c, const int32_t *codes, int n_cod
  * Q8_0 / Q4_K / Q5_K / Q6_K / BF16 matrices (Q8_0, Q4_K_M, Q5_K_M, Q5_K_S, Q6_K and BF16 files;
  * Q5_0 / Q4_0 rows run as the Q8_0 rows they equal); any other tensor type (Q5_1, Q4_1, Q2_K,
  * Q3_K, IQ*) fails the load with the tensor's name and type,
- * F16 KV cache of n_ctx positions (0 -> 2048, :104). */
+ * F16 KV cache of n_ctx positions (0 -> 2048, :104). A file whose matrices are all BF16 (lfm2
+ * short-conv layers included) runs on every path; BF16 matrices beside quantized ones load and
+ * decode single-stream, with the prompt as forced decode steps and no batched decode. */
 int mio_hip_llm_load(mio_hip_device *d, const char *gguf_path, int n_ctx, mio_hip_llm **out);
 void mio_hip_llm_free(mio_hip_llm *m);
 /* info[8] = {n_vocab, n_embd, n_layer, n_head, n_head_kv, head_dim, n_ff, n_ctx} */
@@ -152,7 +154,8 @@ int mio_hip_llm_eval(mio_hip_llm *m, int32_t token, int pos, float *logits);
 /* The prefill llama_decode of test-to-speech.cpp:132-148 (logits for the last token only,
  * :138): positions 0..n_tokens-2 go through the batched prefill (one weight pass per chunk
  * of prompt tokens), the last token through one decode step; logits[n_vocab] to host (NULL
- * = skip). The KV cache then holds positions < n_tokens. */
+ * = skip). The KV cache then holds positions < n_tokens. BF16 matrices beside quantized ones:
+ * the positions run as forced decode steps instead (mio_hip_llm_prompt_chunks tells which). */
 int mio_hip_llm_prefill(mio_hip_llm *m, const int32_t *tokens, int n_tokens, float *logits);
 /* Copies the logits of the last step to host. */
 int mio_hip_llm_logits(mio_hip_llm *m, float *logits);
@@ -177,7 +180,8 @@ int mio_hip_llm_generate(mio_hip_llm *m, const int32_t *prompt, int n_prompt, in
  * uses seeds[b] and returns its tokens in out_tokens[b * max_tokens ...], n_out[b] of them
  * (stopping before an end token as mio_hip_llm_generate does). Each stream's tokens equal
  * mio_hip_llm_generate of its prompt with its seed. Uses its own KV caches (B x the model's),
- * allocated on first use. */
+ * allocated on first use. MIO_ERR_UNSUPPORTED for BF16 matrices beside quantized ones (all-BF16
+ * files, lfm2 ones included, are taken). */
 int mio_hip_llm_generate_batch(mio_hip_llm *m, const int32_t *prompts, const int32_t *prompt_lens, int B,
                                int max_tokens, float temperature, const uint64_t *seeds, int32_t allow_lo,
                                int32_t allow_hi, int32_t eos0, int32_t eos1, int32_t check_interval,
@@ -261,6 +265,11 @@ int mio_hip_llm_load_ms(const mio_hip_llm *m, double *ms);
  * an end token after n_out tokens issued *steps - n_out - 1 steps for nothing (the rest of the
  * end token's graph plus at most one more: <= 15; 0 when it stops at max_tokens). */
 int mio_hip_llm_steps_issued(const mio_hip_llm *m, int *steps);
+/* Weight passes the last mio_hip_llm_prefill or mio_hip_llm_generate spent on prompt positions
+ * [0, n - 1) (the last prompt token goes through a decode step): ceil((n - 1) / 128) chunks of
+ * the batched prefill; n - 1 where the prompt runs as forced decode steps (MIO_SEQ_PREFILL=1 in
+ * generate, or BF16 matrices beside quantized ones); 0 for a 1-token prompt. A host counter. */
+int mio_hip_llm_prompt_chunks(const mio_hip_llm *m, int *chunks);
 /* Cost of those steps after the last mio_hip_llm_generate that stopped at an end token
  * (test-to-speech.cpp:168-170 decodes nothing after it): every decode launch after the end
  * token returns at entry (StepState.done), so such a step costs about its launch boundaries.

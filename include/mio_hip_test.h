@@ -150,6 +150,13 @@ int mio_synth_llm_gguf(const char *path, int preset, uint64_t seed);
  * that are no multiple of 256 fall back to Q8_0), 2 Q4_0, 30 BF16; any other value is
  * MIO_ERR_INVALID. With the preset's own qtype the file equals mio_synth_llm_gguf's. */
 int mio_synth_llm_gguf_as(const char *path, int preset, int qtype, uint64_t seed);
+/* mio_synth_llm_gguf_as with sizes of the caller's: `preset`'s arch / rope / vocab / layer-kind
+ * rules and head_dim, the recipe `qtype`, and n_embd, n_layer, n_head, n_head_kv, n_ff where not
+ * 0 (0 keeps the preset's). The presets' own refusals (the Q5_K recipes' multiples of 256) hold;
+ * row lengths that are no multiple of 32 and kv heads that do not divide the heads are
+ * MIO_ERR_INVALID. */
+int mio_synth_llm_gguf_shape(const char *path, int preset, int qtype, uint64_t seed, int n_embd, int n_layer,
+                             int n_head, int n_head_kv, int n_ff);
 
 #ifdef __cplusplus
 }

@@ -34,6 +34,7 @@ inline QMat qmat_rows(const QMat &q, int r0, int n) {
         case 12: rb[0] = (size_t)q.k / 2, rb[1] = (size_t)q.k / 256 * 16; break;
         case 13: rb[0] = (size_t)q.k / 2, rb[1] = (size_t)q.k / 8, rb[2] = (size_t)q.k / 256 * 16; break;
         case 14: rb[0] = (size_t)q.k / 2, rb[1] = (size_t)q.k / 4, rb[2] = (size_t)q.k / 16, rb[3] = (size_t)q.k / 256 * 2; break;
+        case 30: rb[0] = (size_t)q.k * 2; break;
         default: break;
     }
     QMat v = q;

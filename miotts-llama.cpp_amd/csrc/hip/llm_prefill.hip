@@ -13,9 +13,10 @@
 //   k_pf_attn_out  per-token chunk merge + quantize -> O matvec -> x += .
 //   k_pf_ffn_in    RMSNorm + quantize -> gate|up -> silu(g)*u
 //   k_pf_ffn_down  quantize -> down -> x += .
-// lfm2 short-conv layers: in_proj on the matrix cores, k_bt_conv (gated conv per token, the
-// window from earlier tokens of the chunk or the sequence's ring), k_bt_conv_state (ring),
-// out_proj.
+// lfm2 short-conv layers: in_proj (int8 types on the matrix cores, BF16 on k_pf_attn_in with
+// the B | C rows as q and the X rows as v), k_bt_conv (gated conv per token, the window from
+// earlier tokens of the chunk or the sequence's ring), k_bt_conv_state (ring), out_proj
+// (matrix cores, BF16 on k_pf_attn_out).
 // Arithmetic is the decode step's, token by token, in the same order (same quantizers,
 // same per-superblock integer sums, the same pass order per row, the same online-softmax
 // order): the K/V cache and the last token's logits equal a token-by-token decode bit for
@@ -455,8 +456,9 @@ __global__ __launch_bounds__(MT) void k_bt_quant_split(const float *src, int K, 
 // positions pos - 1, pos - 2: the bcx rows of the tokens before t in this launch when they are
 // that sequence's previous positions, else the sequence's ring (written by an earlier chunk or
 // decode step), zeros before the sequence start. ring = layer il's ring of sequence 0.
+// ak = akind of out_proj (0 Q8_0, 1 Q8_K, 2 BF16: the record is laid out for rec_k = 2K).
 template <int NP>
-__global__ __launch_bounds__(MT) void k_bt_conv(LlmDims d, const float *conv_w, const float *ring, int kq,
+__global__ __launch_bounds__(MT) void k_bt_conv(LlmDims d, const float *conv_w, const float *ring, int ak,
                                                 PrefillBuffers pb) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int t = blockIdx.x, K = d.n_embd;
@@ -464,7 +466,7 @@ __global__ __launch_bounds__(MT) void k_bt_conv(LlmDims d, const float *conv_w, 
     // quantized straight into the token's global record (k_bt_quant's way); LDS keeps the
     // reduction scratch
     Smem s = carve(smem, K);
-    s.a = carve_t(pb.act, K, t).a;
+    s.a = carve_t(pb.act, ak == 2 ? 2 * K : K, t).a;
     const int pos = pb.pos[t * pb.pos_stride], sq = pb.seq[t * pb.seq_stride];
     const float *rs = ring + (size_t)sq * pb.seq_ring;
     ConvPrev pv[2];
@@ -480,7 +482,7 @@ __global__ __launch_bounds__(MT) void k_bt_conv(LlmDims d, const float *conv_w, 
     }
     ConvRegs<NP> cr;
     conv_load(pb.qkv + t * CW, pv[0], pv[1], conv_w, K, cr);
-    conv_quant(cr, K, kq != 0, s, nullptr);
+    conv_quant(cr, K, ak, s, nullptr);
 }
 
 // After k_bt_conv: the bx rows of each sequence's last two positions in this launch go to
@@ -518,11 +520,13 @@ __device__ inline void store_resid_b(const Resid &r, float *lds, int nt, int rpw
 }
 
 // ------------------------------------------------------------------ kernels
+// QD = the token stride of pb.qkv: (n_head + 2 n_kv) hd for q|k|v, 3 n_embd for an lfm2
+// short-conv layer's in_proj (wq = the B | C rows, wk empty, wv = the X rows)
 template <int NP, int TQ, int TV, int FQ = 0>
 __global__ __launch_bounds__(MT) void k_pf_attn_in(LlmDims d, const float *norm_w, QMat wq, QMat wk, QMat wv,
-                                                   int g_qk, PrefillBuffers pb, int nt) {
+                                                   int g_qk, PrefillBuffers pb, int nt, int QD) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int K = d.n_embd, QD = (d.n_head + 2 * d.n_kv) * d.hd, KR = rec_k(K, TQ);
+    const int K = d.n_embd, KR = rec_k(K, TQ);
     const int lane = threadIdx.x & 63;
     const int o1 = wq.rows, o2 = wq.rows + wk.rows;
     Frag ga[CfgB<TQ, NP, 1>::U], gb[CfgB<TQ, NP, 1>::U];
@@ -1050,11 +1054,12 @@ int tokens_per_launch(int K, int nt, int rpw) {
     return n;
 }
 
-PrefillBuffers shifted(const LlmDims &d, const PrefillBuffers &pb, int t, int K) {
+// pb from token t on; K = the act records' K, qkv_stride = the token stride of pb.qkv
+PrefillBuffers shifted(const LlmDims &d, const PrefillBuffers &pb, int t, int K, int qkv_stride) {
     PrefillBuffers q = pb;
     q.act += (size_t)t * act_bytes(K);
     q.x += (size_t)t * d.n_embd;
-    q.qkv += (size_t)t * (d.n_head + 2 * d.n_kv) * d.hd;
+    q.qkv += (size_t)t * qkv_stride;
     q.h += (size_t)t * d.n_ff;
     q.part += (size_t)t * d.n_head * d.max_splits * part_rec(d.hd);
     q.att += (size_t)t * d.n_head * d.hd;
@@ -1102,9 +1107,10 @@ void launch_layers(const LlmDims &d, const LayerW *layers, int n_layer, _Float16
     const int G = d.n_head / d.n_kv;
     // sub-launches over token ranges that fit LDS: f(t_off, n, shifted buffers)
     // (K = the act record's K, rec_k: twice the row length for BF16 weights)
-    auto over_tokens = [&](int K, int rpw, auto &&f) {
+    // qs = the token stride of pb.qkv in this layer
+    auto over_tokens = [&](int K, int rpw, int qs, auto &&f) {
         const int per = tokens_per_launch(K, nt, rpw);
-        for (int t = 0; t < nt; t += per) f(t, nt - t < per ? nt - t : per, shifted(d, pb, t, K));
+        for (int t = 0; t < nt; t += per) f(t, nt - t < per ? nt - t : per, shifted(d, pb, t, K, qs));
     };
     // matvecs on the int8 matrix cores (llm_mmq.hip) above 8 tokens per launch, the dot4
     // streaming engine below up to 8 (both bit-exact with the decode step). Same-box A/B,
@@ -1171,28 +1177,67 @@ void launch_layers(const LlmDims &d, const LayerW *layers, int n_layer, _Float16
         return true;
     };
     const int QD = (d.n_head + 2 * d.n_kv) * d.hd;
+    // a kernel template over the pass count of K
+    auto by_np = [](int K, auto &&f) {
+        const int np = pick_np(K);
+        if (np == 1)
+            f.template operator()<1>();
+        else if (np == 3)
+            f.template operator()<3>();
+        else
+            f.template operator()<6>();
+    };
     for (int il = 0; il < n_layer; ++il) {
         const LayerW &L = layers[il];
         if (L.conv) {
             // lfm2 short-conv layer: RMSNorm + in_proj -> B | C | X rows, the gated conv (k_bt_conv)
-            // -> out_proj -> x += ., ring update. Always on the matrix cores (bit-exact with the
-            // decode step's matvec at any token count).
+            // -> out_proj -> x += ., ring update. The int8 types always on the matrix cores, BF16
+            // on the streaming dot engine (both bit-exact with the decode step's matvec at any
+            // token count; the loader's bf16_mt keeps a BF16 matrix beside an int8 one off this
+            // engine).
             const int n = d.n_embd;
+            const bool bf = L.in_proj.type == 30;
             float *ring = pb.ring + (size_t)il * kConvSlots * n;
             launch_quant(d, 0, pb.x, n, L.attn_norm, akind(L.in_proj.type), pb, nt, s);
-            const MmqSeg sg{L.in_proj, mmq_tiles(L.in_proj.rows), 0};
-            launch_mmq(&sg, &L.in_proj.type, 1, MMQ_STORE, MmqArgs{pb.act, act_bytes(n), n, nt, pb.qkv, 3 * n, {}}, s);
-            const int np = pick_np(n);
-            const int kq = L.out_proj.type != 8;
-            if (np == 1)
-                hipLaunchKernelGGL((k_bt_conv<1>), dim3(nt), dim3(MT), smem_bytes(n), s, d, L.conv_w, ring, kq, pb);
-            else if (np == 3)
-                hipLaunchKernelGGL((k_bt_conv<3>), dim3(nt), dim3(MT), smem_bytes(n), s, d, L.conv_w, ring, kq, pb);
-            else
-                hipLaunchKernelGGL((k_bt_conv<6>), dim3(nt), dim3(MT), smem_bytes(n), s, d, L.conv_w, ring, kq, pb);
+            if (bf) {
+                // the decode step's view of in_proj (kConvIn): B | C rows as q, no k, X rows as v
+                LayerW V = L;
+                V.wq = qmat_rows(L.in_proj, 0, 2 * n);
+                V.wk = qmat_rows(L.in_proj, 2 * n, 0);
+                V.wv = qmat_rows(L.in_proj, 2 * n, n);
+                int GW, g_qk;
+                attn_in_grid(d, V, GW, g_qk);
+                const int KR = rec_k(n, 30);
+                over_tokens(KR, 0, 3 * n, [&](int, int m, const PrefillBuffers &q) {
+                    by_np(n, [&]<int NP>() {
+                        allow_lds(k_pf_attn_in<NP, 30, 30>);
+                        hipLaunchKernelGGL((k_pf_attn_in<NP, 30, 30>), dim3(GW), dim3(MT), pf_lds_bytes(KR, m, 0), s, d,
+                                           L.attn_norm, V.wq, V.wk, V.wv, g_qk, q, m, 3 * n);
+                    });
+                });
+            } else {
+                const MmqSeg sg{L.in_proj, mmq_tiles(L.in_proj.rows), 0};
+                launch_mmq(&sg, &L.in_proj.type, 1, MMQ_STORE, MmqArgs{pb.act, act_bytes(n), n, nt, pb.qkv, 3 * n, {}}, s);
+            }
+            const int ak = akind(L.out_proj.type);
+            by_np(n, [&]<int NP>() {
+                hipLaunchKernelGGL((k_bt_conv<NP>), dim3(nt), dim3(MT), smem_bytes(n), s, d, L.conv_w, ring, ak, pb);
+            });
             hipLaunchKernelGGL(k_bt_conv_state, dim3(nt), dim3(ST), 0, s, d, ring, pb, nt);
-            const MmqSeg so{L.out_proj, mmq_tiles(L.out_proj.rows), 0};
-            launch_mmq(&so, &L.out_proj.type, 1, MMQ_RESID, MmqArgs{pb.act, act_bytes(n), n, nt, pb.x, n, {}}, s);
+            if (bf) {
+                const int grid = matvec_grid(d, L.out_proj.rows), rpw = rows_per_wave(L.out_proj.rows, grid);
+                const int KR = rec_k(n, 30);
+                over_tokens(KR, rpw, 3 * n, [&](int, int m, const PrefillBuffers &q) {
+                    by_np(n, [&]<int NP>() {
+                        allow_lds(k_pf_attn_out<NP, 30>);
+                        hipLaunchKernelGGL((k_pf_attn_out<NP, 30>), dim3(grid), dim3(MT), pf_lds_bytes(KR, m, rpw), s, d,
+                                           L.out_proj, q, m, rpw);
+                    });
+                });
+            } else {
+                const MmqSeg so{L.out_proj, mmq_tiles(L.out_proj.rows), 0};
+                launch_mmq(&so, &L.out_proj.type, 1, MMQ_RESID, MmqArgs{pb.act, act_bytes(n), n, nt, pb.x, n, {}}, s);
+            }
         } else {
             _Float16 *kc = kcache + il * layer_kv, *vc = vcache + il * layer_kv;
             // the attention merger writes the O matvec's activation records when every kv head's
@@ -1217,7 +1262,7 @@ void launch_layers(const LlmDims &d, const LayerW *layers, int n_layer, _Float16
                 int GW, g_qk;
                 attn_in_grid(d, L, GW, g_qk);
                 const int KR = rec_k(d.n_embd, L.wq.type);
-                over_tokens(KR, 0, [&](int, int n, const PrefillBuffers &q) {
+                over_tokens(KR, 0, QD, [&](int, int n, const PrefillBuffers &q) {
                     const size_t lds = pf_lds_bytes(KR, n, 0);
                     dispatch_nt<true>(d.n_embd, L.wq.type, [&]<int NP, int TQ>() {
                         auto go = [&]<int TV>() {
@@ -1225,13 +1270,13 @@ void launch_layers(const LlmDims &d, const LayerW *layers, int n_layer, _Float16
                                 if (fa) {
                                     allow_lds(k_pf_attn_in<NP, TQ, TV, 2>);
                                     hipLaunchKernelGGL((k_pf_attn_in<NP, TQ, TV, 2>), dim3(GW), dim3(MT), lds, s, d,
-                                                       L.attn_norm, L.wq, L.wk, L.wv, g_qk, q, n);
+                                                       L.attn_norm, L.wq, L.wk, L.wv, g_qk, q, n, QD);
                                     return;
                                 }
                             }
                             allow_lds(k_pf_attn_in<NP, TQ, TV>);
                             hipLaunchKernelGGL((k_pf_attn_in<NP, TQ, TV>), dim3(GW), dim3(MT), lds, s, d, L.attn_norm,
-                                               L.wq, L.wk, L.wv, g_qk, q, n);
+                                               L.wq, L.wk, L.wv, g_qk, q, n, QD);
                         };
                         dispatch_v<TQ>(L.wv.type, go);
                     });
@@ -1267,7 +1312,7 @@ void launch_layers(const LlmDims &d, const LayerW *layers, int n_layer, _Float16
             } else {
                 const int grid = matvec_grid(d, L.wo.rows), rpw = rows_per_wave(L.wo.rows, grid);
                 const int KR = rec_k(L.wo.k, L.wo.type);
-                over_tokens(KR, rpw, [&](int, int n, const PrefillBuffers &q) {
+                over_tokens(KR, rpw, QD, [&](int, int n, const PrefillBuffers &q) {
                     dispatch_nt<true>(L.wo.k, L.wo.type, [&]<int NP, int T>() {
                         allow_lds(k_pf_attn_out<NP, T>);
                         hipLaunchKernelGGL((k_pf_attn_out<NP, T>), dim3(grid), dim3(MT), pf_lds_bytes(KR, n, rpw), s,
@@ -1289,7 +1334,7 @@ void launch_layers(const LlmDims &d, const LayerW *layers, int n_layer, _Float16
         } else {
             const int grid = matvec_grid(d, L.gate.rows);
             const int KR = rec_k(d.n_embd, L.gate.type);
-            over_tokens(KR, 0, [&](int, int n, const PrefillBuffers &q) {
+            over_tokens(KR, 0, QD, [&](int, int n, const PrefillBuffers &q) {
                 dispatch_nt<true>(d.n_embd, L.gate.type, [&]<int NP, int T>() {
                     if constexpr (NP == 1 && T != 30) {
                         if (ff) {
@@ -1333,7 +1378,7 @@ void launch_layers(const LlmDims &d, const LayerW *layers, int n_layer, _Float16
         } else {
             const int grid = matvec_grid(d, L.down.rows), rpw = rows_per_wave(L.down.rows, grid);
             const int KR = rec_k(L.down.k, L.down.type);
-            over_tokens(KR, rpw, [&](int, int n, const PrefillBuffers &q) {
+            over_tokens(KR, rpw, QD, [&](int, int n, const PrefillBuffers &q) {
                 dispatch_nt<true>(L.down.k, L.down.type, [&]<int NP, int T>() {
                     allow_lds(k_pf_ffn_down<NP, T>);
                     hipLaunchKernelGGL((k_pf_ffn_down<NP, T>), dim3(grid), dim3(MT), pf_lds_bytes(KR, n, rpw),

@@ -288,6 +288,12 @@ bool sequential_prefill() {
     return seq;
 }
 
+// weight passes over P prompt positions: one per chunk of the batched prefill, one per position
+// as forced decode steps (MIO_SEQ_PREFILL=1, or a model the multi-token engine does not take)
+int prompt_passes(const mio_hip_llm *m, int P) {
+    return sequential_prefill() || !m->bf16_mt() ? P : (P + mio::kPrefillB - 1) / mio::kPrefillB;
+}
+
 // force[j] = the token step j's sampler is forced to: tokens[j + 1] for the prompt, -1 after it
 int upload_force(mio_hip_llm *m, const int32_t *tokens, int n) {
     std::vector<int> force(m->max_steps, -1);
@@ -412,6 +418,7 @@ int llm_begin(mio_hip_llm *m, const int32_t *prompt, int n_prompt, int max_new, 
     // kPrefillB tokens), or, with MIO_SEQ_PREFILL=1, as P forced decode steps; decoding
     // then starts at position P with the step counter at P either way (same sampler stream)
     const int P = n_prompt - 1;
+    m->prompt_chunks = prompt_passes(m, P);
     if (sequential_prefill() || !m->bf16_mt()) {
         m->steps_issued = 0;
         if ((rc = set_state(m, 0, prompt[0]))) return rc;
@@ -512,6 +519,12 @@ extern "C" int mio_hip_llm_load_ms(const mio_hip_llm *m, double *ms) {
     return MIO_OK;
 }
 
+extern "C" int mio_hip_llm_prompt_chunks(const mio_hip_llm *m, int *chunks) {
+    MIO_REQUIRE(m && chunks, MIO_ERR_INVALID, "llm_prompt_chunks: null");
+    *chunks = m->prompt_chunks;
+    return MIO_OK;
+}
+
 extern "C" int mio_hip_llm_steps_issued(const mio_hip_llm *m, int *steps) {
     MIO_REQUIRE(m && steps, MIO_ERR_INVALID, "llm_steps_issued: null");
     *steps = std::max(0, m->steps_issued - (m->n_prompt - 1));
@@ -566,16 +579,19 @@ extern "C" int mio_hip_llm_prefill(mio_hip_llm *m, const int32_t *tokens, int n_
     int rc = mio::bind(m->d);
     if (rc) return rc;
     if (!m->bf16_mt()) {
-        // forced decode steps as llm_begin runs them (the multi-token engine is int8-only):
-        // step j decodes tokens[j] at position j and its sampler is forced to tokens[j + 1]
+        // forced decode steps as llm_begin runs them (BF16 beside int8 matrices is not on the
+        // multi-token engine): step j decodes tokens[j] at position j and its sampler is forced
+        // to tokens[j + 1]
+        m->prompt_chunks = n_tokens - 1;
         if (n_tokens > 1) {
             if ((rc = upload_force(m, tokens, n_tokens)) || (rc = put_cfg(m, greedy_cfg(m))) ||
                 (rc = ensure_graph(m)) || (rc = set_state(m, 0, tokens[0])))
                 return rc;
             for (int j = 0; j + 1 < n_tokens; ++j) MIO_HIP_CHECK(hipGraphLaunch(m->graph, m->d->stream));
         }
-    } else if ((rc = upload_prompt(m, tokens, n_tokens)) || (rc = prefill(m, n_tokens - 1))) {
-        return rc;
+    } else {
+        m->prompt_chunks = (n_tokens - 1 + mio::kPrefillB - 1) / mio::kPrefillB;
+        if ((rc = upload_prompt(m, tokens, n_tokens)) || (rc = prefill(m, n_tokens - 1))) return rc;
     }
     return mio_hip_llm_eval(m, tokens[n_tokens - 1], n_tokens - 1, logits);
 }

@@ -116,8 +116,8 @@ extern "C" int mio_hip_llm_generate_batch(mio_hip_llm *m, const int32_t *prompts
     MIO_REQUIRE(mio::batch_supported(m->dims, B, m->lm.type), MIO_ERR_UNSUPPORTED,
                 "llm_generate_batch: %d streams not supported (1..%d, lm_head LDS)", B, mio::kBatchMax);
     MIO_REQUIRE(m->bf16_mt(), MIO_ERR_UNSUPPORTED,
-                "llm_generate_batch: BF16 weights mixed with quantized ones, or in an lfm2 model, run on the "
-                "single-stream decode only (mio_hip_llm_generate)");
+                "llm_generate_batch: BF16 weights mixed with quantized ones run on the single-stream decode "
+                "only (mio_hip_llm_generate)");
     const mio::LlmDims &D = m->dims;
     std::vector<int> off(B + 1, 0);
     for (int b = 0; b < B; ++b) {

@@ -69,11 +69,11 @@ struct mio_hip_llm {
     std::vector<void *> allocs;
     uint64_t weight_bytes = 0;
     // BF16 matrices: the multi-token engine runs them on its streaming dot engine with bf16
-    // act records (rec_k) when every matrix is BF16 and no layer is an lfm2 short conv (whose
-    // in_proj / out_proj are on the int8 matrix cores); otherwise (bf16_mt false) the prompt is
-    // prefilled as forced decode steps and batched decode is refused
+    // act records (rec_k) when every matrix is BF16 (attention and lfm2 short-conv layers
+    // alike); a BF16 matrix beside an int8 one (bf16_mt false) has the prompt prefilled as
+    // forced decode steps and batched decode refused
     bool bf16 = false, int8 = false, has_conv = false;
-    bool bf16_mt() const { return !bf16 || (!int8 && !has_conv); }
+    bool bf16_mt() const { return !bf16 || !int8; }
     // all quantized matrices live in one arena, in the order a step streams them
     uint8_t *arena = nullptr;
     std::map<std::string, size_t> arena_off;
@@ -96,6 +96,9 @@ struct mio_hip_llm {
     float *d_layers = nullptr;  // mio_hip_llm_eval_layers' residual snapshots (parity tests)
     // generation state
     int n_prompt = 0, max_new = 0, steps_total = 0, steps_issued = 0;
+    // weight passes the last prefill / generate spent on prompt positions [0, n - 1)
+    // (mio_hip_llm_prompt_chunks)
+    int prompt_chunks = 0;
     mio::SampleCfg cfg{};
     double load_ms = 0.0;  // wall time of mio_hip_llm_load (GGUF mmap -> HBM arena)
     std::unique_ptr<Stager> stager;  // weight upload staging (load only)

@@ -122,6 +122,8 @@ def _declare(L: ctypes.CDLL) -> None:
         "mio_synth_voice_gguf": (c_int, [ctypes.c_char_p, ctypes.c_uint64]),
         "mio_synth_llm_gguf": (c_int, [ctypes.c_char_p, c_int, ctypes.c_uint64]),
         "mio_synth_llm_gguf_as": (c_int, [ctypes.c_char_p, c_int, c_int, ctypes.c_uint64]),
+        "mio_synth_llm_gguf_shape": (c_int, [ctypes.c_char_p, c_int, c_int, ctypes.c_uint64, c_int, c_int, c_int,
+                                             c_int, c_int]),
         "mio_hip_llm_load": (c_int, [_vp, ctypes.c_char_p, c_int, ctypes.POINTER(_vp)]),
         "mio_hip_llm_free": (None, [_vp]),
         "mio_normalize_tts_text": (c_int, [ctypes.c_char_p, _vp, c_int, ctypes.POINTER(c_int)]),
@@ -141,6 +143,7 @@ def _declare(L: ctypes.CDLL) -> None:
         "mio_hip_codec_last_flops": (c_int, [_vp, ctypes.POINTER(ctypes.c_double)]),
         "mio_hip_llm_load_ms": (c_int, [_vp, ctypes.POINTER(ctypes.c_double)]),
         "mio_hip_llm_steps_issued": (c_int, [_vp, ctypes.POINTER(c_int)]),
+        "mio_hip_llm_prompt_chunks": (c_int, [_vp, ctypes.POINTER(c_int)]),
         "mio_hip_llm_tail": (c_int, [_vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_float)]),
         "mio_hip_llm_step_kinds": (c_int, [_vp, _vp, c_int, ctypes.POINTER(c_int)]),
         "mio_hip_llm_batch_step_launches": (c_int, [_vp, c_int, ctypes.POINTER(c_int)]),
@@ -512,6 +515,15 @@ def synth_llm_as(path: str, preset: int, qtype: int, seed: int = 1) -> str:
     return path
 
 
+def synth_llm_shape(path: str, preset: int, qtype: int, seed: int = 1, n_embd: int = 0, n_layer: int = 0,
+                    n_head: int = 0, n_head_kv: int = 0, n_ff: int = 0) -> str:
+    """synth_llm_as with sizes of the caller's (0 keeps the preset's); head_dim, arch, rope, vocab and
+    the layer-kind rule stay the preset's."""
+    check(lib().mio_synth_llm_gguf_shape(path.encode(), preset, qtype, seed, n_embd, n_layer, n_head, n_head_kv,
+                                         n_ff))
+    return path
+
+
 class Llm:
     """HIP LLM decode (mirror of the llama.cpp calls in test-to-speech.cpp:44-196)."""
 
@@ -551,6 +563,13 @@ class Llm:
         """Decode steps issued by the last generate, look-ahead past an end token included."""
         v = ctypes.c_int(0)
         check(lib().mio_hip_llm_steps_issued(self.h, ctypes.byref(v)))
+        return v.value
+
+    def prompt_chunks(self) -> int:
+        """Weight passes the last prefill / generate spent on prompt positions [0, n - 1): one per
+        128-token chunk of the batched prefill, one per position as forced decode steps."""
+        v = ctypes.c_int(0)
+        check(lib().mio_hip_llm_prompt_chunks(self.h, ctypes.byref(v)))
         return v.value
 
     def tail(self):
