@@ -6,6 +6,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <string>
 
 #include "mio_hip.h"
@@ -35,6 +36,19 @@ const char *last_error();
             return (code);                                                               \
         }                                                                                \
     } while (0)
+
+// A 0/1 switch of the environment: `def` unless the variable's first character is the other
+// digit. Every knob is read once per process (the callers keep the result in a static).
+inline bool env_flag(const char *name, bool def) {
+    const char *e = getenv(name);
+    return e && *e == (def ? '0' : '1') ? !def : def;
+}
+// An integer knob clamped to [lo, hi]; `def` when unset or empty.
+inline int env_int(const char *name, int def, int lo, int hi) {
+    const char *e = getenv(name);
+    const int v = e && *e ? atoi(e) : def;
+    return v < lo ? lo : (v > hi ? hi : v);
+}
 
 struct mio_hip_device {
     int dev = 0;

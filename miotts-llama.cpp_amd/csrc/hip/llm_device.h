@@ -9,7 +9,10 @@
 #include <climits>
 #include <cstdio>
 #include <cstdlib>
+#include <mutex>
 #include <type_traits>
+#include <utility>
+#include <vector>
 
 #include "llm_kernels.h"
 
@@ -1427,6 +1430,41 @@ void dispatch_v(int tv, F &&f) {
         if (tv == 12) return f.template operator()<12>();
     }
     no_kernel("attn_v beside q|k", tv, TQ);
+}
+
+// Calls f.template operator()<NP>() for the pass count of K.
+template <class F>
+void dispatch_np(int K, F &&f) {
+    const int np = pick_np(K);
+    if (np == 1) return f.template operator()<1>();
+    if (np == 3) return f.template operator()<3>();
+    return f.template operator()<6>();
+}
+
+// Calls f.template operator()<HD>() for the head dim (128, else 64: the loader takes no other).
+template <class F>
+void dispatch_hd(int hd, F &&f) {
+    if (hd == 128) return f.template operator()<128>();
+    return f.template operator()<64>();
+}
+
+// Dynamic LDS beyond the default 64 KB needs the per-kernel opt-in (once per kernel and
+// device: the attribute applies to the current device; the limit leaves room for the
+// kernel's static LDS). Keyed by (device, kernel address): kernels of one signature share a
+// function type.
+constexpr int LDS_DYN_MAX = 160 * 1024 - 1024;
+template <class Kern>
+void allow_lds(Kern k) {
+    static std::mutex mu;
+    static std::vector<std::pair<int, const void *>> done;
+    const void *p = reinterpret_cast<const void *>(k);
+    int dev = 0;
+    hipGetDevice(&dev);
+    std::lock_guard<std::mutex> lk(mu);
+    for (const auto &q : done)
+        if (q.first == dev && q.second == p) return;
+    hipFuncSetAttribute(p, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DYN_MAX);
+    done.push_back({dev, p});
 }
 
 

@@ -24,6 +24,7 @@
 // (tokens) (r & 3) + 8 (r >> 2) + 4 (l >> 5), r = 0..15. A/B: lane l holds row/column
 // l & 31 and a contiguous half of K (the same half in A and B; exact-integer probe:
 // tools/micro/mfma_i8_probe.hip).
+#include "common.h"
 #include "llm_device.h"
 #include "llm_mmq.h"
 #include "llm_quant_producer.h"
@@ -1368,25 +1369,30 @@ size_t mmq_lds(int type, int K, int mode) {
            (size_t)(type == 8 ? K / 32 : K / 256) * TT * sizeof(float);
 }
 
-// dynamic LDS above 64 KB (Q8_0 activation scales of a long K) needs the per-kernel opt-in,
-// once per (device, kernel)
-static void allow_lds_mmq(const void *kern) {
-    static std::mutex mu;
-    static std::vector<std::pair<int, const void *>> done;
-    int dev = 0;
-    hipGetDevice(&dev);
-    std::lock_guard<std::mutex> lk(mu);
-    for (const auto &q : done)
-        if (q.first == dev && q.second == kern) return;
-    hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);
-    done.push_back({dev, kern});
-}
-
 int mmq_tiles(int rows) { return (rows + RT - 1) / RT; }
 
-// types: {T0, T1, T2} (-1 = segment unused); mode MMQ_*.
-// 16 x 16 tiles (k_mmq16) for launches of at most 16 tokens; MIO_MMQ16=0: 32 x 32 tiles always
-// CUs of the current device (the tile-loop grids: one workgroup per CU), cached
+// ------------------------------------------------------------------ switches
+// Every environment switch of the matrix-core launches, read once per process.
+struct MmqSwitches {
+    // MIO_MMQ_LOOP (default 1): Q8_0 one-pass launches with more 16-row tiles than CUs walk their
+    // tiles in k_mmq16_loop (one workgroup per CU) instead of one workgroup per tile
+    bool loop = env_flag("MIO_MMQ_LOOP", true);
+    // MIO_MMQ_LOOP_KQ (bits, default 3): K-quant (Q4_K / Q5_K / Q6_K, K <= 2048) matmuls of more
+    // 16-row tiles than CUs walk their tiles in k_mmq16_loop_kq: bit 0 without in-launch
+    // quantization (the batched lm_head), bit 1 with it (the batched gate|up)
+    int loop_kq = env_int("MIO_MMQ_LOOP_KQ", 3, 0, 3);
+    // MIO_BT_QCHUNK=0: k_mmq16's producers of plain rows (q.mode 1) work per token instead of per
+    // (token, 2048-element chunk)
+    bool qchunk = env_flag("MIO_BT_QCHUNK", true);
+    // MIO_KQ_EARLY=0: K-quant tiles issue their weight loads after the producers' wait
+    bool early = env_flag("MIO_KQ_EARLY", true);
+};
+static const MmqSwitches &switches() {
+    static const MmqSwitches sw;
+    return sw;
+}
+
+// CUs of the current device (the tile-walk grids: one workgroup per CU), cached
 static int n_cu() {
     static const int n = [] {
         int dev = 0, v = 0;
@@ -1395,88 +1401,79 @@ static int n_cu() {
     }();
     return n;
 }
-// MIO_MMQ_LOOP (default 1): Q8_0 one-pass launches with more 16-row tiles than CUs walk their
-// tiles in k_mmq16_loop (one workgroup per CU) instead of one workgroup per tile
-static bool mmq_loop_on() {
-    static const bool on = !(getenv("MIO_MMQ_LOOP") && getenv("MIO_MMQ_LOOP")[0] == '0');
-    return on;
+
+// LDS of the 16 x 16 tiles (k_mmq16 and the walks)
+static size_t mmq16_lds(int type, int K, int mode) {
+    return (size_t)(mode == MMQ_SWIGLU ? 2 : 1) * MMQ_NT * 4 * sizeof(float) +
+           (size_t)(type == 8 ? K / 32 : K / 256) * TT16 * sizeof(float);
 }
 
-// MIO_MMQ_LOOP_KQ (bits, default 3): K-quant (Q4_K / Q6_K, K <= 2048) matmuls of more 16-row
-// tiles than CUs walk their tiles in k_mmq16_loop_kq: bit 0 without in-launch quantization
-// (the batched lm_head), bit 1 with it (the batched gate|up)
-static int kq_loop_mask() {
-    static const int m = getenv("MIO_MMQ_LOOP_KQ") ? atoi(getenv("MIO_MMQ_LOOP_KQ")) : 3;
-    return m;
+// dynamic LDS above 64 KB (Q8_0 activation scales of a long K) needs the per-kernel opt-in
+template <class Kern, class... Args>
+static void launch_tiles(Kern kern, dim3 grid, size_t lds, hipStream_t s, const Args &...args) {
+    if (lds > 64 * 1024) allow_lds(kern);
+    hipLaunchKernelGGL(kern, grid, dim3(MMQ_NT), lds, s, args...);
 }
 
-bool mmq16_on(int nt) {
-    static const bool on = !(getenv("MIO_MMQ16") && getenv("MIO_MMQ16")[0] == '0');
-    return on && nt <= TT16;
+// Do `n_wg` workgroups walk the 16-row tiles (k_mmq16_loop, k_mmq16_loop_kq) instead of one
+// workgroup per tile: one-pass K of whole superblocks, more tiles than workgroups; kq_bit = the
+// K-quants' bit of MIO_MMQ_LOOP_KQ.
+static bool walks(int type, int K, int tiles, int n_wg, int kq_bit) {
+    const MmqSwitches &sw = switches();
+    return K % 256 == 0 && K <= 2048 && tiles > n_wg && n_wg > 0 && sw.loop && (type == 8 || (sw.loop_kq & kq_bit));
+}
+template <class Kern>
+static void launch_walk(Kern kern, int n_wg, size_t lds, hipStream_t s, const MmqSeg &sg, const MmqArgs &a,
+                        const MmqQuant &q, int tiles) {
+    launch_tiles(kern, dim3(n_wg), lds, s, sg, a, q, tiles);
 }
 
+// Calls f.template operator()<MODE>().
+template <class F>
+static void dispatch_mode(int mode, F &&f) {
+    if (mode == MMQ_STORE) return f.template operator()<MMQ_STORE>();
+    if (mode == MMQ_RESID) return f.template operator()<MMQ_RESID>();
+    return f.template operator()<MMQ_SWIGLU>();
+}
+
+// types: {T0, T1, T2} (-1 = segment unused); mode MMQ_*.
+// 16 x 16 tiles (k_mmq16) for launches of at most 16 tokens (r04: 1.516 vs 1.676 ms per 8-stream
+// 1.7B step with the 32 x 32 tiles of k_mmq, which stay above 16 tokens).
 void launch_mmq(const MmqSeg *seg, const int *types, int nseg, int mode, const MmqArgs &a, hipStream_t s) {
     MmqSeg sg[3] = {seg[0], nseg > 1 ? seg[1] : MmqSeg{}, nseg > 2 ? seg[2] : MmqSeg{}};
-    const bool t16 = mmq16_on(a.nt);
+    const bool t16 = a.nt <= TT16;
     int tiles = 0;
-    for (int i = 0; i < nseg; ++i) tiles += t16 ? (sg[i].w.rows + RT16 - 1) / RT16 : sg[i].tiles;
-    const dim3 grid(tiles, t16 ? 1 : (a.nt + TT - 1) / TT);
     size_t lds = 0;
-    for (int i = 0; i < nseg; ++i)
-        lds = std::max(lds, t16 ? (size_t)(mode == MMQ_SWIGLU ? 2 : 1) * MMQ_NT * 4 * sizeof(float) +
-                                      (size_t)(types[i] == 8 ? a.K / 32 : a.K / 256) * TT16 * sizeof(float)
-                                : mmq_lds(types[i], a.K, mode));
+    for (int i = 0; i < nseg; ++i) {
+        tiles += t16 ? (sg[i].w.rows + RT16 - 1) / RT16 : sg[i].tiles;
+        lds = std::max(lds, t16 ? mmq16_lds(types[i], a.K, mode) : mmq_lds(types[i], a.K, mode));
+    }
+    const dim3 grid(tiles, t16 ? 1 : (a.nt + TT - 1) / TT);
+    auto tile = [&](auto kern) { launch_tiles(kern, grid, lds, s, sg[0], sg[1], sg[2], a, MmqQuant{}); };
+    // (walks, tiles, 32 x 32 tiles one after the other, each with its own mode dispatch: this
+    // order of first use keeps every kernel at the place in the code object that the recorded
+    // step times were measured with)
     auto go = [&]<int A, int B, int C>() {
-        auto launch = [&](auto kern) {
-            if (lds > 64 * 1024) allow_lds_mmq(reinterpret_cast<const void *>(kern));
-            hipLaunchKernelGGL(kern, grid, dim3(MMQ_NT), lds, s, sg[0], sg[1], sg[2], a, MmqQuant{});
-        };
         if (t16) {
+            if constexpr (B < 0) {
+                if (walks(A, a.K, tiles, n_cu(), 1))
+                    return dispatch_mode(mode, [&]<int M>() {
+                        if constexpr (A == 8)
+                            launch_walk(k_mmq16_loop<M, 0, 0>, n_cu(), lds, s, sg[0], a, MmqQuant{}, tiles);
+                        else
+                            launch_walk(k_mmq16_loop_kq<A, M, 0, 0>, n_cu(), lds, s, sg[0], a, MmqQuant{}, tiles);
+                    });
+            }
+            // Q8_0 over whole superblocks: the 16-B pair path, one pass (KP 1) or several (2)
             const bool q8 = A == 8 && (B < 0 || B == 8) && (C < 0 || C == 8) && a.K % 256 == 0;
             const int kp = q8 ? (a.K <= 2048 ? 1 : 2) : 0;
-            if constexpr ((A == 12 || A == 13 || A == 14) && B < 0) {
-                if (a.K % 256 == 0 && a.K <= 2048 && tiles > n_cu() && mmq_loop_on() && (kq_loop_mask() & 1)) {
-                    auto kl = [&](auto kern) {
-                        if (lds > 64 * 1024) allow_lds_mmq(reinterpret_cast<const void *>(kern));
-                        hipLaunchKernelGGL(kern, dim3(n_cu()), dim3(MMQ_NT), lds, s, sg[0], a, MmqQuant{}, tiles);
-                    };
-                    if (mode == MMQ_STORE) kl(k_mmq16_loop_kq<A, MMQ_STORE, 0, 0>);
-                    else if (mode == MMQ_RESID) kl(k_mmq16_loop_kq<A, MMQ_RESID, 0, 0>);
-                    else kl(k_mmq16_loop_kq<A, MMQ_SWIGLU, 0, 0>);
-                    return;
-                }
-            }
-            if constexpr (A == 8 && B < 0) {
-                if (kp == 1 && tiles > n_cu() && mmq_loop_on()) {
-                    auto kl = [&](auto kern) {
-                        if (lds > 64 * 1024) allow_lds_mmq(reinterpret_cast<const void *>(kern));
-                        hipLaunchKernelGGL(kern, dim3(n_cu()), dim3(MMQ_NT), lds, s, sg[0], a, MmqQuant{}, tiles);
-                    };
-                    if (mode == MMQ_STORE) kl(k_mmq16_loop<MMQ_STORE, 0, 0>);
-                    else if (mode == MMQ_RESID) kl(k_mmq16_loop<MMQ_RESID, 0, 0>);
-                    else kl(k_mmq16_loop<MMQ_SWIGLU, 0, 0>);
-                    return;
-                }
-            }
-            auto kpl = [&]<int M>() {
-                if (kp == 1) launch(k_mmq16<A, B, C, M, 1>);
-                else if (kp == 2) launch(k_mmq16<A, B, C, M, 2>);
-                else launch(k_mmq16<A, B, C, M, 0>);
-            };
-            if (mode == MMQ_STORE)
-                kpl.template operator()<MMQ_STORE>();
-            else if (mode == MMQ_RESID)
-                kpl.template operator()<MMQ_RESID>();
-            else
-                kpl.template operator()<MMQ_SWIGLU>();
-            return;
+            return dispatch_mode(mode, [&]<int M>() {
+                if (kp == 1) tile(k_mmq16<A, B, C, M, 1>);
+                else if (kp == 2) tile(k_mmq16<A, B, C, M, 2>);
+                else tile(k_mmq16<A, B, C, M, 0>);
+            });
         }
-        if (mode == MMQ_STORE)
-            launch(k_mmq<A, B, C, MMQ_STORE>);
-        else if (mode == MMQ_RESID)
-            launch(k_mmq<A, B, C, MMQ_RESID>);
-        else
-            launch(k_mmq<A, B, C, MMQ_SWIGLU>);
+        dispatch_mode(mode, [&]<int M>() { tile(k_mmq<A, B, C, M>); });
     };
     auto one = [&]<int A>() {
         if (nseg == 1) return go.template operator()<A, -1, -1>();
@@ -1494,89 +1491,71 @@ void launch_mmq(const MmqSeg *seg, const int *types, int nseg, int mode, const M
     else no_kernel("matmul", types[0], a.K);
 }
 
-
-// The fused shapes of the batched decode (launch_layers): q|k|v of the K-quant models (three
-// segments, RMSNorm input), gate|up (Q4_K / Q5_K / Q6_K, or Q8_0 one-pass pairs; RMSNorm input) and the
-// K-quant down matmul (plain h rows of 3 passes). Anything else: false.
+// The fused shapes of the batched decode (launch_layers), each with what routes to it by
+// default at <= 8 streams. Anything else: false.
 bool launch_mmq_q(const MmqSeg *seg, const int *types, int nseg, int mode, const MmqArgs &a, const MmqQuant &q,
                   hipStream_t s) {
-    if (!mmq16_on(a.nt)) return false;
+    if (a.nt > TT16) return false;
     MmqSeg sg[3] = {seg[0], nseg > 1 ? seg[1] : MmqSeg{}, nseg > 2 ? seg[2] : MmqSeg{}};
     int tiles = 0;
-    size_t lds = 0;
+    size_t lds = act_bytes(a.K) + smem_bytes(a.K);  // the producers' record + scratch
     for (int i = 0; i < nseg; ++i) {
         tiles += (sg[i].w.rows + RT16 - 1) / RT16;
-        lds = std::max(lds, (size_t)(mode == MMQ_SWIGLU ? 2 : 1) * MMQ_NT * 4 * sizeof(float) +
-                                (size_t)(types[i] == 8 ? a.K / 32 : a.K / 256) * TT16 * sizeof(float));
+        lds = std::max(lds, mmq16_lds(types[i], a.K, mode));
     }
-    lds = std::max(lds, act_bytes(a.K) + smem_bytes(a.K));  // the producers' record + scratch
+    const MmqSwitches &sw = switches();
     // k_mmq16's producer count: per (token, 2048-element chunk) for plain rows (q.mode 1)
-    static const bool qchunk = !(getenv("MIO_BT_QCHUNK") && getenv("MIO_BT_QCHUNK")[0] == '0');
     MmqQuant qq = q;
-    if (q.mode == 1 && !qchunk) qq.mode = 2;
-    // MIO_KQ_EARLY=0: K-quant tiles issue their weight loads after the producers' wait (A/B)
-    static const bool early = !(getenv("MIO_KQ_EARLY") && getenv("MIO_KQ_EARLY")[0] == '0');
-    qq.early = early ? 1 : 0;
+    if (q.mode == 1 && !sw.qchunk) qq.mode = 2;
+    qq.early = sw.early ? 1 : 0;
     const int nq = qq.mode == 1 ? a.nt * ((a.K + 2047) / 2048) : a.nt;
-    const dim3 grid(nq + tiles);
     auto go = [&](auto kern) {
-        if (lds > 64 * 1024) allow_lds_mmq(reinterpret_cast<const void *>(kern));
-        hipLaunchKernelGGL(kern, grid, dim3(MMQ_NT), lds, s, sg[0], sg[1], sg[2], a, qq);
+        launch_tiles(kern, dim3(nq + tiles), lds, s, sg[0], sg[1], sg[2], a, qq);
         return true;
     };
-    const int np = pick_np(a.K);
-    if (mode == MMQ_STORE && nseg == 3 && q.mode == 0 && np == 1 && types[0] == 12 && types[1] == 12) {
-        if (types[2] == 12) return go(k_mmq16<12, 12, 12, MMQ_STORE, 0, 1, 0>);
-        if (types[2] == 14) return go(k_mmq16<12, 12, 14, MMQ_STORE, 0, 1, 0>);
+    const int np = pick_np(a.K), T = types[0];
+    const bool q8_one_pass = T == 8 && a.K % 256 == 0 && a.K <= 2048;
+    if (mode == MMQ_STORE && nseg == 3 && q.mode == 0 && np == 1 && types[1] == T) {
+        // q|k|v (RMSNorm input, one pass): every K-quant model, v of q's type or the *_K_M mixes' Q6_K
+        if (T == 12 && types[2] == 12) return go(k_mmq16<12, 12, 12, MMQ_STORE, 0, 1, 0>);
+        if (T == 12 && types[2] == 14) return go(k_mmq16<12, 12, 14, MMQ_STORE, 0, 1, 0>);
+        if (T == 13 && types[2] == 13) return go(k_mmq16<13, 13, 13, MMQ_STORE, 0, 1, 0>);
+        if (T == 13 && types[2] == 14) return go(k_mmq16<13, 13, 14, MMQ_STORE, 0, 1, 0>);
+        if (T == 14 && types[2] == 14) return go(k_mmq16<14, 14, 14, MMQ_STORE, 0, 1, 0>);  // all-Q6_K files
+        // Q8_0 models whose n_embd is a multiple of 256 up to 2048 (the others keep q|k|v on the
+        // dot4 engine, quantizing in that launch)
+        if (q8_one_pass && types[2] == 8) return go(k_mmq16<8, 8, 8, MMQ_STORE, 1, 1, 0>);
     }
-    if (mode == MMQ_STORE && nseg == 3 && q.mode == 0 && np == 1 && types[0] == 13 && types[1] == 13) {
-        if (types[2] == 13) return go(k_mmq16<13, 13, 13, MMQ_STORE, 0, 1, 0>);
-        if (types[2] == 14) return go(k_mmq16<13, 13, 14, MMQ_STORE, 0, 1, 0>);
-    }
-    // all-Q6_K files (MOSTLY_Q6_K)
-    if (mode == MMQ_STORE && nseg == 3 && q.mode == 0 && np == 1 && types[0] == 14 && types[1] == 14 && types[2] == 14)
-        return go(k_mmq16<14, 14, 14, MMQ_STORE, 0, 1, 0>);
-    // Q8_0 q|k|v (one pass, K <= 2048) when MIO_BT_FQ=0 takes it off the dot4 in-launch path
-    if (mode == MMQ_STORE && nseg == 3 && q.mode == 0 && np == 1 && types[0] == 8 && types[1] == 8 && types[2] == 8 &&
-        a.K % 256 == 0 && a.K <= 2048)
-        return go(k_mmq16<8, 8, 8, MMQ_STORE, 1, 1, 0>);
     if (mode == MMQ_SWIGLU && nseg == 1 && q.mode == 0 && np == 1) {
-        // Q4_K / Q5_K / Q6_K gate|up
-        auto kq_up = [&]<int T>() {
-            // the tokens are quantized behind producer workgroups: the walk quantizing its <= 8
-            // tokens in its own prologue measured 8 streams 1.7B 1.366 vs 1.252 ms per step
-            // (profiles/r06/bt_iq_ab.txt): one wave per token quantizing 8 superblocks in a row is
-            // a longer chain than the producers' hop
-            const int nl = n_cu() - a.nt;  // the producers keep CUs of their own
-            if (a.K % 256 == 0 && a.K <= 2048 && tiles > nl && nl > 0 && mmq_loop_on() && (kq_loop_mask() & 2)) {
-                auto kern = k_mmq16_loop_kq<T, MMQ_SWIGLU, 1, 0>;
-                if (lds > 64 * 1024) allow_lds_mmq(reinterpret_cast<const void *>(kern));
-                hipLaunchKernelGGL(kern, dim3(a.nt + nl), dim3(MMQ_NT), lds, s, sg[0], a, q, tiles);
-                return true;
-            }
-            return go(k_mmq16<T, -1, -1, MMQ_SWIGLU, 0, 1, 0>);
+        // gate|up (RMSNorm input, one pass): every K-quant model, and Q8_0 where both of the
+        // model's one-pass pair conditions hold (launch_layers' use_mmq). More tiles than the CUs
+        // the producers leave: the walk. The tokens are quantized behind producer workgroups: the
+        // walk quantizing its <= 8 tokens in its own prologue measured 8 streams 1.7B 1.366 vs
+        // 1.252 ms per step (profiles/r06/bt_iq_ab.txt): one wave per token quantizing 8
+        // superblocks in a row is a longer chain than the producers' hop
+        const int nl = n_cu() - a.nt;  // the producers keep CUs of their own
+        auto walk = [&](auto kern) {
+            launch_walk(kern, a.nt + nl, lds, s, sg[0], a, q, tiles);
+            return true;
         };
-        if (types[0] == 12) return kq_up.template operator()<12>();
-        if (types[0] == 13) return kq_up.template operator()<13>();
-        if (types[0] == 14) return kq_up.template operator()<14>();
-        if (types[0] == 8 && a.K % 256 == 0 && a.K <= 2048) {
-            const int nl = n_cu() - a.nt;  // the producers keep CUs of their own
-            if (tiles > nl && nl > 0 && mmq_loop_on()) {
-                auto kern = k_mmq16_loop<MMQ_SWIGLU, 1, 0>;
-                if (lds > 64 * 1024) allow_lds_mmq(reinterpret_cast<const void *>(kern));
-                hipLaunchKernelGGL(kern, dim3(a.nt + nl), dim3(MMQ_NT), lds, s, sg[0], a, q, tiles);
-                return true;
-            }
-            return go(k_mmq16<8, -1, -1, MMQ_SWIGLU, 1, 1, 0>);
-        }
+        const bool w = walks(T, a.K, tiles, nl, 2);
+        auto kq_up = [&]<int TK>() {
+            return w ? walk(k_mmq16_loop_kq<TK, MMQ_SWIGLU, 1, 0>) : go(k_mmq16<TK, -1, -1, MMQ_SWIGLU, 0, 1, 0>);
+        };
+        if (T == 12) return kq_up.template operator()<12>();
+        if (T == 13) return kq_up.template operator()<13>();
+        if (T == 14) return kq_up.template operator()<14>();
+        if (q8_one_pass) return w ? walk(k_mmq16_loop<MMQ_SWIGLU, 1, 0>) : go(k_mmq16<8, -1, -1, MMQ_SWIGLU, 1, 1, 0>);
     }
     if (mode == MMQ_RESID && nseg == 1 && q.mode == 1 && np == 3) {
-        if (types[0] == 12) return go(k_mmq16<12, -1, -1, MMQ_RESID, 0, 3, 1>);
-        if (types[0] == 13) return go(k_mmq16<13, -1, -1, MMQ_RESID, 0, 3, 1>);
-        if (types[0] == 14) return go(k_mmq16<14, -1, -1, MMQ_RESID, 0, 3, 1>);
+        // down (plain h rows of 3 passes): every K-quant model
+        if (T == 12) return go(k_mmq16<12, -1, -1, MMQ_RESID, 0, 3, 1>);
+        if (T == 13) return go(k_mmq16<13, -1, -1, MMQ_RESID, 0, 3, 1>);
+        if (T == 14) return go(k_mmq16<14, -1, -1, MMQ_RESID, 0, 3, 1>);
     }
-    // Q8_0 down (multi-pass pair path) when MIO_MMQ_MASK puts it on the matrix cores
-    if (mode == MMQ_RESID && nseg == 1 && q.mode == 1 && types[0] == 8 && a.K % 256 == 0 && a.K > 2048) {
+    // Q8_0 down (multi-pass pair path): at 9 to 16 streams, or with MIO_MMQ=1 (up to 8 it stays on
+    // the dot4 engine: 2.010 vs 1.984 ms and 171.2 vs 179.4x with it here)
+    if (mode == MMQ_RESID && nseg == 1 && q.mode == 1 && T == 8 && a.K % 256 == 0 && a.K > 2048) {
         if (np == 3) return go(k_mmq16<8, -1, -1, MMQ_RESID, 2, 3, 1>);
         if (np == 6) return go(k_mmq16<8, -1, -1, MMQ_RESID, 2, 6, 1>);
     }

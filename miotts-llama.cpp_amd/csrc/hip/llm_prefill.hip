@@ -21,6 +21,7 @@
 // same per-superblock integer sums, the same pass order per row, the same online-softmax
 // order): the K/V cache and the last token's logits equal a token-by-token decode bit for
 // bit (tests/test_llm_gpu.py::test_batched_prefill_matches_sequential).
+#include "common.h"
 #include "llm_device.h"
 #include "llm_mmq.h"
 #include "llm_quant_producer.h"
@@ -33,8 +34,6 @@
 
 namespace mio {
 namespace {
-
-constexpr int LDS_MAX = 160 * 1024;
 
 // ------------------------------------------------------------------ LDS layout
 // act[t] = {qs i8[K] | d f32[K/32+8] | bs i16[K/16+8]} x nt | resid f32[MW][nt * rpw] (the
@@ -1022,25 +1021,6 @@ void launch_pf_attention(int G, dim3 grid, hipStream_t s, const LlmDims &d, cons
     }
 }
 
-// Dynamic LDS beyond the default 64 KB needs the per-kernel opt-in (once per kernel and
-// device: the attribute applies to the current device; the limit leaves room for the
-// kernel's static LDS). Keyed by (device, kernel address): kernels of one signature share a
-// function type.
-constexpr int LDS_DYN_MAX = LDS_MAX - 1024;
-template <class Kern>
-void allow_lds(Kern k) {
-    static std::mutex mu;
-    static std::vector<std::pair<int, const void *>> done;
-    const void *p = reinterpret_cast<const void *>(k);
-    int dev = 0;
-    hipGetDevice(&dev);
-    std::lock_guard<std::mutex> lk(mu);
-    for (const auto &q : done)
-        if (q.first == dev && q.second == p) return;
-    hipFuncSetAttribute(p, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DYN_MAX);
-    done.push_back({dev, p});
-}
-
 // residual rows per wave of a matvec over `rows` rows on `grid` workgroups (wave_range)
 int rows_per_wave(int rows, int grid) {
     const int rg = (rows + grid - 1) / grid;
@@ -1069,323 +1049,344 @@ PrefillBuffers shifted(const LlmDims &d, const PrefillBuffers &pb, int t, int K,
     return q;
 }
 
+// ------------------------------------------------------------------ switches
+// Every environment switch of the multi-token layers, read once per process.
+struct LayerSwitches {
+    // MIO_MMQ=0 / 1 forces one matvec engine; unset (-1): the int8 matrix cores (llm_mmq.hip)
+    // above 8 tokens per launch, the dot4 streaming engine or the per-site set of plan() up to 8
+    // (both bit-exact with the decode step). Same-box A/B, aggregate x realtime: 8 streams 1.7B
+    // Q4_K_M dot4 139 / MMQ 133, 2.6B Q8_0 101 / 80; 16 streams 2.6B Q8_0 134 / 144; a 64-token
+    // prefill chunk 10.4 / 2.7 ms.
+    int mmq = env_int("MIO_MMQ", -1, -1, 1);
+    // MIO_BT_FQ (bits: 1 q|k|v, 2 gate|up; unset (-1): the policy of LayerRun::xpre): launches of
+    // <= 8 tokens over K <= 2048 RMSNorm + quantize in the launch from inputs loaded ahead of the
+    // weights (xpre), on the dot4 engine, instead of behind a k_bt_quant launch (and, for q|k|v, on
+    // the matrix cores). 8-stream steps (graph; profiles/r04_fq_ab.txt): 2.6B Q8_0 2.354 ms with
+    // q|k|v only, 2.362 both, 2.488 neither or gate|up only; 1.7B Q4_K_M 1.837 / 1.881 / 1.843 /
+    // 1.891
+    int fq = env_int("MIO_BT_FQ", -1, -1, 3);
+    // MIO_BT_QF (default 1): in the batched decode, the 16x16 matmuls quantize their input in
+    // the launch (launch_mmq_q: producer workgroups + counters) instead of behind a k_bt_quant
+    // launch; the counter sets alternate per fused launch (k_bt_sample zeroes both at the end of
+    // each step)
+    bool qf = env_flag("MIO_BT_QF", true);
+    // MIO_BT_DQ=0: the dot4 down keeps its k_bt_quant_split launch (the reference of
+    // test_batch_engine_switches_bit_identical)
+    bool dq = env_flag("MIO_BT_DQ", true);
+    // MIO_ATT_Q=0: a k_bt_quant launch writes the O matvec's act records instead of the attention
+    // merger
+    bool att_q = env_flag("MIO_ATT_Q", true);
+    // MIO_BT_LM_MMQ=0: the batched lm_head on k_bt_lm_head (dot4, sampling partials fused) instead
+    // of the int8 matrix cores (launch_mmq, the dot engine's values bit for bit) + the partials from
+    // the logits (k_bt_gumbel): 8 streams 1.7B 217.0-217.5x vs 214.5-215.0x with k_bt_lm_head, C4
+    // 179.5-179.6 vs 177.3-177.5x (profiles/r05_bt_lm_mmq_ab.txt)
+    bool lm_mmq = env_flag("MIO_BT_LM_MMQ", true);
+};
+const LayerSwitches &switches() {
+    static const LayerSwitches sw;
+    return sw;
+}
+
 // act records of nt tokens (k_bt_quant): mode 0 RMSNorm(src) * w, 1 src; ak = akind of the
 // consuming weights (0 Q8_0, 1 Q8_K, 2 BF16)
 void launch_quant(const LlmDims &d, int mode, const float *src, int K, const float *w, int ak,
                   const PrefillBuffers &pb, int nt, hipStream_t s) {
-    // plain rows: one workgroup per (token, 2048 elements) instead of per token (MIO_QSPLIT=0:
-    // per token, for A/B)
-    static const bool qsplit = !(getenv("MIO_QSPLIT") && getenv("MIO_QSPLIT")[0] == '0');
-    if (mode == 1 && qsplit && K % 256 == 0 && ak != 2) {
+    // plain int8 rows of whole superblocks: one workgroup per (token, 2048 elements)
+    if (mode == 1 && K % 256 == 0 && ak != 2) {
         hipLaunchKernelGGL(k_bt_quant_split, dim3(nt, (K + 2047) / 2048), dim3(MT), 0, s, src, K, ak, pb);
         return;
     }
-    const int np = pick_np(K);
-    auto go = [&]<int NP>() {
+    dispatch_np(K, [&]<int NP>() {
         const size_t lds = smem_bytes(K);
         if (mode == 0)
             hipLaunchKernelGGL((k_bt_quant<NP, 0>), dim3(nt), dim3(MT), lds, s, d, src, K, w, ak, pb);
         else
             hipLaunchKernelGGL((k_bt_quant<NP, 1>), dim3(nt), dim3(MT), lds, s, d, src, K, w, ak, pb);
-    };
-    if (np == 1)
-        go.template operator()<1>();
-    else if (np == 3)
-        go.template operator()<3>();
-    else
-        go.template operator()<6>();
+    });
 }
 
-// Every layer for nt tokens of pb (residual streams pb.x in, out): one weight pass per
-// matvec launch (sub-launches only where a token range does not fit LDS), each preceded by
-// the launch that quantizes its activations once (k_bt_quant).
-// decode: every token is its own sequence (the batched decode step): attention per token
-// with the RoPE / KV append inside (k_bt_attention).
+// a kernel of MT threads that may need more than 64 KB of dynamic LDS
+template <class Kern, class... Args>
+void launch_lds(Kern k, int grid, size_t lds, hipStream_t s, const Args &...args) {
+    allow_lds(k);
+    hipLaunchKernelGGL(k, dim3(grid), dim3(MT), lds, s, args...);
+}
+
+// ------------------------------------------------------------------ matvec sites
+// One matvec of a layer (or the lm_head), described: what it multiplies, where its input comes
+// from and what happens to its output. plan() decides how it runs, run() runs it.
+enum SiteKind { kSiteQkv = 0, kSiteO = 1, kSiteGateUp = 2, kSiteDown = 3, kSiteConvIn, kSiteConvOut, kSiteLmHead };
+enum SiteInput {
+    kInNorm,     // RMSNorm(src) * norm_w
+    kInPlain,    // the rows of src
+    kInRecords,  // act records an earlier launch wrote (the attention merger, k_bt_conv)
+};
+struct Site {
+    SiteKind kind;
+    QMat w[3];  // the matrices whose rows follow each other in out (q | k | v: 3, else 1)
+    int nseg;
+    QMat up;  // SwiGLU: the up matrix beside w[0] = gate
+    int K;
+    SiteInput in;
+    const float *src, *norm_w;
+    int epi;  // MMQ_STORE / MMQ_RESID (out += .) / MMQ_SWIGLU
+    float *out;
+    int ld;  // token stride of out
+    int qs;  // token stride of pb.qkv in this layer (the dot4 kernels' shifted buffers)
+};
+
+enum Engine {
+    kDot4,       // streaming rows over act records
+    kDot4Xpre,   // the same, RMSNorm + quantize in the launch (xpre; FQ = 2)
+    kDot4DownQ,  // the dot4 down with producer workgroups quantizing h (k_pf_ffn_down_q)
+    kMmq,        // int8 matrix cores over act records (launch_mmq)
+    kMmqQ,       // int8 matrix cores with producer workgroups (launch_mmq_q); a shape without a
+                 // fused kernel falls back to kMmq
+};
+struct Plan {
+    Engine engine;
+    bool quant_launch;  // a k_bt_quant launch writes the act records first (kMmqQ: on its fall-back)
+};
+
+// Q8_0 over this K runs the one-pass 16-B pair kernels of the matrix cores
+bool q8_one_pass(int K) { return K % 256 == 0 && K <= 2048; }
+
+// Who writes the O matvec's act records: the attention merger when every kv head's G * hd outputs
+// are whole quantization blocks (0: Q8_0 blocks, 1: Q8_K superblocks), else (-1) a k_bt_quant
+// launch; BF16 always the launch.
+int merger_records(const LayerSwitches &sw, int o_type, int gh) {
+    if (!sw.att_q || o_type == 30) return -1;
+    if (o_type == 8) return gh % 32 == 0 ? 0 : -1;
+    return gh % 256 == 0 ? 1 : -1;
+}
+
+// The multi-token layers of one launch_layers / launch_batch_step call: nt tokens of pb.
+// decode: every token is its own sequence (the batched decode step).
+struct LayerRun {
+    const LlmDims &d;
+    const PrefillBuffers &pb;
+    int nt;
+    bool decode;
+    hipStream_t s;
+    const LayerSwitches &sw = switches();
+    int set = 0;  // the producer counter set of the next fused launch
+
+    bool mmq_all() const { return sw.mmq >= 0 ? sw.mmq != 0 : nt > 8; }
+    // producer workgroups exist in the batched decode only (the counters are the step's)
+    bool producers() const { return decode && sw.qf && pb.qcnt; }
+
+    // At <= 8 tokens the engine is chosen per site (bit `kind` set = int8 MFMA). r04: the 16x16
+    // MFMA tiles load 16 B per lane (llm_mmq.hip, swap_halves) and every K-quant matvec runs on
+    // the matrix cores (8-stream 1.7B Q4_K_M step 1.516 ms vs 1.640 with q|k|v + gate|up only and
+    // 1.676 before the 16-B loads, profiles/r04_batch8_mmq16_ab.txt); Q8_0 (one-pass kernels
+    // compiled with the pair path alone, k_mmq16 P1): O and gate|up on MFMA too where their 16-B
+    // pair kernels apply (both K one pass), q|k|v on the dot4 engine quantizing in the launch or
+    // on MFMA with producers, down on dot4 (2.6B 8-stream step 2.026 ms vs 2.059 with q|k|v only,
+    // 2.061 adding down; down on MFMA again 2.010 vs 1.984 ms and 171.2 vs 179.4x).
+    // BF16 weights: the streaming dot engine (v_dot2 in the decode's lane order) at any token
+    // count; the matrix-core matmuls are int8.
+    bool use_mmq(int kind, int type) const {
+        const bool q8_o_gateup_one_pass = q8_one_pass(d.n_embd) && q8_one_pass(d.n_head * d.hd);
+        const int mask = type == 8 ? (q8_o_gateup_one_pass ? 7 : 1) : 15;
+        return type != 30 && (mmq_all() || (nt <= 8 && sw.mmq < 0 && ((mask >> kind) & 1)));
+    }
+    // xpre (bit 0 q|k|v, 1 gate|up). Default: Q8_0 only; q|k|v where the matrix cores cannot
+    // quantize it in the launch themselves (r05: C4 169.0-169.3x with q|k|v on k_mmq16 + producers
+    // vs 161.8-162.2x on dot4, profiles/r05_c4_qkv_mfma_ab.txt), gate|up where n_embd has no
+    // one-pass pair kernel; none for the K-quants (every matvec on the matrix cores).
+    bool xpre(int bit, int type) const {
+        const bool qkv_producers = producers() && q8_one_pass(d.n_embd);
+        const bool on = sw.fq >= 0 ? ((sw.fq >> bit) & 1) != 0
+                                   : (type == 8 && (bit == 0 ? !qkv_producers : !q8_one_pass(d.n_embd)));
+        return !mmq_all() && nt <= MW && pick_np(d.n_embd) == 1 && on && type != 30;
+    }
+
+    Plan plan(const Site &st) const {
+        const QMat &W = st.w[0];
+        switch (st.kind) {
+            case kSiteQkv:
+            case kSiteGateUp:
+                if (xpre(st.kind == kSiteQkv ? 0 : 1, W.type)) return {kDot4Xpre, false};
+                if (use_mmq(st.kind, W.type)) return {producers() ? kMmqQ : kMmq, true};
+                return {kDot4, true};
+            case kSiteO: return {use_mmq(st.kind, W.type) ? kMmq : kDot4, st.in != kInRecords};
+            case kSiteDown:
+                if (use_mmq(st.kind, W.type)) return {producers() ? kMmqQ : kMmq, true};
+                // the dot4 down quantizing h in the launch (Q8_0 / Q8_K, every token in one launch)
+                if (producers() && sw.dq && st.K % 256 == 0 && akind(W.type) != 2 &&
+                    tokens_per_launch(rec_k(st.K, W.type), nt, rows_per_wave(W.rows, matvec_grid(d, W.rows))) >= nt)
+                    return {kDot4DownQ, false};
+                return {kDot4, true};
+            // lfm2: the int8 types always on the matrix cores, BF16 on the streaming dot engine (both
+            // bit-exact with the decode step's matvec at any token count; the loader's bf16_mt keeps
+            // a BF16 matrix beside an int8 one off this engine)
+            case kSiteConvIn:
+            case kSiteConvOut: return {W.type == 30 ? kDot4 : kMmq, st.in != kInRecords};
+            // k_bt_lm_head (kDot4) is launch_batch_step's own
+            case kSiteLmHead: break;
+        }
+        return {sw.lm_mmq && W.type != 30 ? kMmq : kDot4, true};
+    }
+
+    void quant(const Site &st) const {
+        launch_quant(d, st.in == kInNorm ? 0 : 1, st.src, st.K, st.norm_w, akind(st.w[0].type), pb, nt, s);
+    }
+
+    // f(MmqQuant of the current counter set) launches a kernel with producer workgroups for the
+    // site's input, or returns false; the sets alternate per such launch.
+    template <class F>
+    bool with_producers(const Site &st, F &&f) {
+        const MmqQuant q{st.src, st.norm_w, st.in == kInNorm ? 0 : 1, d.eps, pb.qcnt + 512 * set,
+                         pb.qcnt + 512 * (1 - set), pb.qcnt + kQcntFlag};
+        if (!f(q)) return false;
+        set ^= 1;
+        return true;
+    }
+
+    // sub-launches over token ranges that fit LDS: f(n, shifted buffers)
+    // (K = the act record's K, rec_k: twice the row length for BF16 weights)
+    template <class F>
+    void over_tokens(int K, int rpw, int qs, F &&f) const {
+        const int per = tokens_per_launch(K, nt, rpw);
+        for (int t = 0; t < nt; t += per) f(nt - t < per ? nt - t : per, shifted(d, pb, t, K, qs));
+    }
+
+    void dot4(const Site &st, bool xp) const {
+        const QMat &W = st.w[0];
+        const int KR = rec_k(st.K, W.type);
+        if (st.kind == kSiteQkv || st.kind == kSiteConvIn) {
+            LayerW V{};
+            V.wq = W, V.wk = st.w[1], V.wv = st.w[2];
+            if (st.kind == kSiteConvIn) {
+                // the decode step's view of in_proj (kConvIn): B | C rows as q, no k, X rows as v
+                V.wq = qmat_rows(W, 0, 2 * st.K);
+                V.wk = qmat_rows(W, 2 * st.K, 0);
+                V.wv = qmat_rows(W, 2 * st.K, st.K);
+            }
+            int GW, g_qk;
+            attn_in_grid(d, V, GW, g_qk);
+            over_tokens(KR, 0, st.qs, [&](int n, const PrefillBuffers &q) {
+                const size_t lds = pf_lds_bytes(KR, n, 0);
+                dispatch_nt<true>(st.K, W.type, [&]<int NP, int TQ>() {
+                    dispatch_v<TQ>(V.wv.type, [&]<int TV>() {
+                        if constexpr (NP == 1 && TQ != 30) {
+                            if (xp)
+                                return launch_lds(k_pf_attn_in<NP, TQ, TV, 2>, GW, lds, s, d, st.norm_w, V.wq, V.wk, V.wv,
+                                                  g_qk, q, n, st.ld);
+                        }
+                        launch_lds(k_pf_attn_in<NP, TQ, TV>, GW, lds, s, d, st.norm_w, V.wq, V.wk, V.wv, g_qk, q, n,
+                                   st.ld);
+                    });
+                });
+            });
+        } else if (st.kind == kSiteGateUp) {
+            const int grid = matvec_grid(d, W.rows);
+            over_tokens(KR, 0, st.qs, [&](int n, const PrefillBuffers &q) {
+                const size_t lds = pf_lds_bytes(KR, n, 0);
+                dispatch_nt<true>(st.K, W.type, [&]<int NP, int T>() {
+                    if constexpr (NP == 1 && T != 30) {
+                        if (xp) return launch_lds(k_pf_ffn_in<NP, T, 2>, grid, lds, s, d, st.norm_w, W, st.up, q, n);
+                    }
+                    launch_lds(k_pf_ffn_in<NP, T>, grid, lds, s, d, st.norm_w, W, st.up, q, n);
+                });
+            });
+        } else {  // x += W act: O / out_proj, down
+            const int grid = matvec_grid(d, W.rows), rpw = rows_per_wave(W.rows, grid);
+            over_tokens(KR, rpw, st.qs, [&](int n, const PrefillBuffers &q) {
+                const size_t lds = pf_lds_bytes(KR, n, rpw);
+                dispatch_nt<true>(st.K, W.type, [&]<int NP, int T>() {
+                    if (st.kind == kSiteDown)
+                        launch_lds(k_pf_ffn_down<NP, T>, grid, lds, s, d, W, q, n, rpw);
+                    else
+                        launch_lds(k_pf_attn_out<NP, T>, grid, lds, s, d, W, q, n, rpw);
+                });
+            });
+        }
+    }
+
+    void down_q(const Site &st) {
+        const QMat &W = st.w[0];
+        const int grid = matvec_grid(d, W.rows), rpw = rows_per_wave(W.rows, grid);
+        const int nch = (st.K + 2047) / 2048;
+        const size_t lds = std::max(pf_lds_bytes(rec_k(st.K, W.type), nt, rpw), act_bytes(st.K));
+        with_producers(st, [&](const MmqQuant &q) {
+            dispatch_nt<true>(st.K, W.type, [&]<int NP, int T>() {
+                launch_lds(k_pf_ffn_down_q<NP, T>, nt * nch + grid, lds, s, d, W, pb, nt, rpw, q, nch);
+            });
+            return true;
+        });
+    }
+
+    void run(const Site &st) {
+        const Plan p = plan(st);
+        MmqSeg sg[3] = {};
+        int ty[3] = {};
+        for (int i = 0, off = 0; i < st.nseg; off += st.w[i++].rows) {
+            sg[i] = {st.w[i], mmq_tiles(st.w[i].rows), off};
+            ty[i] = st.w[i].type;
+        }
+        const MmqArgs a{pb.act, act_bytes(st.K), st.K, nt, st.out, st.ld, st.up};
+        if (p.engine == kMmqQ &&
+            with_producers(st, [&](const MmqQuant &q) { return launch_mmq_q(sg, ty, st.nseg, st.epi, a, q, s); }))
+            return;
+        if (p.quant_launch) quant(st);
+        switch (p.engine) {
+            case kMmq:
+            case kMmqQ: launch_mmq(sg, ty, st.nseg, st.epi, a, s); break;
+            case kDot4: dot4(st, false); break;
+            case kDot4Xpre: dot4(st, true); break;
+            case kDot4DownQ: down_q(st); break;
+        }
+    }
+
+    // RoPE + K/V rows + attention of nt tokens; the merger writes pb.att and, with att_q >= 0,
+    // the O matvec's act records. decode: all inside k_bt_attention, per token.
+    void attention(const LayerW &L, _Float16 *kc, _Float16 *vc, int n_chunks, int att_q) const {
+        const int G = d.n_head / d.n_kv;
+        const dim3 grid(d.n_kv * nt, n_chunks);
+        dispatch_hd(d.hd, [&]<int HD>() {
+            if (decode) return launch_bt_attention<HD>(G, grid, s, d, L, kc, vc, pb, att_q);
+            hipLaunchKernelGGL((k_pf_rope<HD>), dim3(d.n_head + d.n_kv, nt), dim3(64), 0, s, d, L.q_norm, L.k_norm,
+                               L.bqkv, kc, vc, pb);
+            launch_pf_attention<HD>(G, grid, s, d, kc, vc, pb, att_q);
+        });
+    }
+
+    // lfm2: the gated short conv between in_proj and out_proj, writing out_proj's act records,
+    // then the ring update
+    void conv(const LayerW &L, float *ring) const {
+        const int ak = akind(L.out_proj.type);
+        dispatch_np(d.n_embd, [&]<int NP>() {
+            hipLaunchKernelGGL((k_bt_conv<NP>), dim3(nt), dim3(MT), smem_bytes(d.n_embd), s, d, L.conv_w, ring, ak, pb);
+        });
+        hipLaunchKernelGGL(k_bt_conv_state, dim3(nt), dim3(ST), 0, s, d, ring, pb, nt);
+    }
+};
+
+// Every layer for nt tokens of pb (residual streams pb.x in, out): one weight pass per matvec
+// site (sub-launches only where a token range does not fit LDS).
 void launch_layers(const LlmDims &d, const LayerW *layers, int n_layer, _Float16 *kcache, _Float16 *vcache,
                    const PrefillBuffers &pb, int nt, int n_chunks, bool decode, hipStream_t s) {
+    LayerRun r{d, pb, nt, decode, s};
     const size_t layer_kv = (size_t)d.n_kv * d.n_ctx * d.hd;
-    const int G = d.n_head / d.n_kv;
-    // sub-launches over token ranges that fit LDS: f(t_off, n, shifted buffers)
-    // (K = the act record's K, rec_k: twice the row length for BF16 weights)
-    // qs = the token stride of pb.qkv in this layer
-    auto over_tokens = [&](int K, int rpw, int qs, auto &&f) {
-        const int per = tokens_per_launch(K, nt, rpw);
-        for (int t = 0; t < nt; t += per) f(t, nt - t < per ? nt - t : per, shifted(d, pb, t, K, qs));
-    };
-    // matvecs on the int8 matrix cores (llm_mmq.hip) above 8 tokens per launch, the dot4
-    // streaming engine below up to 8 (both bit-exact with the decode step). Same-box A/B,
-    // aggregate x realtime: 8 streams 1.7B Q4_K_M dot4 139 / MMQ 133, 2.6B Q8_0 101 / 80;
-    // 16 streams 2.6B Q8_0 134 / 144; a 64-token prefill chunk 10.4 / 2.7 ms.
-    // MIO_MMQ=0 / 1 forces one engine.
-    static const int mmq_env = getenv("MIO_MMQ") ? atoi(getenv("MIO_MMQ")) : -1;
-    const bool mmq_all = mmq_env >= 0 ? mmq_env != 0 : nt > 8;
-    // At <= 8 tokens the engine is chosen per launch kind (bit 0 attn_in, 1 attn_out, 2 ffn_in,
-    // 3 ffn_down set = int8 MFMA). r04: the 16x16 MFMA tiles load 16 B per lane (llm_mmq.hip,
-    // swap_halves) and every K-quant matvec runs on the matrix cores (8-stream 1.7B Q4_K_M step
-    // 1.516 ms vs 1.640 with q|k|v + gate|up only and 1.676 before the 16-B loads,
-    // profiles/r04_batch8_mmq16_ab.txt); Q8_0 (one-pass kernels compiled with the pair path
-    // alone, k_mmq16 P1): O and gate|up on MFMA too, q|k|v on the dot4 engine quantizing in the
-    // launch, down on dot4 (2.6B 8-stream step 2.026 ms vs 2.059 with q|k|v only, 2.061 adding
-    // down).
-    // MIO_MMQ_MASK overrides the set for every type (A/B).
-    static const int mmq_mask = getenv("MIO_MMQ_MASK") ? atoi(getenv("MIO_MMQ_MASK")) : -1;
-    auto use_mmq = [&](int kind, int type) {
-        // Q8_0 O and gate|up only where their 16-B pair kernels apply (K % 256 == 0, one pass)
-        const bool q8_pair = d.n_embd % 256 == 0 && d.n_embd <= 2048 && (d.n_head * d.hd) % 256 == 0 &&
-                             d.n_head * d.hd <= 2048;
-        const int mask = mmq_mask >= 0 ? mmq_mask : (type == 8 ? (q8_pair ? 7 : 1) : 15);
-        // BF16 weights: the streaming dot engine (v_dot2 in the decode's lane order) at any token
-        // count; the matrix-core matmuls are int8
-        return type != 30 && (mmq_all || (nt <= 8 && mmq_env < 0 && ((mask >> kind) & 1)));
-    };
-    const bool mmq = mmq_all;
-    // MIO_BT_FQ (bits: 1 attn_in, 2 ffn_in; default below): launches of <= 8 tokens over K <= 2048
-    // RMSNorm + quantize in the launch from inputs loaded ahead of the weights (xpre), on the
-    // dot4 engine, instead of behind a k_bt_quant launch (and, for q|k|v, on the matrix cores).
-    // 8-stream steps (graph; profiles/r04_fq_ab.txt): 2.6B Q8_0 2.354 ms with attn_in only,
-    // 2.362 both, 2.488 neither or ffn_in only; 1.7B Q4_K_M 1.837 / 1.881 / 1.843 / 1.891
-    // MIO_BT_ATT=0: the batched decode step uses k_pf_rope + k_pf_attention (A/B)
-    static const bool bt_att = !(getenv("MIO_BT_ATT") && getenv("MIO_BT_ATT")[0] == '0');
-    decode = decode && bt_att;
-    // MIO_BT_QF (default 1): in the batched decode, the 16x16 matmuls quantize their input in
-    // the launch (launch_mmq_q: producer workgroups + counters) instead of behind a k_bt_quant
-    // launch; the counter sets alternate per fused launch (k_bt_sample zeroes both at the end of
-    // each step)
-    static const bool qf_env = !(getenv("MIO_BT_QF") && getenv("MIO_BT_QF")[0] == '0');
-    // MIO_BT_DQ=0: the dot4 down keeps its k_bt_quant_split launch (A/B)
-    static const bool dq_env = !(getenv("MIO_BT_DQ") && getenv("MIO_BT_DQ")[0] == '0');
-    // default: the Q8_0 q|k|v in-launch on dot4 only where the matrix cores cannot quantize in
-    // the launch themselves (r05: C4 169.0-169.3x with q|k|v on k_mmq16 + producers vs
-    // 161.8-162.2x on dot4, profiles/r05_c4_qkv_mfma_ab.txt); none for the K-quants (every
-    // matvec on the matrix cores)
-    static const int fq2_env = getenv("MIO_BT_FQ") ? atoi(getenv("MIO_BT_FQ")) : -1;
-    const bool qkv_qf = decode && qf_env && pb.qcnt && d.n_embd % 256 == 0 && d.n_embd <= 2048;
-    auto fq2 = [&](int kind, int type) {
-        const bool q8_pair = d.n_embd % 256 == 0 && d.n_embd <= 2048;
-        const bool on = fq2_env >= 0 ? ((fq2_env >> kind) & 1) != 0 : (type == 8 && (kind == 0 ? !qkv_qf : !q8_pair));
-        return !mmq && nt <= MW && pick_np(d.n_embd) == 1 && on && type != 30;
-    };
-    static const bool att_q_env = !(getenv("MIO_ATT_Q") && getenv("MIO_ATT_Q")[0] == '0');
-    int qi = 0;
-    auto fused_q = [&](const MmqSeg *sg, const int *ty, int nseg, int mode, const MmqArgs &a, const float *src,
-                       const float *nw, int qmode) {
-        if (!decode || !qf_env || !pb.qcnt) return false;
-        const int set = qi & 1;
-        const MmqQuant q{src, nw, qmode, d.eps, pb.qcnt + 512 * set, pb.qcnt + 512 * (1 - set), pb.qcnt + kQcntFlag};
-        if (!launch_mmq_q(sg, ty, nseg, mode, a, q, s)) return false;
-        ++qi;
-        return true;
-    };
-    const int QD = (d.n_head + 2 * d.n_kv) * d.hd;
-    // a kernel template over the pass count of K
-    auto by_np = [](int K, auto &&f) {
-        const int np = pick_np(K);
-        if (np == 1)
-            f.template operator()<1>();
-        else if (np == 3)
-            f.template operator()<3>();
-        else
-            f.template operator()<6>();
-    };
+    const int n = d.n_embd, QD = (d.n_head + 2 * d.n_kv) * d.hd;
     for (int il = 0; il < n_layer; ++il) {
         const LayerW &L = layers[il];
         if (L.conv) {
-            // lfm2 short-conv layer: RMSNorm + in_proj -> B | C | X rows, the gated conv (k_bt_conv)
-            // -> out_proj -> x += ., ring update. The int8 types always on the matrix cores, BF16
-            // on the streaming dot engine (both bit-exact with the decode step's matvec at any
-            // token count; the loader's bf16_mt keeps a BF16 matrix beside an int8 one off this
-            // engine).
-            const int n = d.n_embd;
-            const bool bf = L.in_proj.type == 30;
-            float *ring = pb.ring + (size_t)il * kConvSlots * n;
-            launch_quant(d, 0, pb.x, n, L.attn_norm, akind(L.in_proj.type), pb, nt, s);
-            if (bf) {
-                // the decode step's view of in_proj (kConvIn): B | C rows as q, no k, X rows as v
-                LayerW V = L;
-                V.wq = qmat_rows(L.in_proj, 0, 2 * n);
-                V.wk = qmat_rows(L.in_proj, 2 * n, 0);
-                V.wv = qmat_rows(L.in_proj, 2 * n, n);
-                int GW, g_qk;
-                attn_in_grid(d, V, GW, g_qk);
-                const int KR = rec_k(n, 30);
-                over_tokens(KR, 0, 3 * n, [&](int, int m, const PrefillBuffers &q) {
-                    by_np(n, [&]<int NP>() {
-                        allow_lds(k_pf_attn_in<NP, 30, 30>);
-                        hipLaunchKernelGGL((k_pf_attn_in<NP, 30, 30>), dim3(GW), dim3(MT), pf_lds_bytes(KR, m, 0), s, d,
-                                           L.attn_norm, V.wq, V.wk, V.wv, g_qk, q, m, 3 * n);
-                    });
-                });
-            } else {
-                const MmqSeg sg{L.in_proj, mmq_tiles(L.in_proj.rows), 0};
-                launch_mmq(&sg, &L.in_proj.type, 1, MMQ_STORE, MmqArgs{pb.act, act_bytes(n), n, nt, pb.qkv, 3 * n, {}}, s);
-            }
-            const int ak = akind(L.out_proj.type);
-            by_np(n, [&]<int NP>() {
-                hipLaunchKernelGGL((k_bt_conv<NP>), dim3(nt), dim3(MT), smem_bytes(n), s, d, L.conv_w, ring, ak, pb);
-            });
-            hipLaunchKernelGGL(k_bt_conv_state, dim3(nt), dim3(ST), 0, s, d, ring, pb, nt);
-            if (bf) {
-                const int grid = matvec_grid(d, L.out_proj.rows), rpw = rows_per_wave(L.out_proj.rows, grid);
-                const int KR = rec_k(n, 30);
-                over_tokens(KR, rpw, 3 * n, [&](int, int m, const PrefillBuffers &q) {
-                    by_np(n, [&]<int NP>() {
-                        allow_lds(k_pf_attn_out<NP, 30>);
-                        hipLaunchKernelGGL((k_pf_attn_out<NP, 30>), dim3(grid), dim3(MT), pf_lds_bytes(KR, m, rpw), s, d,
-                                           L.out_proj, q, m, rpw);
-                    });
-                });
-            } else {
-                const MmqSeg so{L.out_proj, mmq_tiles(L.out_proj.rows), 0};
-                launch_mmq(&so, &L.out_proj.type, 1, MMQ_RESID, MmqArgs{pb.act, act_bytes(n), n, nt, pb.x, n, {}}, s);
-            }
+            // lfm2 short-conv layer: RMSNorm + in_proj -> B | C | X rows, the gated conv -> out_proj
+            // -> x += .
+            r.run({kSiteConvIn, {L.in_proj}, 1, {}, n, kInNorm, pb.x, L.attn_norm, MMQ_STORE, pb.qkv, 3 * n, 3 * n});
+            r.conv(L, pb.ring + (size_t)il * kConvSlots * n);
+            r.run({kSiteConvOut, {L.out_proj}, 1, {}, n, kInRecords, nullptr, nullptr, MMQ_RESID, pb.x, n, 3 * n});
         } else {
-            _Float16 *kc = kcache + il * layer_kv, *vc = vcache + il * layer_kv;
-            // the attention merger writes the O matvec's activation records when every kv head's
-            // G * hd outputs are whole quantization blocks (MIO_ATT_Q=0: a k_bt_quant launch)
-            const int gh = G * d.hd;
-            const int att_q = !att_q_env || L.wo.type == 30
-                                  ? -1
-                                  : (L.wo.type == 8 ? (gh % 32 == 0 ? 0 : -1) : (gh % 256 == 0 ? 1 : -1));
-            const bool fa = fq2(0, L.wq.type);
-            const bool mq0 = !fa && use_mmq(0, L.wq.type);
-            const MmqSeg sg0[3] = {{L.wq, mmq_tiles(L.wq.rows), 0}, {L.wk, mmq_tiles(L.wk.rows), L.wq.rows},
-                                   {L.wv, mmq_tiles(L.wv.rows), L.wq.rows + L.wk.rows}};
-            const int ty0[3] = {L.wq.type, L.wk.type, L.wv.type};
-            const MmqArgs a0{pb.act, act_bytes(d.n_embd), d.n_embd, nt, pb.qkv, QD, {}};
-            const bool q0 = mq0 && fused_q(sg0, ty0, 3, MMQ_STORE, a0, pb.x, L.attn_norm, 0);
-            if (!fa && !q0)
-                launch_quant(d, 0, pb.x, d.n_embd, L.attn_norm, akind(L.wq.type), pb, nt, s);
-            if (q0) {
-            } else if (mq0) {
-                launch_mmq(sg0, ty0, 3, MMQ_STORE, a0, s);
-            } else {
-                int GW, g_qk;
-                attn_in_grid(d, L, GW, g_qk);
-                const int KR = rec_k(d.n_embd, L.wq.type);
-                over_tokens(KR, 0, QD, [&](int, int n, const PrefillBuffers &q) {
-                    const size_t lds = pf_lds_bytes(KR, n, 0);
-                    dispatch_nt<true>(d.n_embd, L.wq.type, [&]<int NP, int TQ>() {
-                        auto go = [&]<int TV>() {
-                            if constexpr (NP == 1 && TQ != 30) {
-                                if (fa) {
-                                    allow_lds(k_pf_attn_in<NP, TQ, TV, 2>);
-                                    hipLaunchKernelGGL((k_pf_attn_in<NP, TQ, TV, 2>), dim3(GW), dim3(MT), lds, s, d,
-                                                       L.attn_norm, L.wq, L.wk, L.wv, g_qk, q, n, QD);
-                                    return;
-                                }
-                            }
-                            allow_lds(k_pf_attn_in<NP, TQ, TV>);
-                            hipLaunchKernelGGL((k_pf_attn_in<NP, TQ, TV>), dim3(GW), dim3(MT), lds, s, d, L.attn_norm,
-                                               L.wq, L.wk, L.wv, g_qk, q, n, QD);
-                        };
-                        dispatch_v<TQ>(L.wv.type, go);
-                    });
-                });
-            }
-            if (decode) {
-                const dim3 grid(d.n_kv * nt, n_chunks);
-                if (d.hd == 128)
-                    launch_bt_attention<128>(G, grid, s, d, L, kc, vc, pb, att_q);
-                else
-                    launch_bt_attention<64>(G, grid, s, d, L, kc, vc, pb, att_q);
-            } else {
-                {
-                    const dim3 grid(d.n_head + d.n_kv, nt);
-                    if (d.hd == 128)
-                        hipLaunchKernelGGL((k_pf_rope<128>), grid, dim3(64), 0, s, d, L.q_norm, L.k_norm, L.bqkv, kc,
-                                           vc, pb);
-                    else
-                        hipLaunchKernelGGL((k_pf_rope<64>), grid, dim3(64), 0, s, d, L.q_norm, L.k_norm, L.bqkv, kc,
-                                           vc, pb);
-                }
-                const dim3 grid(d.n_kv * nt, n_chunks);
-                if (d.hd == 128)
-                    launch_pf_attention<128>(G, grid, s, d, kc, vc, pb, att_q);
-                else
-                    launch_pf_attention<64>(G, grid, s, d, kc, vc, pb, att_q);
-            }
-            if (att_q < 0) launch_quant(d, 1, pb.att, L.wo.k, nullptr, akind(L.wo.type), pb, nt, s);
-            if (use_mmq(1, L.wo.type)) {
-                const MmqSeg sg{L.wo, mmq_tiles(L.wo.rows), 0};
-                launch_mmq(&sg, &L.wo.type, 1, MMQ_RESID, MmqArgs{pb.act, act_bytes(L.wo.k), L.wo.k, nt, pb.x, d.n_embd, {}},
-                           s);
-            } else {
-                const int grid = matvec_grid(d, L.wo.rows), rpw = rows_per_wave(L.wo.rows, grid);
-                const int KR = rec_k(L.wo.k, L.wo.type);
-                over_tokens(KR, rpw, QD, [&](int, int n, const PrefillBuffers &q) {
-                    dispatch_nt<true>(L.wo.k, L.wo.type, [&]<int NP, int T>() {
-                        allow_lds(k_pf_attn_out<NP, T>);
-                        hipLaunchKernelGGL((k_pf_attn_out<NP, T>), dim3(grid), dim3(MT), pf_lds_bytes(KR, n, rpw), s,
-                                           d, L.wo, q, n, rpw);
-                    });
-                });
-            }
+            const int att_q = merger_records(r.sw, L.wo.type, d.n_head / d.n_kv * d.hd);
+            r.run({kSiteQkv, {L.wq, L.wk, L.wv}, 3, {}, n, kInNorm, pb.x, L.attn_norm, MMQ_STORE, pb.qkv, QD, QD});
+            r.attention(L, kcache + il * layer_kv, vcache + il * layer_kv, n_chunks, att_q);
+            r.run({kSiteO, {L.wo}, 1, {}, L.wo.k, att_q < 0 ? kInPlain : kInRecords, pb.att, nullptr, MMQ_RESID, pb.x, n,
+                   QD});
         }
-        const bool ff = fq2(1, L.gate.type);
-        const bool mq2 = !ff && use_mmq(2, L.gate.type);
-        const MmqSeg sg2{L.gate, mmq_tiles(L.gate.rows), 0};
-        const MmqArgs a2{pb.act, act_bytes(d.n_embd), d.n_embd, nt, pb.h, d.n_ff, L.up};
-        const bool q2 = mq2 && fused_q(&sg2, &L.gate.type, 1, MMQ_SWIGLU, a2, pb.x, L.ffn_norm, 0);
-        if (!ff && !q2)
-            launch_quant(d, 0, pb.x, d.n_embd, L.ffn_norm, akind(L.gate.type), pb, nt, s);
-        if (q2) {
-        } else if (mq2) {
-            launch_mmq(&sg2, &L.gate.type, 1, MMQ_SWIGLU, a2, s);
-        } else {
-            const int grid = matvec_grid(d, L.gate.rows);
-            const int KR = rec_k(d.n_embd, L.gate.type);
-            over_tokens(KR, 0, QD, [&](int, int n, const PrefillBuffers &q) {
-                dispatch_nt<true>(d.n_embd, L.gate.type, [&]<int NP, int T>() {
-                    if constexpr (NP == 1 && T != 30) {
-                        if (ff) {
-                            allow_lds(k_pf_ffn_in<NP, T, 2>);
-                            hipLaunchKernelGGL((k_pf_ffn_in<NP, T, 2>), dim3(grid), dim3(MT), pf_lds_bytes(d.n_embd, n, 0),
-                                               s, d, L.ffn_norm, L.gate, L.up, q, n);
-                            return;
-                        }
-                    }
-                    allow_lds(k_pf_ffn_in<NP, T>);
-                    hipLaunchKernelGGL((k_pf_ffn_in<NP, T>), dim3(grid), dim3(MT), pf_lds_bytes(KR, n, 0), s, d,
-                                       L.ffn_norm, L.gate, L.up, q, n);
-                });
-            });
-        }
-        const bool mq3 = use_mmq(3, L.down.type);
-        const MmqSeg sg3{L.down, mmq_tiles(L.down.rows), 0};
-        const MmqArgs a3{pb.act, act_bytes(L.down.k), L.down.k, nt, pb.x, d.n_embd, {}};
-        const bool q3 = mq3 && fused_q(&sg3, &L.down.type, 1, MMQ_RESID, a3, pb.h, nullptr, 1);
-        // the dot4 down quantizing h in the launch (Q8_0 / Q8_K, every token in one launch)
-        const int KD = L.down.k, akd = akind(L.down.type);
-        const bool q3d = !mq3 && decode && qf_env && pb.qcnt && dq_env && KD % 256 == 0 && akd != 2 &&
-                         tokens_per_launch(rec_k(KD, L.down.type), nt,
-                                           rows_per_wave(L.down.rows, matvec_grid(d, L.down.rows))) >= nt;
-        if (!q3 && !q3d) launch_quant(d, 1, pb.h, L.down.k, nullptr, akind(L.down.type), pb, nt, s);
-        if (q3) {
-        } else if (mq3) {
-            launch_mmq(&sg3, &L.down.type, 1, MMQ_RESID, a3, s);
-        } else if (q3d) {
-            const int grid = matvec_grid(d, L.down.rows), rpw = rows_per_wave(L.down.rows, grid);
-            const int KR = rec_k(KD, L.down.type), nch = (KD + 2047) / 2048;
-            const int set = qi & 1;
-            ++qi;
-            const MmqQuant q{pb.h, nullptr, 1, d.eps, pb.qcnt + 512 * set, pb.qcnt + 512 * (1 - set), pb.qcnt + kQcntFlag};
-            const size_t lds = std::max(pf_lds_bytes(KR, nt, rpw), act_bytes(KD));
-            dispatch_nt<true>(KD, L.down.type, [&]<int NP, int T>() {
-                allow_lds(k_pf_ffn_down_q<NP, T>);
-                hipLaunchKernelGGL((k_pf_ffn_down_q<NP, T>), dim3(nt * nch + grid), dim3(MT), lds, s, d, L.down, pb, nt,
-                                   rpw, q, nch);
-            });
-        } else {
-            const int grid = matvec_grid(d, L.down.rows), rpw = rows_per_wave(L.down.rows, grid);
-            const int KR = rec_k(L.down.k, L.down.type);
-            over_tokens(KR, rpw, QD, [&](int, int n, const PrefillBuffers &q) {
-                dispatch_nt<true>(L.down.k, L.down.type, [&]<int NP, int T>() {
-                    allow_lds(k_pf_ffn_down<NP, T>);
-                    hipLaunchKernelGGL((k_pf_ffn_down<NP, T>), dim3(grid), dim3(MT), pf_lds_bytes(KR, n, rpw),
-                                       s, d, L.down, q, n, rpw);
-                });
-            });
-        }
+        r.run({kSiteGateUp, {L.gate}, 1, L.up, n, kInNorm, pb.x, L.ffn_norm, MMQ_SWIGLU, pb.h, d.n_ff, QD});
+        r.run({kSiteDown, {L.down}, 1, {}, L.down.k, kInPlain, pb.h, nullptr, MMQ_RESID, pb.x, n, QD});
     }
 }
 
@@ -1427,27 +1428,19 @@ void launch_batch_step(const LlmDims &d, const LayerW *layers, int n_layer, _Flo
                        const float *out_norm, const QMat &lm, const QMat &tok_embd, const PrefillBuffers &pb,
                        const BatchBuffers &bb, int B, bool chain, hipStream_t s) {
     launch_layers(d, layers, n_layer, kcache, vcache, pb, B, d.max_splits, true, s);
-    launch_quant(d, 0, pb.x, d.n_embd, out_norm, akind(lm.type), pb, B, s);
+    LayerRun r{d, pb, B, true, s};
+    const Site head{kSiteLmHead, {lm}, 1, {}, d.n_embd, kInNorm, pb.x, out_norm, MMQ_STORE, bb.logits, lm.rows, 0};
     const int nblk = matvec_grid(d, d.n_vocab);  // the batched lm_head keeps one workgroup per CU
-    // the logits on the int8 matrix cores (launch_mmq, the dot engine's values bit for bit),
-    // then the sampling partials from them (k_bt_gumbel): 8 streams 1.7B 217.0-217.5x vs
-    // 214.5-215.0x with k_bt_lm_head (dot4, partials fused), C4 179.5-179.6 vs 177.3-177.5x
-    // (profiles/r05_bt_lm_mmq_ab.txt). MIO_BT_LM_MMQ=0: k_bt_lm_head
-    static const bool lm_mmq = !(getenv("MIO_BT_LM_MMQ") && getenv("MIO_BT_LM_MMQ")[0] == '0');
-    if (lm_mmq && lm.type != 30) {
-        const MmqSeg sg{lm, mmq_tiles(lm.rows), 0};
-        launch_mmq(&sg, &lm.type, 1, MMQ_STORE,
-                   MmqArgs{pb.act, act_bytes(d.n_embd), d.n_embd, B, bb.logits, lm.rows, {}}, s);
+    if (r.plan(head).engine == kMmq) {
+        // the logits on the matrix cores, then the sampling partials from them
+        r.run(head);
         hipLaunchKernelGGL(k_bt_gumbel, dim3(nblk), dim3(MT), 0, s, lm.rows, bb, B);
-        if (chain) launch_sample_chain(ChainArgs{bb.logits, (size_t)lm.rows, bb.st, bb.cfg, bb.smp, nblk, nullptr, 0}, B, s);
-        hipLaunchKernelGGL(k_bt_sample, dim3(B), dim3(ST), 0, s, d, tok_embd, nblk, pb, bb);
-        return;
+    } else {
+        r.quant(head);
+        dispatch_nt<true>(d.n_embd, lm.type, [&]<int NP, int T>() {
+            launch_lds(k_bt_lm_head<NP, T>, nblk, batch_lm_head_lds(d, B, T), s, d, out_norm, lm, pb, bb, B);
+        });
     }
-    dispatch_nt<true>(d.n_embd, lm.type, [&]<int NP, int T>() {
-        allow_lds(k_bt_lm_head<NP, T>);
-        hipLaunchKernelGGL((k_bt_lm_head<NP, T>), dim3(nblk), dim3(MT), batch_lm_head_lds(d, B, T), s, d, out_norm, lm,
-                           pb, bb, B);
-    });
     if (chain) launch_sample_chain(ChainArgs{bb.logits, (size_t)lm.rows, bb.st, bb.cfg, bb.smp, nblk, nullptr, 0}, B, s);
     hipLaunchKernelGGL(k_bt_sample, dim3(B), dim3(ST), 0, s, d, tok_embd, nblk, pb, bb);
 }

@@ -139,19 +139,6 @@ struct mio_hip_llm {
 
 #pragma GCC visibility push(hidden)
 
-// A 0/1 switch of the environment: `def` unless the variable's first character is the other
-// digit. Every knob is read once per process (the callers keep the result in a static).
-inline bool env_flag(const char *name, bool def) {
-    const char *e = getenv(name);
-    return e && *e == (def ? '0' : '1') ? !def : def;
-}
-// An integer knob clamped to [lo, hi]; `def` when unset or empty.
-inline int env_int(const char *name, int def, int lo, int hi) {
-    const char *e = getenv(name);
-    const int v = e && *e ? atoi(e) : def;
-    return v < lo ? lo : (v > hi ? hi : v);
-}
-
 // llm.cpp: the step plan
 int graph_steps();  // steps per replayed step graph (MIO_GRAPH_STEPS)
 bool no_graph();    // MIO_NO_GRAPH=1: every launch eager

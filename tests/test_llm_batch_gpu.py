@@ -34,16 +34,18 @@ def _prompts(B, seed):
     return [list(rng.integers(0, 256, n)) for n in lens]
 
 
-@pytest.mark.parametrize("preset,B", [(0, 3), (1, 4), (0, 16)])
-def test_batch_equals_single_streams(device, llm_files, preset, B):
-    g = m.Llm(device, llm_files[preset], 256)
+@pytest.mark.parametrize("preset,B", [(0, 3), (1, 4), (0, 16), (2, 3)])
+def test_batch_equals_single_streams(device, llm_files, synth_llm_path, preset, B):
+    """(2, 3): the 0.1B shape, a Q8_0 model whose n_embd (576) is no multiple of 256, so both
+    q|k|v and gate|up of the batched decode quantize in the launch on the dot4 engine (xpre)."""
+    g = m.Llm(device, llm_files[preset] if preset in llm_files else synth_llm_path(preset), 256)
     prompts = _prompts(B, 10 * preset + B)
     seeds = [1000 + 17 * b for b in range(B)]
     got = g.generate_batch(prompts, 24, 0.8, seeds, allow=ALLOW)
     for b in range(B):
         ref = g.generate(prompts[b], 24, 0.8, seeds[b], allow=ALLOW)
         assert np.array_equal(got[b], ref), (b, got[b], ref)
-    if B == 3:
+    if B == 3 and preset == 0:
         o = pyoracle.Llm(llm_files[preset], 256)
         to = o.generate(prompts[0], 24, 0.8, seeds[0], allow=ALLOW)
         assert (got[0] == to).sum() >= 22

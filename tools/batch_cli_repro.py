@@ -35,7 +35,7 @@ for i in range(3):
     run(["-p", prompts[i], "-o", f"{d}/s{i}_0.wav"])
 print("single", [h(f"{d}/s{i}_0.wav") for i in range(3)], flush=True)
 runs = [("def", {})] * 3 + [("no_qf", {"MIO_BT_QF": "0"})] * 3 + [("nograph", {"MIO_NO_GRAPH": "1"})] * 2 + \
-       [("no_attq", {"MIO_ATT_Q": "0"})] * 2 + [("no_btatt", {"MIO_BT_ATT": "0"})] * 2
+       [("no_attq", {"MIO_ATT_Q": "0"})] * 2
 for k, (name, env) in enumerate(runs):
     run(["--batch", d + "/batch.txt", "-o", f"{d}/b{k}.wav", "--gpus", "1"], env)
     print(name, [h(f"{d}/b{k}_{i:03d}.wav") for i in range(3)], flush=True)
