@@ -135,9 +135,12 @@ int mio_hip_codec_decode_stage(mio_hip_codec *c, const int32_t *codes, int n_cod
 /* ---------------- LLM decode ----------------
  * Replaces llama_model_load_from_file + llama_init_from_model (test-to-speech.cpp:47-49,
  * :103-108): GGUF "llama" / "mistral" / "qwen2" / "qwen3" / "lfm2" (short-conv hybrid) with
- * Q8_0 / Q4_K / Q5_K / Q6_K / BF16 matrices (Q8_0, Q4_K_M, Q5_K_M, Q5_K_S, Q6_K and BF16 files;
- * Q5_0 / Q4_0 rows run as the Q8_0 rows they equal); any other tensor type (Q5_1, Q4_1, Q2_K,
- * Q3_K, IQ*) fails the load with the tensor's name and type,
+ * Q8_0 / Q3_K / Q4_K / Q5_K / Q6_K / BF16 matrices (Q8_0, Q3_K_S, Q3_K_M, Q3_K_L, Q4_K_M, Q5_K_M,
+ * Q5_K_S, Q6_K and BF16 files; Q5_0 / Q4_0 rows run as the Q8_0 rows they equal); any other tensor
+ * type (Q5_1, Q4_1, Q2_K, IQ*: IQ4_NL is what llama-quantize makes of Q3_K rows that are not whole
+ * superblocks) fails the load with the tensor's name and type, and so does Q3_K as the output
+ * matrix (output.weight or a tied token_embd.weight: llama-quantize's files carry Q6_K there); a
+ * Q3_K token_embd.weight loads in a file whose layer 0 is Q3_K,
  * F16 KV cache of n_ctx positions (0 -> 2048, :104). A file whose matrices are all BF16 (lfm2
  * short-conv layers included) runs on every path; BF16 matrices beside quantized ones load and
  * decode single-stream, with the prompt as forced decode steps and no batched decode. */

@@ -43,6 +43,10 @@ int mio_quantize_rows(uint32_t type, const float *x, int rows, int k, void *out)
 /* The host dequantizer (ggml dequantize_row_* expression order) on rows of ggml blocks:
  * out[rows][k] f32. */
 int mio_dequantize_rows(uint32_t type, const void *rows_bytes, int rows, int k, float *out);
+/* The split layout the kernels stream (csrc/host/quant.h) of rows of ggml blocks, on the host:
+ * *nbytes = its size, off[4] = the planes' byte offsets; out NULL returns those alone. */
+int mio_debug_to_split(uint32_t type, const void *rows_bytes, int rows, int k, uint8_t *out, uint64_t *nbytes,
+                       uint64_t *off);
 /* The decode step's activation quantizer (one 512-thread workgroup, the kernels' own prologue
  * code) on x[k]: type 12 -> Q8_K, 8 -> Q8_0, 30 -> bf16 rounding; w != NULL: RMSNorm(x, eps) * w
  * first; sc1 != 0: the activation loaded the way an in-launch hand-off loads it. Out, the

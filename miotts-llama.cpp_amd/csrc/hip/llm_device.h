@@ -441,7 +441,7 @@ __device__ __forceinline__ void x_after_weights_plain(XRegs<XV> &xr) {
 }
 
 // Activation kind of a weight type (ggml's vec_dot_type): 0 Q8_0 (Q8_0 weights), 1 Q8_K
-// (Q4_K / Q5_K / Q6_K), 2 BF16 (BF16 weights: the activation rounded to bf16, ggml_fp32_to_bf16).
+// (Q3_K / Q4_K / Q5_K / Q6_K), 2 BF16 (BF16 weights: the activation rounded to bf16, ggml_fp32_to_bf16).
 __host__ __device__ constexpr int akind(int T) { return T == 30 ? 2 : (T == 8 ? 0 : 1); }
 
 // ggml_compute_fp32_to_bf16: round to nearest even, NaN kept quiet
@@ -668,6 +668,8 @@ constexpr uint32_t M4 = 0x0F0F0F0Fu, M2 = 0x03030303u;
 //   Q5_K: a, c as Q4_K; b = the 16 B of the superblock's fifth-bit plane (qh) under the lane's
 //         nibble bytes (qh[16 (pc & 1) .. +16], pc = lane & 7; sub-block j's bit is bit j)
 //   Q6_K: a = 16 B of ql, b = 16 B of qh, c = the lane's two int8 sub-block scales, e = d
+//   Q3_K: a.x, a.y = the piece's two runs of 16 2-bit codes, b.x = their 32 high bits, c = the two
+//         int8 sub-block scales, e = d (quant.h: piece pc = lane & 7 at position 4 (pc & 1) + (pc >> 1))
 //   Q8_0: a, b = the lane's 32 codes, e = d
 //   BF16: a, b, a2, b2 = the lane's 32 weights (bf16 pairs), one contiguous KB per register
 //         over the wave (weights pass*2048 + 512 i + 8 l .. +8 for register i = a, b, a2, b2)
@@ -725,6 +727,12 @@ __device__ __forceinline__ uint32_t bld2(const uint8_t *base, uint32_t bytes, ui
     return __builtin_amdgcn_raw_buffer_load_b16(rsrc(base, bytes), voff, soff, AUX);
 }
 
+template <int AUX = MIO_WEIGHT_AUX>
+__device__ __forceinline__ uint2 bld8(const uint8_t *base, uint32_t bytes, uint32_t voff, uint32_t soff) {
+    const auto v = __builtin_amdgcn_raw_buffer_load_b64(rsrc(base, bytes), voff, soff, AUX);
+    return make_uint2(v[0], v[1]);
+}
+
 template <int T, int AUX = MIO_WEIGHT_AUX>
 __device__ __forceinline__ Frag load_frag(const QMat W, int row, int pass) {
     const int lane = MIO_TIDX & 63;
@@ -757,6 +765,16 @@ __device__ __forceinline__ Frag load_frag(const QMat W, int row, int pass) {
         f.b = bld16<AUX>(W.p1, R * hb, sb * 64 + 32 * (pc >> 2) + 16 * (pc & 1), r * hb);
         f.c = bld2<AUX>(W.p2, R * sbb, sb * 16 + 2 * pc, r * sbb);
         f.e = bld2<AUX>(W.p3, R * db, sb * 2, r * db);
+    } else if constexpr (T == 11) {
+        const int nsb = W.k >> 8, sb = min(pass * 8 + (lane >> 3), nsb - 1), pc = lane & 7;
+        const int P = 4 * (pc & 1) + (pc >> 1);
+        const uint32_t qb = (uint32_t)(W.k / 4), hb = (uint32_t)(W.k / 8), sbb = (uint32_t)(W.k / 16),
+                       db = (uint32_t)nsb * 2;
+        const uint2 q = bld8<AUX>(W.p0, R * qb, sb * 64 + P * 8, r * qb);
+        f.a = make_uint4(q.x, q.y, 0, 0);
+        f.b = make_uint4(bld4<AUX>(W.p1, R * hb, sb * 32 + P * 4, r * hb), 0, 0, 0);
+        f.c = bld2<AUX>(W.p2, R * sbb, sb * 16 + 2 * P, r * sbb);
+        f.e = bld2<AUX>(W.p3, R * db, sb * 2, r * db);
     } else if constexpr (T == 30) {
         // element offsets clamped into the row (past K: another valid piece, zeroed in dot_frag)
         const uint32_t rb = (uint32_t)W.k * 2;
@@ -782,11 +800,11 @@ template <int T>
 __device__ __forceinline__ ALane load_alane(const ActL &a, int K, int pass) {
     const int lane = MIO_TIDX & 63;
     ALane r;
-    if constexpr (T == 12 || T == 13 || T == 14) {
+    if constexpr (T == 11 || T == 12 || T == 13 || T == 14) {
         const int nsb = K >> 8, sb = pass * 8 + (lane >> 3), pc = lane & 7;
         const int sbc = sb < nsb ? sb : 0;
         int e, e2;
-        if constexpr (T == 12 || T == 13) {
+        if constexpr (T == 11 || T == 12 || T == 13) {
             e = sbc * 256 + 64 * (pc >> 1) + 16 * (pc & 1);
             e2 = e + 32;
         } else {
@@ -819,7 +837,7 @@ __device__ __forceinline__ ALane load_alane(const ActL &a, int K, int pass) {
 
 // The per-lane part of a K-quant unit's row dot: the scaled integer terms of the lane's 32
 // weights (isum; Q4_K / Q5_K also imin, the mins against the activation's bsums) and the
-// superblock's raw float factors hd (Q4_K / Q5_K: the header's d | dmin f16 pair, Q6_K: d).
+// superblock's raw float factors hd (Q4_K / Q5_K: the header's d | dmin f16 pair, Q6_K / Q3_K: d).
 // No cross-lane sum: dot_frag reduces one unit's terms, pair_term two units' together.
 struct LaneTerms {
     int isum, imin;
@@ -827,10 +845,32 @@ struct LaneTerms {
 };
 template <int T>
 __device__ __forceinline__ LaneTerms lane_terms(const Frag &f, const ALane &al) {
-    static_assert(T == 12 || T == 13 || T == 14, "K-quants");
+    static_assert(T == 11 || T == 12 || T == 13 || T == 14, "K-quants");
     const int lane = MIO_TIDX & 63;
     LaneTerms t;
-    if constexpr (T == 12 || T == 13) {
+    if constexpr (T == 11) {
+        // the codes of a run's elements 4 k .. 4 k + 3 are (q >> 2 k) & 0x03030303; their high bits
+        // sit at bit hb = k (run lo) or 4 + k (run hi) of each byte of h and move to bit 2. The
+        // codes enter as 0 .. 7; their - 4 comes off through the activation's 16-element bsums
+        // (integer-exact, as Q6_K's - 32)
+        auto code = [](uint32_t q, uint32_t h, int k, int hb) {
+            const uint32_t hi = hb >= 2 ? h >> (hb - 2) : h << (2 - hb);
+            return (int)(((q >> (2 * k)) & M2) | (hi & 0x04040404u));
+        };
+        int dlo = 0, dhi = 0;
+        dlo = sdot4(code(f.a.x, f.b.x, 0, 0), al.lo.x, dlo);
+        dlo = sdot4(code(f.a.x, f.b.x, 1, 1), al.lo.y, dlo);
+        dlo = sdot4(code(f.a.x, f.b.x, 2, 2), al.lo.z, dlo);
+        dlo = sdot4(code(f.a.x, f.b.x, 3, 3), al.lo.w, dlo);
+        dhi = sdot4(code(f.a.y, f.b.x, 0, 4), al.hi.x, dhi);
+        dhi = sdot4(code(f.a.y, f.b.x, 1, 5), al.hi.y, dhi);
+        dhi = sdot4(code(f.a.y, f.b.x, 2, 6), al.hi.z, dhi);
+        dhi = sdot4(code(f.a.y, f.b.x, 3, 7), al.hi.w, dhi);
+        const int sa = (int)(int8_t)(f.c & 0xFF), sb = (int)(int8_t)(f.c >> 8);
+        t.isum = __mul24(sa, dlo - 4 * al.b0) + __mul24(sb, dhi - 4 * al.b1);
+        t.imin = 0;
+        t.hd = f.e;
+    } else if constexpr (T == 12 || T == 13) {
         const int jj = (lane & 7) >> 1;
         uint4 h;  // the superblock header {d|dmin, scale/min words} from the quad's four dwords
         // Q4_K: broadcasts without an `old` operand (four zeroing moves less per unit). Q5_K keeps
@@ -896,7 +936,7 @@ __device__ __forceinline__ LaneTerms lane_terms(const Frag &f, const ALane &al) 
 // semantics; every caller runs these operations in this order).
 template <int T>
 __device__ __forceinline__ float sb_term(int isum, int imin, uint32_t hd, float ad) {
-    if constexpr (T == 14) {
+    if constexpr (T == 14 || T == 11) {
         const float d = h2f(hd) * ad;
         return d * (float)isum;
     } else {
@@ -915,10 +955,10 @@ __device__ __forceinline__ float sb_term(int isum, int imin, uint32_t hd, float 
 template <int T>
 __device__ __forceinline__ float dot_frag(const Frag &f, const ALane &al, int K, int pass) {
     const int lane = MIO_TIDX & 63;
-    if constexpr (T == 12 || T == 13 || T == 14) {
+    if constexpr (T == 11 || T == 12 || T == 13 || T == 14) {
         const LaneTerms t = lane_terms<T>(f, al);
         const int isum = sum8_i(t.isum);
-        const int imin = T == 14 ? 0 : sum8_i(t.imin);
+        const int imin = T == 14 || T == 11 ? 0 : sum8_i(t.imin);
         const float v = sb_term<T>(isum, imin, t.hd, al.d);
         return pass * 8 + (lane >> 3) < (K >> 8) ? v : 0.0f;
     } else if constexpr (T == 30) {
@@ -985,7 +1025,7 @@ template <int T>
 __device__ __forceinline__ float pair_term(const Frag &fa, const Frag &fb, const ALane &al, bool side_b, bool in_k) {
     const LaneTerms a = lane_terms<T>(fa, al), b = lane_terms<T>(fb, al);
     const int isum = pair_sum8(a.isum, b.isum, side_b);
-    const int imin = T == 14 ? 0 : pair_sum8(a.imin, b.imin, side_b);
+    const int imin = T == 14 || T == 11 ? 0 : pair_sum8(a.imin, b.imin, side_b);
     const float v = sb_term<T>(isum, imin, side_b ? b.hd : a.hd, al.d);
     return in_k ? v : 0.0f;
 }
@@ -1013,7 +1053,7 @@ __device__ __forceinline__ float swapadd32(float a, float b) {
 // whose instantiations would lose an occupancy step to the joint form's registers (k_ffn<1, 13,
 // 6, 3, 13, 3> 80 -> 81 VGPRs, k_attn_in<1, 12, 12, 6> 64 -> 65, k_attn_out<1, 14, 6> 79 -> 84)
 template <int T, int NP, int NM, int SU>
-constexpr bool joint_rows = (T == 12 || T == 14) && NP == 1 && SU >= 2 && (NM == 2 || SU <= 4);
+constexpr bool joint_rows = (T == 11 || T == 12 || T == 14) && NP == 1 && SU >= 2 && (NM == 2 || SU <= 4);
 
 // The rows of one group F (SU one-pass units: unit u = row lo + u / NM, matrix u % NM; units
 // past the share are clamped duplicates, computed and dropped) reduced pairwise, fin(row, dot0,
@@ -1245,7 +1285,24 @@ __device__ inline void wave_range(const LlmDims &d, int R, int &lo, int &hi) {
 
 
 // ------------------------------------------------------------------ embedding rows
+// Q3: the table may be Q3_K too (an untied token_embd of a Q3_K_S / _M / _L file). Only the kernels
+// of such a model are built with it, so the others' embedding lookups stay the code they were.
+template <bool Q3 = false>
 __device__ float dequant_elem(const QMat &W, int row, int e) {
+    if constexpr (Q3) {
+        if (W.type == 11) {
+            // quant.h: element c of the superblock lies in piece pc's run t at index i
+            const int nsb = W.k >> 8, sb = e >> 8, c = e & 255, pc = 2 * (c >> 6) + ((c >> 4) & 1), t = (c >> 5) & 1,
+                      i = c & 15;
+            const int P = 4 * (pc & 1) + (pc >> 1);
+            const uint8_t qb = W.p0[(size_t)row * (W.k / 4) + sb * 64 + 8 * P + 4 * t + (i & 3)];
+            const uint8_t hb = W.p1[(size_t)row * (W.k / 8) + sb * 32 + 4 * P + (i & 3)];
+            const int q = (int)(((qb >> (2 * (i >> 2))) & 3) | (((hb >> (4 * t + (i >> 2))) & 1) << 2)) - 4;
+            const int sc = ((const int8_t *)W.p2)[(size_t)row * (W.k / 16) + sb * 16 + 2 * P + t];
+            const float dd = h2f(((const uint16_t *)W.p3)[(size_t)row * nsb + sb]);
+            return dd * (float)sc * (float)q;  // dequantize_row_q3_K: dl = d * (scale - 32), y = dl * q
+        }
+    }
     if (W.type == 12 || W.type == 13) {
         const int nsb = W.k >> 8, sb = e >> 8, c = e & 255, j = c >> 6, w = c & 63, hi = w >> 5, l = w & 31;
         const uint8_t q = W.p0[(size_t)row * (W.k / 2) + sb * 128 + 32 * j + l];
@@ -1278,12 +1335,13 @@ __device__ float dequant_elem(const QMat &W, int row, int e) {
 
 constexpr int ST = 1024;  // sampler / embedding threads (n_embd <= 4 * ST)
 
+template <bool Q3 = false>
 __device__ inline void embed_row(const QMat &emb, int tok, int n, float *x) {
     float v[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int e = MIO_TIDX + i * ST;
-        v[i] = e < n ? dequant_elem(emb, tok, e) : 0.0f;
+        v[i] = e < n ? dequant_elem<Q3>(emb, tok, e) : 0.0f;
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -1382,7 +1440,7 @@ __device__ int sample_token(const float *smp, int nblk, const SampleCfg &sc, int
 
 // Embedding row of tok in the matvec prologue's register layout (thread t: elements
 // 4(t + i*MT) .. +3), the same dequantization as embed_row.
-template <int XV>
+template <int XV, bool Q3 = false>
 __device__ inline void embed_regs(const QMat &emb, int tok, int K, XRegs<XV> &xr) {
 #pragma unroll
     for (int i = 0; i < XV; ++i) {
@@ -1390,7 +1448,7 @@ __device__ inline void embed_regs(const QMat &emb, int tok, int K, XRegs<XV> &xr
         float v[4] = {0.f, 0.f, 0.f, 0.f};
         if (e < K)
 #pragma unroll
-            for (int q = 0; q < 4; ++q) v[q] = dequant_elem(emb, tok, e + q);
+            for (int q = 0; q < 4; ++q) v[q] = dequant_elem<Q3>(emb, tok, e + q);
         xr.v[i] = make_float4(v[0], v[1], v[2], v[3]);
     }
 }
@@ -1404,8 +1462,9 @@ __device__ inline void embed_regs(const QMat &emb, int tok, int K, XRegs<XV> &xr
 }
 
 // Calls f.template operator()<NP, T>() for the matrix's pass count and weight type. BF = false:
-// the int8 types only (the multi-token engine: BF16 models prefill token by token).
-template <bool BF = true, class F>
+// the int8 types only (the multi-token engine: BF16 models prefill token by token). Q3 = false:
+// without Q3_K (the lm_head launches: the loader refuses a Q3_K output matrix).
+template <bool BF = true, bool Q3 = true, class F>
 void dispatch_nt(int K, int type, F &&f) {
     const int np = pick_np(K);
 #define NT_CASE(NPV, TV) \
@@ -1414,6 +1473,9 @@ void dispatch_nt(int K, int type, F &&f) {
     NT_CASE(3, 14) NT_CASE(6, 8) NT_CASE(6, 12) NT_CASE(6, 13) NT_CASE(6, 14)
     if constexpr (BF) {
         NT_CASE(1, 30) NT_CASE(3, 30) NT_CASE(6, 30)
+    }
+    if constexpr (Q3) {
+        NT_CASE(1, 11) NT_CASE(3, 11) NT_CASE(6, 11)
     }
 #undef NT_CASE
     no_kernel("matvec", type, K);
@@ -1428,6 +1490,10 @@ void dispatch_v(int tv, F &&f) {
     }
     if constexpr (TQ == 14) {
         if (tv == 12) return f.template operator()<12>();
+    }
+    if constexpr (TQ == 11) {
+        if (tv == 12) return f.template operator()<12>();
+        if (tv == 13) return f.template operator()<13>();
     }
     no_kernel("attn_v beside q|k", tv, TQ);
 }

@@ -21,7 +21,7 @@ static_assert(kAttChunk == 32 || kAttChunk == 64 || kAttChunk == 128, "attention
 
 // One quantized matrix in the split layout (csrc/host/quant.h), rows x k.
 struct QMat {
-    int type;  // ggml type id: 8 Q8_0, 12 Q4_K, 13 Q5_K, 14 Q6_K, 30 BF16
+    int type;  // ggml type id: 8 Q8_0, 11 Q3_K, 12 Q4_K, 13 Q5_K, 14 Q6_K, 30 BF16
     int rows, k;
     const uint8_t *p0, *p1, *p2, *p3;
 };
@@ -31,6 +31,7 @@ inline QMat qmat_rows(const QMat &q, int r0, int n) {
     size_t rb[4] = {0, 0, 0, 0};
     switch (q.type) {
         case 8: rb[0] = (size_t)q.k, rb[1] = (size_t)q.k / 32 * 2; break;
+        case 11: rb[0] = (size_t)q.k / 4, rb[1] = (size_t)q.k / 8, rb[2] = (size_t)q.k / 16, rb[3] = (size_t)q.k / 256 * 2; break;
         case 12: rb[0] = (size_t)q.k / 2, rb[1] = (size_t)q.k / 256 * 16; break;
         case 13: rb[0] = (size_t)q.k / 2, rb[1] = (size_t)q.k / 8, rb[2] = (size_t)q.k / 256 * 16; break;
         case 14: rb[0] = (size_t)q.k / 2, rb[1] = (size_t)q.k / 4, rb[2] = (size_t)q.k / 16, rb[3] = (size_t)q.k / 256 * 2; break;
@@ -44,9 +45,11 @@ inline QMat qmat_rows(const QMat &q, int r0, int n) {
 }
 
 // attn_v types the q|k|v launches are instantiated for beside q|k of type tq: its own, Q6_K
-// beside Q4_K / Q5_K (the *_K_M mixes' use_more_bits layers), Q4_K beside Q6_K.
+// beside Q4_K / Q5_K (the *_K_M mixes' use_more_bits layers), Q4_K beside Q6_K, Q4_K / Q5_K
+// beside Q3_K (Q3_K_M / Q3_K_L).
 inline bool attn_v_supported(int tq, int tv) {
-    return tv == tq || ((tq == 12 || tq == 13) && tv == 14) || (tq == 14 && tv == 12);
+    return tv == tq || ((tq == 12 || tq == 13) && tv == 14) || (tq == 14 && tv == 12) ||
+           (tq == 11 && (tv == 12 || tv == 13));
 }
 
 // Device-resident decode state (read by every kernel of a step; advanced by the sampler),

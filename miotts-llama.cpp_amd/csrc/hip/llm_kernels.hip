@@ -294,7 +294,8 @@ __global__ __launch_bounds__(MT) void k_ffn(LlmDims d, const float *norm_w, QMat
 
 // the instantiated (np, gate|up type, su, down np, down type, down su): 1.7B Q4_K_M (down Q4_K
 // or Q6_K), Q5_K_M / Q5_K_S (gate|up Q5_K, down Q5_K or Q6_K), Q6_K and BF16, 0.1B Q8_0 (down Q8_0,
-// or Q6_K: its Q6_K file), 2.6B Q8_0 (and LFM2-2.6B) and Q6_K, the tiny test presets' shapes
+// or Q6_K: its Q6_K file), 2.6B Q8_0 (and LFM2-2.6B) and Q6_K, the tiny test presets' shapes; last,
+// the 1.7B shape as Q3_K_S / Q3_K_M / Q3_K_L (gate|up Q3_K, down Q3_K, Q4_K or Q5_K)
 #define MIO_FFN_SHAPES(X) \
     X(1, 12, 6, 3, 12, 3)  \
     X(1, 12, 6, 3, 14, 3)  \
@@ -305,7 +306,10 @@ __global__ __launch_bounds__(MT) void k_ffn(LlmDims d, const float *norm_w, QMat
     X(1, 8, 2, 1, 8, 1)    \
     X(1, 8, 2, 1, 14, 1)   \
     X(1, 8, 0, 6, 8, 0)    \
-    X(1, 14, 0, 6, 14, 0)
+    X(1, 14, 0, 6, 14, 0)  \
+    X(1, 11, 6, 3, 11, 3)  \
+    X(1, 11, 6, 3, 12, 3)  \
+    X(1, 11, 6, 3, 13, 3)
 
 struct FfnShape {
     int np, t, su, npd, td, sud, GI, GD;
@@ -494,7 +498,8 @@ void launch_att_o(int G, int grid, size_t lds, hipStream_t s, const LlmDims &d, 
 // ------------------------------------------------------------------ sampler / embedding
 // The flush sampler (after the last step of a run; the step graph samples inside the next
 // step's layer-0 attn_in): the pending token, its embedding into b.x, the state advance.
-template <bool DG>
+// Q3: the embedding table is Q3_K (dequant_elem)
+template <bool DG, bool Q3>
 __global__ __launch_bounds__(ST) void k_sample(LlmDims d, QMat emb, int nblk, LlmBuffers b) {
     constexpr bool kDiag = DG;
     __shared__ float rs_[ST / 64];
@@ -508,7 +513,7 @@ __global__ __launch_bounds__(ST) void k_sample(LlmDims d, QMat emb, int nblk, Ll
     const int tok = sample_token<ST>(b.smp, nblk, sc, step, rs_, ri_);
     MIO_TRACE(b, 1);
     MIO_TL_MARK1(b);
-    embed_row(emb, tok, d.n_embd, b.x);
+    embed_row<Q3>(emb, tok, d.n_embd, b.x);
     MIO_TL_END(b);
     MIO_TRACE(b, 15);
     if (MIO_TIDX == 0) {
@@ -523,8 +528,9 @@ __global__ __launch_bounds__(ST) void k_sample(LlmDims d, QMat emb, int nblk, Ll
     }
 }
 
+template <bool Q3>
 __global__ __launch_bounds__(ST) void k_embed(LlmDims d, QMat emb, LlmBuffers b) {
-    embed_row(emb, b.st->token, d.n_embd, b.x);
+    embed_row<Q3>(emb, b.st->token, d.n_embd, b.x);
 }
 
 }  // namespace
@@ -561,7 +567,7 @@ int lm_head_blocks(const LlmDims &d) { const LlmDims l = lm_dims(d); return matv
 size_t matvec_lds(int K) { return smem_bytes(K); }
 
 void launch_embed_token(const LlmDims &d, const QMat &tok_embd, const LlmBuffers &b, hipStream_t s) {
-    hipLaunchKernelGGL(k_embed, dim3(1), dim3(ST), 0, s, d, tok_embd, b);
+    hipLaunchKernelGGL(tok_embd.type == 11 ? k_embed<true> : k_embed<false>, dim3(1), dim3(ST), 0, s, d, tok_embd, b);
 }
 
 inline size_t mv_lds(int K) { return smem_bytes(K); }
@@ -679,7 +685,7 @@ void launch_step_kernel(StepKind which, const StepCtx &c, int il, const LlmBuffe
         }
         case kLmHead: {
             const LlmDims dl = lm_dims(d);
-            dispatch_nt(d.n_embd, lm.type, [&]<int NP, int T>() {
+            dispatch_nt<true, false>(d.n_embd, lm.type, [&]<int NP, int T>() {
                 hipLaunchKernelGGL((k_lm_head<NP, T, DG>), dim3(lm_head_blocks(d)), dim3(MT), smem_bytes(d.n_embd), s, dl,
                                    out_norm, lm, b);
             });
@@ -689,7 +695,8 @@ void launch_step_kernel(StepKind which, const StepCtx &c, int il, const LlmBuffe
             launch_sample_chain(ChainArgs{b.logits, 0, b.st, b.cfg, b.smp, lm_head_blocks(d), nullptr, 0}, 1, s);
             break;
         case kSample:
-            hipLaunchKernelGGL(k_sample<DG>, dim3(1), dim3(ST), 0, s, d, tok_embd, lm_head_blocks(d), b);
+            hipLaunchKernelGGL((tok_embd.type == 11 ? k_sample<DG, true> : k_sample<DG, false>), dim3(1), dim3(ST), 0, s, d,
+                               tok_embd, lm_head_blocks(d), b);
             break;
         default: break;
     }

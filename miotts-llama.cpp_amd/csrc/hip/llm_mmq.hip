@@ -211,6 +211,66 @@ __device__ __forceinline__ v16f sb_q6k(const QMat &W, int row, int s, const int8
     return v;
 }
 
+// code - 4 for 4 packed 3-bit codes (signed int8): bit 2 set -> code & 3, clear -> code | 0xFC
+__device__ __forceinline__ int q3s(uint32_t q) {
+    const uint32_t t = q ^ 0x04040404u, m = t & 0x04040404u;
+    return (int)(t | ((m << 6) - (m << 1)));  // m * 62: bits 3-7 of every byte whose bit 2 is set
+}
+// the split-layout position of sub-block j's int8 scale (quant.h: piece 2 (j >> 2) + (j & 1), run
+// (j >> 1) & 1)
+__device__ __forceinline__ constexpr int q3_sc_at(int j) { return 2 * (4 * (j & 1) + (j >> 2)) + ((j >> 1) & 1); }
+
+// Q3_K superblock s: 16 sub-blocks of 16 values, one 32x32x16 MFMA each on (code - 4);
+// v = d * sum_j sc_j * C_j (ggml vec_dot_q3_K_q8_K; the Q6_K product with 3-bit codes).
+__device__ __forceinline__ v16f sb_q3k(const QMat &W, int row, int s, const int8_t *aq, const float *da_lds) {
+    const int lane = threadIdx.x & 63, h = lane >> 5;
+    const int nsb = W.k >> 8;
+    const uint8_t *qrow = W.p0 + (size_t)row * (W.k / 4);
+    const uint8_t *hrow = W.p1 + (size_t)row * (W.k / 8);
+    const int8_t *screw = (const int8_t *)W.p2 + (size_t)row * (W.k / 16);
+    const uint16_t *drow = (const uint16_t *)W.p3 + (size_t)row * nsb;
+    const uint4 scr = *reinterpret_cast<const uint4 *>(screw + (size_t)s * 16);
+    int8_t sc[16];
+    __builtin_memcpy(sc, &scr, 16);
+    uint32_t q[16], hm[8];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(qrow + (size_t)s * 64 + 16 * i);
+        q[4 * i] = v.x, q[4 * i + 1] = v.y, q[4 * i + 2] = v.z, q[4 * i + 3] = v.w;
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(hrow + (size_t)s * 32 + 16 * i);
+        hm[4 * i] = v.x, hm[4 * i + 1] = v.y, hm[4 * i + 2] = v.z, hm[4 * i + 3] = v.w;
+    }
+    long aa[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) aa[j] = *reinterpret_cast<const long *>(aq + s * 256 + 16 * j + 8 * h);
+    v16i isum = {};
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        // sub-block j = run t of the piece at position P; this lane's half: elements 8 h .. 8 h + 7
+        // of the run = code groups 2 h, 2 h + 1
+        const int P = 4 * (j & 1) + (j >> 2), t = (j >> 1) & 1;
+        const uint32_t qd = q[2 * P + t] >> (4 * h), hd = hm[P] >> (4 * t + 2 * h);
+        const uint32_t b0 = q3s((qd & M2) | ((hd & 0x01010101u) << 2));
+        const uint32_t b1 = q3s(((qd >> 2) & M2) | (((hd >> 1) & 0x01010101u) << 2));
+        const long bq = (long)b0 | ((long)b1 << 32);
+        const v16i c = __builtin_amdgcn_mfma_i32_32x32x16_i8(aa[j], bq, v16i{}, 0, 0, 0);
+        const int scj = sc[q3_sc_at(j)];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) isum[r] += __mul24(scj, c[r]);
+    }
+    const float dw = h2f(drow[s]);
+    v16f v;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const float d = dw * da_lds[s * TT + tok_of(lane, r)];
+        v[r] = d * (float)isum[r];
+    }
+    return v;
+}
+
 // slot k's pass accumulation (K-quants)
 template <int T>
 __device__ v16f slot_kq(const QMat &W, int row, int k, const int8_t *aq, const float *da_lds) {
@@ -220,8 +280,10 @@ __device__ v16f slot_kq(const QMat &W, int row, int k, const int8_t *aq, const f
         const int s = p * 8 + k;
         v16f v = {};
         if (s < nsb) {
-            static_assert(T == 12 || T == 13 || T == 14, "slot_kq: K-quant types");
-            if constexpr (T == 12)
+            static_assert(T == 11 || T == 12 || T == 13 || T == 14, "slot_kq: K-quant types");
+            if constexpr (T == 11)
+                v = sb_q3k(W, row, s, aq, da_lds);
+            else if constexpr (T == 12)
                 v = sb_q4k(W.p0 + (size_t)row * (W.k / 2), W.p1 + (size_t)row * nsb * 16, s, aq, da_lds);
             else if constexpr (T == 13)
                 v = sb_q4k<true>(W.p0 + (size_t)row * (W.k / 2), W.p2 + (size_t)row * nsb * 16, s, aq, da_lds,
@@ -336,7 +398,7 @@ __device__ v16f slot_q80(const QMat &W, int row, int k, const int8_t *aq, const 
 
 template <int T>
 __device__ __forceinline__ v16f slot_val(const QMat &W, int row, int k, const int8_t *aq, const float *da_lds) {
-    static_assert(T == 8 || T == 12 || T == 13 || T == 14, "slot_val: weight type");
+    static_assert(T == 8 || T == 11 || T == 12 || T == 13 || T == 14, "slot_val: weight type");
     if constexpr (T == 8) return slot_q80(W, row, k, aq, da_lds);
     else return slot_kq<T>(W, row, k, aq, da_lds);
 }
@@ -717,12 +779,82 @@ __device__ __forceinline__ v4f sb16_q6k(const QMat &W, int row, int s, const AP 
     return q6p_val(p, x, s, da_lds);
 }
 
+// Q3_K superblock s: v = d * sum_j sc_j * dot_j over its 16 sub-blocks of 16 (ggml
+// vec_dot_q3_K_q8_K), on the activations as kq_act leaves them: chunk c's low (high) half holds
+// elements 64 c (+ 32) + 8 pi(g) .. + 7, pi = {0, 2, 1, 3}, i.e. sub-block 4 c (+ 2) in groups 0, 2
+// and the next one in groups 1, 3 - two 16x16x32 MFMAs per half, each on one sub-block's lanes
+// (the others zero), as Q6_K's. The split layout (quant.h) keeps the pieces of parity g & 1 of
+// every plane together: a lane's codes are two 16-B loads, their high bits one, the superblock's
+// scales one; of each run's dword it takes code groups 2 (g >> 1) and + 1.
+struct Q3Pass {
+    uint4 scr;
+    uint4 q[2], h;
+    uint16_t d;
+};
+__device__ __forceinline__ void q3p_load(const QMat &W, int row, int s, Q3Pass &p) {
+    const int lane = threadIdx.x & 63, g = lane >> 4;
+    const int nsb = W.k >> 8;
+    const uint8_t *qrow = W.p0 + (size_t)row * (W.k / 4);
+    const uint8_t *hrow = W.p1 + (size_t)row * (W.k / 8);
+    const int8_t *screw = (const int8_t *)W.p2 + (size_t)row * (W.k / 16);
+    const uint16_t *drow = (const uint16_t *)W.p3 + (size_t)row * nsb;
+    p.scr = *reinterpret_cast<const uint4 *>(screw + (size_t)s * 16);
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+        p.q[i] = *reinterpret_cast<const uint4 *>(qrow + (size_t)s * 64 + 32 * (g & 1) + 16 * i);
+    p.h = *reinterpret_cast<const uint4 *>(hrow + (size_t)s * 32 + 16 * (g & 1));
+    p.d = drow[s];
+}
+// x: the superblock's activation codes of this lane, already swap_halves'd
+__device__ __forceinline__ v4f q3p_val(const Q3Pass &p, const v4i (&x)[4], int s, const float *da_lds) {
+    const int lane = threadIdx.x & 63, g = lane >> 4;
+    const bool first = (g & 1) == 0;  // groups 0, 2: the half's first sub-block
+    int8_t sc[16];
+    __builtin_memcpy(sc, &p.scr, 16);
+    const float dw = h2f(p.d);
+    const uint32_t qw[8] = {p.q[0].x, p.q[0].y, p.q[0].z, p.q[0].w, p.q[1].x, p.q[1].y, p.q[1].z, p.q[1].w};
+    const uint32_t hw[4] = {p.h.x, p.h.y, p.h.z, p.h.w};
+    v4i isum = {};
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            // piece 2 c + (g & 1), run t
+            const uint32_t qd = qw[2 * c + t] >> (4 * (g >> 1)), hd = hw[c] >> (4 * t + 2 * (g >> 1));
+            const uint32_t b0 = q3s((qd & M2) | ((hd & 0x01010101u) << 2));
+            const uint32_t b1 = q3s(((qd >> 2) & M2) | (((hd >> 1) & 0x01010101u) << 2));
+            const long bq = (long)b0 | ((long)b1 << 32);
+            const long a = t ? hi8(x[c]) : lo8(x[c]);
+            const v4i c0 = mfma16(first ? a : 0l, bq, v4i{});
+            const v4i c1 = mfma16(first ? 0l : a, bq, v4i{});
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int j = 4 * c + 2 * t + h;  // sub-block
+                const int scj = sc[q3_sc_at(j)];
+                const v4i &cc = h ? c1 : c0;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) isum[i] += __mul24(scj, cc[i]);
+            }
+        }
+    }
+    v4f v;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const float d = dw * da_lds[s * TT16 + tok16(lane, i)];
+        v[i] = d * (float)isum[i];
+    }
+    return v;
+}
+
 template <int T>
-using KqPass = std::conditional_t<T == 12, Q4Pass, std::conditional_t<T == 13, Q5Pass, Q6Pass>>;
+using KqPass = std::conditional_t<T == 11, Q3Pass,
+                                  std::conditional_t<T == 12, Q4Pass, std::conditional_t<T == 13, Q5Pass, Q6Pass>>>;
 template <int T>
 __device__ __forceinline__ void kqp_load(const QMat &W, int row, int s, KqPass<T> &p) {
-    static_assert(T == 12 || T == 13 || T == 14, "kqp_load: K-quant types");
-    if constexpr (T == 12)
+    static_assert(T == 11 || T == 12 || T == 13 || T == 14, "kqp_load: K-quant types");
+    if constexpr (T == 11)
+        q3p_load(W, row, s, p);
+    else if constexpr (T == 12)
         q4p_load(W.p0 + (size_t)row * (W.k / 2), W.p1 + (size_t)row * (W.k >> 8) * 16, s, p);
     else if constexpr (T == 13)
         q5p_load(W.p0 + (size_t)row * (W.k / 2), W.p1 + (size_t)row * (W.k / 8),
@@ -732,7 +864,9 @@ __device__ __forceinline__ void kqp_load(const QMat &W, int row, int s, KqPass<T
 }
 template <int T>
 __device__ __forceinline__ v4f kqp_val(const KqPass<T> &p, const v4i (&x)[4], int s, const float *da) {
-    if constexpr (T == 14)
+    if constexpr (T == 11)
+        return q3p_val(p, x, s, da);
+    else if constexpr (T == 14)
         return q6p_val(p, x, s, da);
     else
         return q4p_val(p, x, s, da);
@@ -746,8 +880,14 @@ __device__ v4f slot16_kq(const QMat &W, int row, int k, const AP &aq, const floa
         const int s = p * 8 + k;
         v4f v = {};
         if (s < nsb) {
-            static_assert(T == 12 || T == 13 || T == 14, "slot16_kq: K-quant types");
-            if constexpr (T == 12) {
+            static_assert(T == 11 || T == 12 || T == 13 || T == 14, "slot16_kq: K-quant types");
+            if constexpr (T == 11) {
+                Q3Pass ps;
+                q3p_load(W, row, s, ps);
+                v4i x[4];
+                kq_act(aq, s, x);
+                v = q3p_val(ps, x, s, da_lds);
+            } else if constexpr (T == 12) {
                 v = sb16_q4k(W.p0 + (size_t)row * (W.k / 2), W.p1 + (size_t)row * nsb * 16, s, aq, da_lds);
             } else if constexpr (T == 13) {
                 Q5Pass ps;
@@ -887,7 +1027,7 @@ __device__ __forceinline__ void slot16_q80p(const QMat &W, const QMat &U, int ro
 
 template <int T, class AP>
 __device__ __forceinline__ v4f slot16_val(const QMat &W, int row, int k, const AP &aq, const float *da_lds) {
-    static_assert(T == 8 || T == 12 || T == 13 || T == 14, "slot16_val: weight type");
+    static_assert(T == 8 || T == 11 || T == 12 || T == 13 || T == 14, "slot16_val: weight type");
     if constexpr (T == 8) {
         // the 8-B Q8_0 path (K % 256 != 0) never runs in an in-launch-quantization launch
         // (launch_mmq_q takes K % 256 == 0 only): no kernel with producers instantiates it
@@ -1081,7 +1221,7 @@ __global__ __launch_bounds__(MMQ_NT) void k_mmq16(MmqSeg s0, MmqSeg s1, MmqSeg s
             slot16_store(y, red);
             if constexpr (NV == 2) slot16_store(u, red + MMQ_NT * 4);
         } else {
-            if constexpr (NV == 1 && (T == 12 || T == 13 || T == 14)) {
+            if constexpr (NV == 1 && (T == 11 || T == 12 || T == 13 || T == 14)) {
                 // up to three passes' weights (K <= 6144, the 1.7B down) are in flight before
                 // the activations are read (with in-launch quantization: while the producers
                 // quantize); then slot16_kq's arithmetic. The activation codes of
@@ -1263,11 +1403,11 @@ __global__ __launch_bounds__(MMQ_NT) void k_mmq16_loop(MmqSeg s0, MmqArgs a, Mmq
     }
 }
 
-// K-quants (T 12 = Q4_K, 14 = Q6_K), K <= 2048 (one superblock per wave): k_mmq16_loop's walk
-// (the batched lm_head: 10296 16-row Q6_K tiles; the 1.7B gate|up: 384 Q4_K tile pairs). The
-// activation codes (this wave's superblock k of every tile) and their scales are loaded once
-// per workgroup, the next tile's weights (q4p_load / q6p_load) are in flight while the current
-// one is reduced. Per tile the arithmetic is k_mmq16's slot16_kq (the 0 + v pass sum,
+// K-quants (T 11 = Q3_K, 12 = Q4_K, 13 = Q5_K, 14 = Q6_K), K <= 2048 (one superblock per wave):
+// k_mmq16_loop's walk (the batched lm_head: 10296 16-row Q6_K tiles; the 1.7B gate|up: 384 Q4_K or
+// Q3_K tile pairs). The activation codes (this wave's superblock k of every tile) and their scales
+// are loaded once per workgroup, the next tiles' weights (kqp_load: q3p_load / q4p_load / q5p_load /
+// q6p_load) are in flight while the current one is reduced (a ring of D tiles; Q3_K pairs: 2). Per tile the arithmetic is k_mmq16's slot16_kq (the 0 + v pass sum,
 // slot16_sum, the same epilogue): bit-identical. QNP > 0: the first a.nt workgroups are the
 // in-launch quantization producers (as k_mmq16_loop).
 template <int T, int MODE, int QNP, int QM>
@@ -1295,7 +1435,9 @@ __global__ __launch_bounds__(MMQ_NT) void k_mmq16_loop_kq(MmqSeg s0, MmqArgs a, 
     // ring of D tiles' weights: D - 1 tiles in flight while one is reduced
     // Q6_K W | U pairs: 3 (four Q6Pass pairs exceed 256 VGPRs: 12 B of scratch per lane; three
     // hold the 2.6B gate|up's <= 3 tiles per workgroup, two of them before the producers' wait)
-    constexpr int D = (T == 14 && NV == 2 && MIO_LOOP_D > 3) ? 3 : MIO_LOOP_D;
+    // Q3_K W | U pairs: 2, the ping-pong (a Q3Pass is as many registers as a Q6Pass, 17 per lane, and
+    // its unpacking holds more temporaries: three pairs spill 64 dwords per lane)
+    constexpr int D = (T == 11 && NV == 2 && MIO_LOOP_D > 2) ? 2 : ((T == 14 && NV == 2 && MIO_LOOP_D > 3) ? 3 : MIO_LOOP_D);
     KqPass<T> w[D], u[D];
 #pragma unroll
     for (int d = 0; d < D - 1; ++d) {
@@ -1483,11 +1625,16 @@ void launch_mmq(const MmqSeg *seg, const int *types, int nseg, int mode, const M
         if (types[2] == A) return go.template operator()<A, A, A>();
         if constexpr (A == 12 || A == 13) return go.template operator()<A, A, 14>();
         if constexpr (A == 14) return go.template operator()<A, A, 12>();
+        if constexpr (A == 11) {  // Q3_K_M / Q3_K_L: v Q4_K or Q5_K
+            if (types[2] == 12) return go.template operator()<A, A, 12>();
+            return go.template operator()<A, A, 13>();
+        }
     };
     if (types[0] == 12) one.template operator()<12>();
     else if (types[0] == 13) one.template operator()<13>();
     else if (types[0] == 14) one.template operator()<14>();
     else if (types[0] == 8) one.template operator()<8>();
+    else if (types[0] == 11) one.template operator()<11>();  // last: the earlier types' kernels keep their places
     else no_kernel("matmul", types[0], a.K);
 }
 
@@ -1522,6 +1669,9 @@ bool launch_mmq_q(const MmqSeg *seg, const int *types, int nseg, int mode, const
         if (T == 13 && types[2] == 13) return go(k_mmq16<13, 13, 13, MMQ_STORE, 0, 1, 0>);
         if (T == 13 && types[2] == 14) return go(k_mmq16<13, 13, 14, MMQ_STORE, 0, 1, 0>);
         if (T == 14 && types[2] == 14) return go(k_mmq16<14, 14, 14, MMQ_STORE, 0, 1, 0>);  // all-Q6_K files
+        if (T == 11 && types[2] == 11) return go(k_mmq16<11, 11, 11, MMQ_STORE, 0, 1, 0>);  // Q3_K_S
+        if (T == 11 && types[2] == 12) return go(k_mmq16<11, 11, 12, MMQ_STORE, 0, 1, 0>);  // Q3_K_M
+        if (T == 11 && types[2] == 13) return go(k_mmq16<11, 11, 13, MMQ_STORE, 0, 1, 0>);  // Q3_K_M / _L
         // Q8_0 models whose n_embd is a multiple of 256 up to 2048 (the others keep q|k|v on the
         // dot4 engine, quantizing in that launch)
         if (q8_one_pass && types[2] == 8) return go(k_mmq16<8, 8, 8, MMQ_STORE, 1, 1, 0>);
@@ -1545,6 +1695,7 @@ bool launch_mmq_q(const MmqSeg *seg, const int *types, int nseg, int mode, const
         if (T == 12) return kq_up.template operator()<12>();
         if (T == 13) return kq_up.template operator()<13>();
         if (T == 14) return kq_up.template operator()<14>();
+        if (T == 11) return kq_up.template operator()<11>();
         if (q8_one_pass) return w ? walk(k_mmq16_loop<MMQ_SWIGLU, 1, 0>) : go(k_mmq16<8, -1, -1, MMQ_SWIGLU, 1, 1, 0>);
     }
     if (mode == MMQ_RESID && nseg == 1 && q.mode == 1 && np == 3) {
@@ -1552,6 +1703,7 @@ bool launch_mmq_q(const MmqSeg *seg, const int *types, int nseg, int mode, const
         if (T == 12) return go(k_mmq16<12, -1, -1, MMQ_RESID, 0, 3, 1>);
         if (T == 13) return go(k_mmq16<13, -1, -1, MMQ_RESID, 0, 3, 1>);
         if (T == 14) return go(k_mmq16<14, -1, -1, MMQ_RESID, 0, 3, 1>);
+        if (T == 11) return go(k_mmq16<11, -1, -1, MMQ_RESID, 0, 3, 1>);  // Q3_K_S
     }
     // Q8_0 down (multi-pass pair path): at 9 to 16 streams, or with MIO_MMQ=1 (up to 8 it stays on
     // the dot4 engine: 2.010 vs 1.984 ms and 171.2 vs 179.4x with it here)

@@ -817,9 +817,11 @@ __global__ __launch_bounds__(MT) void k_pf_ffn_down_q(LlmDims d, QMat down, Pref
     });
 }
 
+// Q3 (here and in k_bt_sample, k_bt_embed): the embedding table is Q3_K (dequant_elem)
+template <bool Q3>
 __global__ __launch_bounds__(ST) void k_pf_embed(LlmDims d, QMat emb, PrefillBuffers pb, int p0) {
     const int t = blockIdx.x;
-    embed_row(emb, pb.tokens[p0 + t], d.n_embd, pb.x + (size_t)t * d.n_embd);
+    embed_row<Q3>(emb, pb.tokens[p0 + t], d.n_embd, pb.x + (size_t)t * d.n_embd);
 }
 
 // ------------------------------------------------------------------ batched decode (B utterances)
@@ -935,6 +937,7 @@ __global__ __launch_bounds__(MT) void k_bt_gumbel(int R, BatchBuffers bb, int nt
 // selection rule), the token ring, end-token flag, the next embedding into pb.x[b], and the
 // state advance. A stream whose step budget (cfg.max_steps) is spent, or that sampled an end
 // token, is frozen: nothing is recorded and its position no longer advances.
+template <bool Q3>
 __global__ __launch_bounds__(ST) void k_bt_sample(LlmDims d, QMat emb, int nblk, PrefillBuffers pb,
                                                   BatchBuffers bb) {
     __shared__ float bs_[ST / 64];
@@ -978,7 +981,7 @@ __global__ __launch_bounds__(ST) void k_bt_sample(LlmDims d, QMat emb, int nblk,
     // a stream whose step budget is spent or that sampled its end token stays frozen
     // (test-to-speech.cpp:168-170: the reference decodes nothing after the end token)
     const bool live = step < sc.max_steps && !st->done;
-    if (live) embed_row(emb, tok, d.n_embd, pb.x + (size_t)t * d.n_embd);
+    if (live) embed_row<Q3>(emb, tok, d.n_embd, pb.x + (size_t)t * d.n_embd);
     if (tid == 0 && live) {
         sc.out_tokens[step] = tok;
         if (tok == sc.eos0 || tok == sc.eos1) st->done = 1, signal_host_done(sc);
@@ -989,9 +992,10 @@ __global__ __launch_bounds__(ST) void k_bt_sample(LlmDims d, QMat emb, int nblk,
     }
 }
 
+template <bool Q3>
 __global__ __launch_bounds__(ST) void k_bt_embed(LlmDims d, QMat emb, PrefillBuffers pb, BatchBuffers bb) {
     const int t = blockIdx.x;
-    embed_row(emb, bb.st[t].token, d.n_embd, pb.x + (size_t)t * d.n_embd);
+    embed_row<Q3>(emb, bb.st[t].token, d.n_embd, pb.x + (size_t)t * d.n_embd);
 }
 
 template <int HD>
@@ -1396,7 +1400,8 @@ void launch_prefill_chunk(const LlmDims &d, const LayerW *layers, int n_layer, _
                           _Float16 *vcache, const QMat &tok_embd, const PrefillBuffers &pb, int p0, int nt,
                           int n_chunks, hipStream_t s) {
     if (nt <= 0) return;
-    hipLaunchKernelGGL(k_pf_embed, dim3(nt), dim3(ST), 0, s, d, tok_embd, pb, p0);
+    hipLaunchKernelGGL(tok_embd.type == 11 ? k_pf_embed<true> : k_pf_embed<false>, dim3(nt), dim3(ST), 0, s, d, tok_embd,
+                       pb, p0);
     launch_layers(d, layers, n_layer, kcache, vcache, pb, nt, n_chunks, false, s);
 }
 
@@ -1437,17 +1442,19 @@ void launch_batch_step(const LlmDims &d, const LayerW *layers, int n_layer, _Flo
         hipLaunchKernelGGL(k_bt_gumbel, dim3(nblk), dim3(MT), 0, s, lm.rows, bb, B);
     } else {
         r.quant(head);
-        dispatch_nt<true>(d.n_embd, lm.type, [&]<int NP, int T>() {
+        dispatch_nt<true, false>(d.n_embd, lm.type, [&]<int NP, int T>() {
             launch_lds(k_bt_lm_head<NP, T>, nblk, batch_lm_head_lds(d, B, T), s, d, out_norm, lm, pb, bb, B);
         });
     }
     if (chain) launch_sample_chain(ChainArgs{bb.logits, (size_t)lm.rows, bb.st, bb.cfg, bb.smp, nblk, nullptr, 0}, B, s);
-    hipLaunchKernelGGL(k_bt_sample, dim3(B), dim3(ST), 0, s, d, tok_embd, nblk, pb, bb);
+    hipLaunchKernelGGL(tok_embd.type == 11 ? k_bt_sample<true> : k_bt_sample<false>, dim3(B), dim3(ST), 0, s, d, tok_embd,
+                       nblk, pb, bb);
 }
 
 void launch_batch_embed(const LlmDims &d, const QMat &tok_embd, const PrefillBuffers &pb, const BatchBuffers &bb,
                         int B, hipStream_t s) {
-    hipLaunchKernelGGL(k_bt_embed, dim3(B), dim3(ST), 0, s, d, tok_embd, pb, bb);
+    hipLaunchKernelGGL(tok_embd.type == 11 ? k_bt_embed<true> : k_bt_embed<false>, dim3(B), dim3(ST), 0, s, d, tok_embd, pb,
+                       bb);
 }
 
 }  // namespace mio

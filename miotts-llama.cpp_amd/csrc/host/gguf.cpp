@@ -18,6 +18,7 @@ size_t ggml_type_block_elems(uint32_t t) {
         case GGML_Q4_0:
         case GGML_Q5_0:
         case GGML_Q8_0: return 32;
+        case GGML_Q3_K:
         case GGML_Q4_K:
         case GGML_Q5_K:
         case GGML_Q6_K:
@@ -37,6 +38,7 @@ size_t ggml_type_block_bytes(uint32_t t) {
         case GGML_Q4_0: return 18;
         case GGML_Q5_0: return 22;
         case GGML_Q8_0: return 34;
+        case GGML_Q3_K: return 110;
         case GGML_Q4_K: return 144;
         case GGML_Q5_K: return 176;
         case GGML_Q6_K: return 210;
@@ -62,6 +64,7 @@ const char *ggml_type_name(uint32_t t) {
         case GGML_Q4_0: return "q4_0";
         case GGML_Q5_0: return "q5_0";
         case GGML_Q8_0: return "q8_0";
+        case GGML_Q3_K: return "q3_K";
         case GGML_Q4_K: return "q4_K";
         case GGML_Q5_K: return "q5_K";
         case GGML_Q6_K: return "q6_K";

@@ -76,9 +76,9 @@ bool upload_qmat(mio_hip_llm *m, const mio::GgufTensor *t, mio::QMat &q) {
         return false;
     }
     const bool repack = mio::repacks_to_q8_0(t->type);
-    if (t->type != mio::GGML_Q8_0 && t->type != mio::GGML_Q4_K && t->type != mio::GGML_Q5_K &&
-        t->type != mio::GGML_Q6_K && t->type != mio::GGML_BF16 && !repack) {
-        mio::set_error("llm: tensor %s has type %s; supported: bf16, q8_0, q4_K, q5_K, q6_K, q5_0 / q4_0 (run as q8_0)",
+    if (t->type != mio::GGML_Q8_0 && t->type != mio::GGML_Q3_K && t->type != mio::GGML_Q4_K &&
+        t->type != mio::GGML_Q5_K && t->type != mio::GGML_Q6_K && t->type != mio::GGML_BF16 && !repack) {
+        mio::set_error("llm: tensor %s has type %s; supported: bf16, q8_0, q3_K, q4_K, q5_K, q6_K, q5_0 / q4_0 (run as q8_0)",
                        t->name.c_str(), mio::ggml_type_name(t->type));
         return false;
     }
@@ -127,7 +127,9 @@ bool upload_qmat(mio_hip_llm *m, const mio::GgufTensor *t, mio::QMat &q) {
     q.p1 = dp + L.off[1];
     q.p2 = dp + L.off[2];
     q.p3 = dp + L.off[3];
-    m->weight_bytes += t->nbytes;
+    // Q3_K streams its split layout's 114 B per superblock, not the GGUF's 110 (quant.h)
+    m->weight_bytes += type == mio::GGML_Q3_K ? (uint64_t)t->ne[1] * (uint64_t)(t->ne[0] / 256) * mio::kQ3KSplitBytes
+                                              : t->nbytes;
     return true;
 }
 
@@ -230,8 +232,24 @@ int upload_globals(const Load &ld, mio_hip_llm *m) {
     D.n_vocab = (int)te->ne[1];
     MIO_REQUIRE(D.n_vocab <= 128 * 8 * D.n_wg, MIO_ERR_UNSUPPORTED, "llm_load: vocab %d > %d", D.n_vocab,
                 128 * 8 * D.n_wg);
+    // the output matrix (or the tied table) as Q3_K does not occur in llama-quantize's files (they
+    // carry Q6_K there): no lm_head kernel is instantiated for it
+    const mio::GgufTensor *tl = ld.g.tensor("output.weight") ? ld.g.tensor("output.weight") : te;
+    MIO_REQUIRE(tl->type != mio::GGML_Q3_K, MIO_ERR_UNSUPPORTED,
+                "llm: tensor %s has type %s as the output matrix; supported there: bf16, q8_0, q4_K, q5_K, q6_K",
+                tl->name.c_str(), mio::ggml_type_name(tl->type));
+    // a Q3_K table's row lookup is built into the launches of a Q3_K model only (layer 0's first
+    // matrix Q3_K: llm_device.h dequant_elem), which is where llama-quantize's files have one
+    if (te->type == mio::GGML_Q3_K) {
+        const mio::GgufTensor *t0 = ld.g.tensor("blk.0.attn_q.weight");
+        if (!t0) t0 = ld.g.tensor("blk.0.shortconv.in_proj.weight");
+        MIO_REQUIRE(t0 && t0->type == mio::GGML_Q3_K, MIO_ERR_UNSUPPORTED,
+                    "llm: tensor %s has type %s beside a layer 0 that is not q3_K: not supported", te->name.c_str(),
+                    mio::ggml_type_name(te->type));
+    }
+    const uint64_t before = m->weight_bytes;
     if (!upload_qmat(m, te, m->tok)) return MIO_ERR_FORMAT;
-    const uint64_t embd_bytes = te->nbytes;
+    const uint64_t embd_bytes = m->weight_bytes - before;
     m->weight_bytes -= embd_bytes;  // one embedding row per step, not the whole table
     if (const mio::GgufTensor *to = ld.g.tensor("output.weight")) {
         if (!upload_qmat(m, to, m->lm)) return MIO_ERR_FORMAT;

@@ -235,6 +235,49 @@ void quantize_row_q6_K(const float *x, void *vy, int64_t k) {
     }
 }
 
+// Q3_K: per sub-block of 16 the scale amax / 4 with the sign that sends the element of largest
+// magnitude to code -4 (the codes span [-4, 3]: the asymmetric end goes to the largest element, as
+// ggml's make_q3_quants does), d = the largest |scale| / 31, 6-bit scales round(scale / d) in
+// [-32, 31] stored + 32, codes round(x / (d * scale)) clamped to [-4, 3]. Not ggml's search.
+void quantize_row_q3_K(const float *x, void *vy, int64_t k) {
+    BlockQ3_K *y = (BlockQ3_K *)vy;
+    for (int64_t i = 0; i < k / 256; ++i) {
+        const float *xb = x + i * 256;
+        float scales[16], max_scale = 0.0f;
+        for (int j = 0; j < 16; ++j) {
+            float amax = 0.0f, vmax = 0.0f;
+            for (int l = 0; l < 16; ++l)
+                if (std::fabs(xb[16 * j + l]) > amax) amax = std::fabs(xb[16 * j + l]), vmax = xb[16 * j + l];
+            scales[j] = vmax > 0.0f ? -amax / 4.0f : amax / 4.0f;
+            max_scale = std::max(max_scale, amax / 4.0f);
+        }
+        y[i].d = f32_to_fp16(max_scale / 31.0f);
+        const float dh = fp16_to_f32(y[i].d);
+        std::memset(y[i].hmask, 0, 32);
+        std::memset(y[i].qs, 0, 64);
+        std::memset(y[i].scales, 0, 12);
+        for (int j = 0; j < 16; ++j) {
+            const int ls = dh > 0 ? std::min(31, std::max(-32, nearest_int(scales[j] / dh))) : 0;
+            const uint8_t s6 = (uint8_t)(ls + 32);
+            y[i].scales[j % 8] |= (uint8_t)((s6 & 0xF) << (4 * (j / 8)));
+            y[i].scales[8 + j % 4] |= (uint8_t)((s6 >> 4) << (2 * (j / 4)));
+            const float dd = dh * ls;
+            for (int l = 0; l < 16; ++l) {
+                const int e = 16 * j + l;
+                int q = dd != 0 ? nearest_int(xb[e] / dd) : 0;
+                q = std::min(3, std::max(-4, q)) + 4;
+                y[i].qs[32 * (e / 128) + e % 32] |= (uint8_t)((q & 3) << (2 * ((e / 32) % 4)));
+                y[i].hmask[e % 32] |= (uint8_t)((q >> 2) << (e / 32));
+            }
+        }
+    }
+}
+
+// sub-block j's 6-bit scale of a Q3_K block (ggml's kmask1 / kmask2 shuffle, written out)
+static int q3k_scale6(const uint8_t *sc, int j) {
+    return ((sc[j % 8] >> (4 * (j / 8))) & 0xF) | (((sc[8 + j % 4] >> (2 * (j / 4))) & 3) << 4);
+}
+
 bool quantize_row(uint32_t type, const float *x, void *y, int64_t k) {
     switch (type) {
         case GGML_F32: std::memcpy(y, x, k * 4); return true;
@@ -247,6 +290,7 @@ bool quantize_row(uint32_t type, const float *x, void *y, int64_t k) {
         case GGML_Q8_0: quantize_row_q8_0(x, y, k); return true;
         case GGML_Q4_0: quantize_row_q4_0(x, y, k); return true;
         case GGML_Q5_0: quantize_row_q5_0(x, y, k); return true;
+        case GGML_Q3_K: quantize_row_q3_K(x, y, k); return true;
         case GGML_Q4_K: quantize_row_q4_K(x, y, k); return true;
         case GGML_Q5_K: quantize_row_q5_K(x, y, k); return true;
         case GGML_Q6_K: quantize_row_q6_K(x, y, k); return true;
@@ -284,6 +328,19 @@ bool dequantize_row(uint32_t type, const void *vx, float *y, int64_t k) {
                 block_codes_4_5(type, (const uint8_t *)vx + (size_t)i * bb, q, dh);
                 const float d = fp16_to_f32(dh);
                 for (int j = 0; j < 32; ++j) y[i * 32 + j] = q[j] * d;
+            }
+            return true;
+        }
+        case GGML_Q3_K: {  // dequantize_row_q3_K: dl = d * (scale - 32), y = dl * q
+            const BlockQ3_K *x = (const BlockQ3_K *)vx;
+            for (int64_t i = 0; i < k / 256; ++i) {
+                const float d = fp16_to_f32(x[i].d);
+                for (int e = 0; e < 256; ++e) {
+                    const float dl = d * (float)(q3k_scale6(x[i].scales, e / 16) - 32);
+                    const int code = (x[i].qs[32 * (e / 128) + e % 32] >> (2 * ((e / 32) % 4))) & 3;
+                    const int high = (x[i].hmask[e % 32] >> (e / 32)) & 1;
+                    y[i * 256 + e] = dl * (float)(code + 4 * high - 4);
+                }
             }
             return true;
         }
@@ -385,6 +442,10 @@ SplitLayout split_layout(uint32_t type, int64_t R, int64_t K) {
             take(0, (size_t)R * K / 2), take(1, (size_t)R * K / 4), take(2, (size_t)R * K / 16),
                 take(3, (size_t)R * (K / 256) * 2);
             break;
+        case GGML_Q3_K:
+            take(0, (size_t)R * K / 4), take(1, (size_t)R * K / 8), take(2, (size_t)R * K / 16),
+                take(3, (size_t)R * (K / 256) * 2);
+            break;
         case GGML_F32: take(0, (size_t)R * K * 4); break;
         case GGML_F16:
         case GGML_BF16: take(0, (size_t)R * K * 2); break;
@@ -450,6 +511,33 @@ bool to_split(uint32_t type, const void *src, int64_t R, int64_t K, uint8_t *dst
                 std::memcpy(qs + 128 * i, b[i].qs, 128);
                 std::memcpy(qh + 32 * i, b[i].qh, 32);
                 split_header_k4(b[i].d, b[i].dmin, b[i].scales, hd + 16 * i);
+            }
+        } else if (type == GGML_Q3_K) {
+            // quant.h: piece pc at position P = 4 (pc & 1) + (pc >> 1); run t (0 lo, 1 hi) = elements
+            // 64 (pc >> 1) + 16 (pc & 1) + 32 t + i, i < 16
+            const BlockQ3_K *b = (const BlockQ3_K *)row;
+            uint8_t *q = dst + L.off[0] + (size_t)r * K / 4;
+            uint8_t *h = dst + L.off[1] + (size_t)r * K / 8;
+            int8_t *sc = (int8_t *)(dst + L.off[2]) + (size_t)r * K / 16;
+            uint16_t *d = (uint16_t *)(dst + L.off[3]) + (size_t)r * (K / 256);
+            for (int64_t i = 0; i < K / 256; ++i) {
+                std::memset(q + 64 * i, 0, 64);
+                std::memset(h + 32 * i, 0, 32);
+                for (int pc = 0; pc < 8; ++pc) {
+                    const int P = 4 * (pc & 1) + (pc >> 1);
+                    for (int t = 0; t < 2; ++t) {
+                        const int e0 = 64 * (pc >> 1) + 16 * (pc & 1) + 32 * t;
+                        sc[16 * i + 2 * P + t] = (int8_t)(q3k_scale6(b[i].scales, e0 / 16) - 32);
+                        for (int l = 0; l < 16; ++l) {
+                            const int e = e0 + l;
+                            const int code = (b[i].qs[32 * (e / 128) + e % 32] >> (2 * ((e / 32) % 4))) & 3;
+                            const int high = (b[i].hmask[e % 32] >> (e / 32)) & 1;
+                            q[64 * i + 8 * P + 4 * t + l % 4] |= (uint8_t)(code << (2 * (l / 4)));
+                            h[32 * i + 4 * P + l % 4] |= (uint8_t)(high << (4 * t + l / 4));
+                        }
+                    }
+                }
+                d[i] = b[i].d;
             }
         } else {  // Q6_K
             const BlockQ6_K *b = (const BlockQ6_K *)row;

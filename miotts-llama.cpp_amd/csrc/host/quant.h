@@ -7,9 +7,29 @@
 //   Q4_K : qs [R][K/2]    u8 nibbles    | hd [R][K/256] 16 B = {d, dmin, 4 x 24-bit scale pairs}
 //   Q5_K : qs [R][K/2]    u8 nibbles    | qh [R][K/8] u8 fifth-bit plane | hd [R][K/256] 16 B as Q4_K's
 //   Q6_K : ql [R][K/2]    u8            | qh [R][K/4] u8 | sc [R][K/16] i8 (lane-pair order) | d [R][K/256] f16
+//   Q3_K : q  [R][K/4]    u8            | h  [R][K/8] u8 | sc [R][K/16] i8 (piece order)     | d [R][K/256] f16
 //
-// Same bytes per weight as GGUF (algorithmic bytes unchanged); each row's quant payload
-// becomes one contiguous, 16-B aligned run, so one wave reads a row with 16 B per lane.
+// Same bytes per weight as GGUF (algorithmic bytes unchanged; Q3_K: 114 B per superblock for
+// the GGUF's 110, below); each row's quant payload becomes one contiguous, 16-B aligned run, so
+// one wave reads a row with 16 B per lane (Q3_K: 8 B).
+//
+// Q3_K regroups the bits inside a superblock (the same 256 codes and 16 scales, permuted), so a
+// matvec lane's 32 weights are two whole sub-blocks, 32 elements apart, as Q4_K's and Q5_K's are.
+// Piece pc (0..7) holds the runs lo = elements 64 (pc >> 1) + 16 (pc & 1) .. + 15 (sub-block
+// 4 (pc >> 1) + (pc & 1)) and hi = lo + 32 (sub-block + 2). The pieces are stored at position
+// P(pc) = 4 (pc & 1) + (pc >> 1) of each plane - the even pieces, then the odd ones - so the
+// matrix-core tiles, whose lanes hold the pieces of one parity, read them with 16-B loads:
+//   q  : 64 B, piece at byte 8 P: dword 0 = run lo, dword 1 = run hi; the 2-bit code of the
+//        run's element i sits in byte i % 4 at bits 2 (i / 4), so (dword >> 2 k) & 0x03030303 are
+//        the codes of elements 4 k .. 4 k + 3, one per byte, as the dot4 instructions take them
+//   h  : 32 B, piece at byte 4 P: one dword; hmask's bit of run lo's element i sits in byte i % 4
+//        at bit i / 4, run hi's at bit 4 + i / 4 (1 = the code counts + 4, as in hmask)
+//   sc : 16 B, piece at byte 2 P: the two sub-blocks' 6-bit scales unpacked and the 32 taken off,
+//        int8 in [-32, 31] (run lo, run hi)
+//   d  : the superblock's f16 d
+// 114 B, not the 112 B of the packed 12 scale bytes + d rounded up to a header: with int8
+// scales no lane runs ggml's kmask shuffle per unit, as Q6_K's lanes do not; 3.6 % more bytes
+// than the GGUF, which mio_hip_llm_weight_bytes counts.
 #pragma once
 
 #include <cstddef>
@@ -34,6 +54,16 @@ struct BlockQ5_0 {
     uint8_t qh[4];
     uint8_t qs[16];
 };
+// 16 sub-blocks of 16 weights: weight e has the 2-bit code (qs[32 (e / 128) + e % 32] >> 2 ((e / 32)
+// % 4)) & 3 and the high bit (hmask[e % 32] >> (e / 32)) & 1, q = code + 4 high - 4; sub-block j's
+// 6-bit scale is ((scales[j % 8] >> 4 (j / 8)) & 0xF) | (((scales[8 + j % 4] >> 2 (j / 4)) & 3) << 4),
+// used as scale - 32
+struct BlockQ3_K {
+    uint8_t hmask[32];
+    uint8_t qs[64];
+    uint8_t scales[12];
+    uint16_t d;
+};
 struct BlockQ4_K {
     uint16_t d, dmin;
     uint8_t scales[12];
@@ -56,6 +86,7 @@ struct BlockQ6_K {
 static_assert(sizeof(BlockQ8_0) == 34, "q8_0");
 static_assert(sizeof(BlockQ4_0) == 18, "q4_0");
 static_assert(sizeof(BlockQ5_0) == 22, "q5_0");
+static_assert(sizeof(BlockQ3_K) == 110, "q3_K");
 static_assert(sizeof(BlockQ4_K) == 144, "q4_K");
 static_assert(sizeof(BlockQ5_K) == 176, "q5_K");
 static_assert(sizeof(BlockQ6_K) == 210, "q6_K");
@@ -67,6 +98,7 @@ uint16_t f32_to_bf16(float f);  // ggml_compute_fp32_to_bf16
 void quantize_row_q8_0(const float *x, void *y, int64_t k);
 void quantize_row_q4_0(const float *x, void *y, int64_t k);
 void quantize_row_q5_0(const float *x, void *y, int64_t k);
+void quantize_row_q3_K(const float *x, void *y, int64_t k);
 void quantize_row_q4_K(const float *x, void *y, int64_t k);
 void quantize_row_q5_K(const float *x, void *y, int64_t k);
 void quantize_row_q6_K(const float *x, void *y, int64_t k);
@@ -88,6 +120,8 @@ struct SplitLayout {
     size_t bytes = 0;
 };
 SplitLayout split_layout(uint32_t type, int64_t rows, int64_t k);
+// Bytes of one split-layout superblock of Q3_K (the GGUF block has 110)
+constexpr size_t kQ3KSplitBytes = 114;
 // GGUF rows -> split layout (dst has layout.bytes). Returns false on unsupported type.
 bool to_split(uint32_t type, const void *src, int64_t rows, int64_t k, uint8_t *dst);
 

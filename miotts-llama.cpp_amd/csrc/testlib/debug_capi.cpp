@@ -48,7 +48,7 @@ struct GuardedY {
 int debug_matvec(mio_hip_device *d, uint32_t type, const void *gguf_rows, const void *gguf_up, int rows, int k,
                  const float *x, float *y, int su = 0, int grid = 0) {
     MIO_REQUIRE(d && gguf_rows && x && y && rows > 0 && k > 0, MIO_ERR_INVALID, "debug_matvec: bad args");
-    MIO_REQUIRE(type == mio::GGML_Q8_0 || type == mio::GGML_Q4_K || type == mio::GGML_Q5_K ||
+    MIO_REQUIRE(type == mio::GGML_Q8_0 || type == mio::GGML_Q3_K || type == mio::GGML_Q4_K || type == mio::GGML_Q5_K ||
                     type == mio::GGML_Q6_K || type == mio::GGML_BF16 || (!gguf_up && mio::repacks_to_q8_0(type)),
                 MIO_ERR_UNSUPPORTED, "debug_matvec: type %u", type);
     const bool k32 = type == mio::GGML_Q8_0 || type == mio::GGML_BF16 || mio::repacks_to_q8_0(type);
@@ -115,7 +115,7 @@ extern "C" int mio_hip_debug_matvec_group(mio_hip_device *d, uint32_t type, cons
                                           const void *gguf_up, int rows, int k, int su, int grid, const float *x,
                                           float *y) {
     MIO_REQUIRE(su > 0 && grid > 0 && grid <= 4096, MIO_ERR_INVALID, "debug_matvec_group: su %d / grid %d", su, grid);
-    MIO_REQUIRE(type == mio::GGML_Q8_0 || type == mio::GGML_Q4_K || type == mio::GGML_Q5_K ||
+    MIO_REQUIRE(type == mio::GGML_Q8_0 || type == mio::GGML_Q3_K || type == mio::GGML_Q4_K || type == mio::GGML_Q5_K ||
                     type == mio::GGML_Q6_K || type == mio::GGML_BF16,
                 MIO_ERR_UNSUPPORTED, "debug_matvec_group: type %u", type);
     return debug_matvec(d, type, gguf_gate, gguf_up, rows, k, x, y, su, grid);
@@ -157,7 +157,7 @@ extern "C" int mio_hip_debug_mmq(mio_hip_device *d, uint32_t type, const void *g
     MIO_REQUIRE(d && gguf_rows && x && y && rows > 0 && k > 0 && nt > 0 && nt <= 4096 && mode >= 0 && mode <= 2 &&
                     (mode != 2 || gguf_up),
                 MIO_ERR_INVALID, "debug_mmq: bad args");
-    MIO_REQUIRE(type == mio::GGML_Q8_0 || type == mio::GGML_Q4_K || type == mio::GGML_Q5_K ||
+    MIO_REQUIRE(type == mio::GGML_Q8_0 || type == mio::GGML_Q3_K || type == mio::GGML_Q4_K || type == mio::GGML_Q5_K ||
                     type == mio::GGML_Q6_K,
                 MIO_ERR_UNSUPPORTED, "debug_mmq: type %u", type);
     MIO_REQUIRE(k % (type == mio::GGML_Q8_0 ? 32 : 256) == 0, MIO_ERR_INVALID, "debug_mmq: k %d", k);
@@ -240,5 +240,19 @@ extern "C" int mio_dequantize_rows(uint32_t type, const void *rows_bytes, int ro
     for (int r = 0; r < rows; ++r)
         if (!mio::dequantize_row(type, (const uint8_t *)rows_bytes + r * rb, out + (size_t)r * k, k))
             return MIO_ERR_UNSUPPORTED;
+    return MIO_OK;
+}
+
+// The split layout of GGUF rows (quant.h to_split), host only: *nbytes receives the layout's
+// size and the four planes' byte offsets go to off[4]; out (may be null: sizes only) must hold
+// that many bytes.
+extern "C" int mio_debug_to_split(uint32_t type, const void *rows_bytes, int rows, int k, uint8_t *out,
+                                  uint64_t *nbytes, uint64_t *off) {
+    MIO_REQUIRE(rows_bytes && nbytes && off && rows > 0 && k > 0, MIO_ERR_INVALID, "debug_to_split: bad args");
+    const mio::SplitLayout L = mio::split_layout(type, rows, k);
+    MIO_REQUIRE(L.bytes && mio::ggml_row_bytes(type, k), MIO_ERR_UNSUPPORTED, "debug_to_split: type %u / k %d", type, k);
+    *nbytes = L.bytes;
+    for (int i = 0; i < 4; ++i) off[i] = L.off[i];
+    if (out && !mio::to_split(type, rows_bytes, rows, k, out)) return MIO_ERR_UNSUPPORTED;
     return MIO_OK;
 }

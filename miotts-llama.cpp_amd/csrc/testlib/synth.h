@@ -35,7 +35,8 @@ struct SynthLlmCfg {
     float rope_base = 10000.f, rms_eps = 1e-6f, w_std = 0.02f;
     // 8 = all Q8_0; 15 = Q4_K_M mix (Q4_K + Q6_K); 17 = Q5_K_M mix (Q5_K + Q6_K); 16 = Q5_K_S (Q5_K,
     // Q6_K output); 18 = MOSTLY_Q6_K (Q6_K for every matrix, token_embd / output and the lfm2
-    // in_proj / out_proj included); 2 = Q4_0; 30 = all BF16
+    // in_proj / out_proj included); 2 = Q4_0; 30 = all BF16; 11 / 12 / 13 = Q3_K_S / Q3_K_M / Q3_K_L
+    // (Q3_K with attn_v, attn_output and ffn_down as Q3_K / Q4_K, Q5_K / Q5_K; Q6_K output)
     int qtype = 8;
     // llama-quantize's fallback for rows whose length is not a multiple of 256: Q4_K -> Q5_0,
     // Q6_K -> Q8_0 (llama-quant.cpp); Q4_K_M files of the 0.1B model (n_embd 576) carry them, and

@@ -111,13 +111,15 @@ SynthLlmCfg synth_llm_preset(int p) {
 }
 
 bool synth_llm_qtype_known(int q) {
-    return q == 8 || q == 15 || q == 16 || q == 17 || q == 18 || q == 2 || q == 30;
+    return q == 8 || q == 15 || q == 16 || q == 17 || q == 18 || q == 2 || q == 30 || q == 11 || q == 12 || q == 13;
 }
 
 const char *synth_llm_check(const SynthLlmCfg &c) {
     // llama-quantize turns Q5_K rows that are not whole 256-element superblocks into Q5_1, which
     // the loader refuses: such a file would be of no use
-    if ((c.qtype == 16 || c.qtype == 17) && (c.n_embd % 256 || c.n_ff % 256 || (c.n_head * c.head_dim) % 256))
+    // (Q3_K rows likewise become IQ4_NL, refused too: the same message for Q3_K_S / _M / _L)
+    const bool q3 = c.qtype == 11 || c.qtype == 12 || c.qtype == 13;
+    if ((c.qtype == 16 || c.qtype == 17 || q3) && (c.n_embd % 256 || c.n_ff % 256 || (c.n_head * c.head_dim) % 256))
         return "Q5_K_S / Q5_K_M need n_embd, n_ff and n_head * head_dim to be multiples of 256";
     return nullptr;
 }
@@ -158,8 +160,9 @@ bool synth_write_llm(const std::string &path, const SynthLlmCfg &c) {
     w.kv_str("general.architecture", a);
     w.kv_str("general.name", c.name);
     // llama_ftype: 7 MOSTLY_Q8_0, 15 MOSTLY_Q4_K_M, 16 MOSTLY_Q5_K_S, 17 MOSTLY_Q5_K_M, 18 MOSTLY_Q6_K,
-    // 2 MOSTLY_Q4_0, 32 MOSTLY_BF16
-    const bool kmix = c.qtype == 15 || c.qtype == 16 || c.qtype == 17 || c.qtype == 18;
+    // 2 MOSTLY_Q4_0, 32 MOSTLY_BF16, 11 MOSTLY_Q3_K_S, 12 MOSTLY_Q3_K_M, 13 MOSTLY_Q3_K_L
+    const bool q3mix = c.qtype == 11 || c.qtype == 12 || c.qtype == 13;
+    const bool kmix = c.qtype == 15 || c.qtype == 16 || c.qtype == 17 || c.qtype == 18 || q3mix;
     w.kv_u32("general.file_type", kmix ? c.qtype : (c.qtype == 2 ? 2 : (c.qtype == 30 ? 32 : 7)));
     w.kv_u32(a + ".context_length", c.n_ctx);
     w.kv_u32(a + ".embedding_length", c.n_embd);
@@ -211,11 +214,23 @@ bool synth_write_llm(const std::string &path, const SynthLlmCfg &c) {
     // K-quant mixes: base everywhere, `more` for attn_v / ffn_down on use_more_bits layers (the
     // _S mix has none), Q6_K for the output matrix (the tied embedding is one). MOSTLY_Q6_K has
     // Q6_K as its base, so every matrix is one.
-    const uint32_t kbase = c.qtype == 15 ? GGML_Q4_K : (c.qtype == 18 ? GGML_Q6_K : GGML_Q5_K);
+    // The Q3_K mixes (llama_tensor_get_type): Q3_K everywhere but attn_v (_S Q3_K; _M Q5_K on the
+    // first two attention layers, Q4_K after; _L Q5_K), attn_output (Q3_K / Q4_K / Q5_K) and ffn_down
+    // (_S Q3_K; _M Q5_K on layers i < n_layer / 16, Q4_K after; _L Q5_K); the untied embedding is
+    // Q3_K, the output matrix Q6_K.
+    const uint32_t kbase = q3mix ? GGML_Q3_K : (c.qtype == 15 ? GGML_Q4_K : (c.qtype == 18 ? GGML_Q6_K : GGML_Q5_K));
     const uint32_t base = pick(kbase, GGML_Q4_0), more = pick(c.qtype == 16 ? kbase : GGML_Q6_K, GGML_Q4_0);
+    int i_attn = 0;  // attention layers so far (llama-quant's i_attention_wv)
+    auto q3_v = [&](int ia) -> uint32_t {
+        return c.qtype == 11 ? GGML_Q3_K : (c.qtype == 13 ? GGML_Q5_K : (ia < 2 ? GGML_Q5_K : GGML_Q4_K));
+    };
+    const uint32_t q3_o = c.qtype == 11 ? GGML_Q3_K : (c.qtype == 12 ? GGML_Q4_K : GGML_Q5_K);
+    auto q3_down = [&](int i) -> uint32_t {
+        return c.qtype == 11 ? GGML_Q3_K : (c.qtype == 13 ? GGML_Q5_K : (i < c.n_layer / 16 ? GGML_Q5_K : GGML_Q4_K));
+    };
     const uint32_t outp = pick(GGML_Q6_K, GGML_Q4_0);
     const int q_dim = c.n_head * c.head_dim, kv_dim = c.n_head_kv * c.head_dim;
-    const uint32_t emb = c.tied ? outp : pick(c.qtype == 15 ? GGML_Q6_K : kbase, GGML_Q4_0);
+    const uint32_t emb = c.tied ? outp : pick(c.qtype == 15 ? GGML_Q6_K : kbase, GGML_Q4_0);  // (Q3_K mixes: Q3_K)
     ts.push_back({"token_embd.weight", emb, c.n_embd, c.n_vocab, false});
     for (int i = 0; i < c.n_layer; ++i) {
         const std::string p = "blk." + std::to_string(i) + ".";
@@ -229,8 +244,8 @@ bool synth_write_llm(const std::string &path, const SynthLlmCfg &c) {
         } else {
         ts.push_back({p + "attn_q.weight", base, c.n_embd, q_dim, false});
         ts.push_back({p + "attn_k.weight", base, c.n_embd, kv_dim, false});
-        ts.push_back({p + "attn_v.weight", mb ? more : base, c.n_embd, kv_dim, false});
-        ts.push_back({p + "attn_output.weight", base, q_dim, c.n_embd, false});
+        ts.push_back({p + "attn_v.weight", q3mix ? q3_v(i_attn++) : (mb ? more : base), c.n_embd, kv_dim, false});
+        ts.push_back({p + "attn_output.weight", q3mix ? q3_o : base, q_dim, c.n_embd, false});
         if (c.qkv_bias) {
             ts.push_back({p + "attn_q.bias", GGML_F32, q_dim, 1, 2});
             ts.push_back({p + "attn_k.bias", GGML_F32, kv_dim, 1, 2});
@@ -244,7 +259,7 @@ bool synth_write_llm(const std::string &path, const SynthLlmCfg &c) {
         ts.push_back({p + "ffn_norm.weight", GGML_F32, c.n_embd, 1, true});
         ts.push_back({p + "ffn_gate.weight", base, c.n_embd, c.n_ff, false});
         ts.push_back({p + "ffn_up.weight", base, c.n_embd, c.n_ff, false});
-        ts.push_back({p + "ffn_down.weight", mb ? more : base, c.n_ff, c.n_embd, false});
+        ts.push_back({p + "ffn_down.weight", q3mix ? q3_down(i) : (mb ? more : base), c.n_ff, c.n_embd, false});
     }
     // lfm2's final norm is token_embd_norm (llama.cpp model.tok_norm)
     ts.push_back({lfm2 ? "token_embd_norm.weight" : "output_norm.weight", GGML_F32, c.n_embd, 1, true});

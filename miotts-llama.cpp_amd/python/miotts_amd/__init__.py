@@ -164,6 +164,7 @@ def _declare(L: ctypes.CDLL) -> None:
                                             _vp]),
         "mio_quantize_rows": (c_int, [ctypes.c_uint32, _vp, c_int, c_int, _vp]),
         "mio_dequantize_rows": (c_int, [ctypes.c_uint32, _vp, c_int, c_int, _vp]),
+        "mio_debug_to_split": (c_int, [ctypes.c_uint32, _vp, c_int, c_int, _vp, _vp, _vp]),
         "mio_hip_debug_mmq": (c_int, [_vp, ctypes.c_uint32, _vp, c_int, c_int, _vp, c_int, c_int, _vp, _vp]),
         "mio_hip_debug_codec_gemm": (c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(c_int)]),
         "mio_hip_debug_codec_conv": (c_int, [_vp, _vp, c_int, c_int, c_int, c_int, _vp, c_int, _vp, c_int, _vp, _vp,
@@ -510,7 +511,7 @@ def synth_llm(path: str, preset: int = 0, seed: int = 1) -> str:
 
 def synth_llm_as(path: str, preset: int, qtype: int, seed: int = 1) -> str:
     """Preset `preset`'s shape, arch and seed rule written with the recipe `qtype` (SynthLlmCfg's
-    numbering: 8, 15, 16, 17, 18 = MOSTLY_Q6_K, 2, 30)."""
+    numbering: 8, 15, 16, 17, 18 = MOSTLY_Q6_K, 11 / 12 / 13 = Q3_K_S / _M / _L, 2, 30)."""
     check(lib().mio_synth_llm_gguf_as(path.encode(), preset, qtype, seed))
     return path
 
@@ -735,7 +736,7 @@ class Llm:
         return [out[b, : n[b]].copy() for b in range(B)]
 
 
-GGML_BLOCK = {2: (32, 18), 6: (32, 22), 8: (32, 34), 12: (256, 144), 13: (256, 176), 14: (256, 210),
+GGML_BLOCK = {2: (32, 18), 6: (32, 22), 8: (32, 34), 11: (256, 110), 12: (256, 144), 13: (256, 176), 14: (256, 210),
               30: (1, 2)}
 
 
@@ -758,6 +759,19 @@ def dequantize_rows(qtype: int, rows_bytes: np.ndarray, k: int) -> np.ndarray:
     out = np.empty((rows_bytes.shape[0], k), np.float32)
     check(lib().mio_dequantize_rows(qtype, _ptr(rows_bytes), rows_bytes.shape[0], k, _ptr(out)))
     return out
+
+
+def to_split(qtype: int, rows_bytes: np.ndarray, k: int):
+    """The split layout (csrc/host/quant.h to_split) of GGUF block bytes [rows][row_bytes], host only:
+    (the layout's bytes, the four planes' byte offsets)."""
+    rows_bytes = np.ascontiguousarray(rows_bytes, dtype=np.uint8)
+    be, bb = GGML_BLOCK[qtype]
+    assert rows_bytes.ndim == 2 and rows_bytes.shape[1] == k // be * bb, rows_bytes.shape
+    n, off = np.zeros(1, np.uint64), np.zeros(4, np.uint64)
+    check(lib().mio_debug_to_split(qtype, _ptr(rows_bytes), rows_bytes.shape[0], k, None, _ptr(n), _ptr(off)))
+    out = np.zeros(int(n[0]), np.uint8)
+    check(lib().mio_debug_to_split(qtype, _ptr(rows_bytes), rows_bytes.shape[0], k, _ptr(out), _ptr(n), _ptr(off)))
+    return out, [int(o) for o in off]
 
 
 def debug_matvec(dev: Device, qtype: int, w_rows: np.ndarray, k: int, x: np.ndarray) -> np.ndarray:

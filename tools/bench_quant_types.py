@@ -1,5 +1,6 @@
-"""Decode-step cost of the 1.7B shape as Q4_K_M (preset 3), Q5_K_M (preset 16) and Q6_K (preset 3
-written as MOSTLY_Q6_K), one process; --shape 2.6B / 0.1B: that shape as Q8_0 and as Q6_K.
+"""Decode-step cost of the 1.7B shape as Q4_K_M (preset 3), Q5_K_M (preset 16), Q6_K (preset 3
+written as MOSTLY_Q6_K), Q3_K_M and Q3_K_S (preset 3 written with recipes 12 and 11), one process;
+--shape 2.6B / 0.1B: that shape as Q8_0 and as Q6_K.
 
 All models are loaded, then timed alternately (REPS rounds): HIP events around a free-running
 generate() of N_LONG tokens and one of N_SHORT tokens from the same prompt and seed; the
@@ -32,7 +33,7 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E
 N_SHORT, N_LONG, REPS = 64, 464, 3
 BATCH, B_SHORT, B_LONG = 8, 32, 232
 # shape -> (name, preset, recipe or None for the preset's own)
-SHAPES = {"1.7B": (("q4_K_M", 3, None), ("q5_K_M", 16, None), ("q6_K", 3, 18)),
+SHAPES = {"1.7B": (("q4_K_M", 3, None), ("q5_K_M", 16, None), ("q6_K", 3, 18), ("q3_K_M", 3, 12), ("q3_K_S", 3, 11)),
           "2.6B": (("q8_0", 4, None), ("q6_K", 4, 18)),
           "0.1B": (("q8_0", 2, None), ("q6_K", 2, 18))}
 SWITCHES = ("MIO_LAYER_ATT", "MIO_ATT_FUSE_O", "MIO_FFN_FUSE")
