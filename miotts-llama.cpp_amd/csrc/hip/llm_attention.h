@@ -21,11 +21,12 @@ __device__ inline float lane_value(float v, int i) {
 // WQ (k_layer_att: q|k|v produced in the same launch): the K/V rows are loaded and staged
 // first, then one lane waits until the kv head's q|k|v row counter (b.att_cnt + kQkvOff +
 // kQkvStride * kvh) reaches (G + 2) * HD rows, and the head rows are loaded sc1.
-// Returns false for a workgroup with no positions (or after an end token).
+// Returns false for a workgroup with no positions (or after an end token). done: StepState.done
+// as the caller read it.
 template <int HD, int G, bool DG, bool WQ = false>
 __device__ __forceinline__ bool attention_wg(const LlmDims &d, const float *q_norm, const float *k_norm,
                                              const float *bqkv, _Float16 *kc, _Float16 *vc, const LlmBuffers &b,
-                                             int ch, int kvh, int pos, int *rdy) {
+                                             bool done, int ch, int kvh, int pos, int *rdy) {
     constexpr bool kDiag = DG;
     using C = AttCfg<HD>;
     constexpr int PER = HD / 64;
@@ -37,7 +38,7 @@ __device__ __forceinline__ bool attention_wg(const LlmDims &d, const float *q_no
     __shared__ __attribute__((aligned(16))) _Float16 qh[G][HD];
 
     const int t0 = ch * ATT_CHUNK;
-    if (t0 > pos || b.st->done) return false;
+    if (t0 > pos || done) return false;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const float2 *rope = b.rope + (size_t)pos * (HD / 2);
     // q heads (waves 0..G-1) and, for the chunk owning `pos`, the new k/v row (wave G); the
@@ -118,11 +119,12 @@ __device__ __forceinline__ bool attention_wg(const LlmDims &d, const float *q_no
 // order: every producer has a lower workgroup index than every consumer and never waits, so
 // it is dispatched (and finishes) whatever the residency. The counter is zeroed by the next
 // launch, k_ffn_in (kernel boundary ordered), and by reset_tickets.
+// K = wo.k (k_att_o has it in its entry pack).
 template <int NP, int T, int SU, bool DG>
-__device__ __forceinline__ void o_consumer(const LlmDims &d, const QMat &wo, const LlmBuffers &b, int ob, int no) {
+__device__ __forceinline__ void o_consumer(const LlmDims &d, const QMat &wo, int K, const LlmBuffers &b, int ob,
+                                           int no) {
     constexpr bool kDiag = DG;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int K = wo.k;
     const Smem s = carve(smem, K);
     int lo, hi;
     wave_range(wo.rows, lo, hi, ob, no);

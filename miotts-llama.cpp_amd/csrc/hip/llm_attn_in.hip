@@ -15,34 +15,42 @@
 namespace mio {
 namespace {
 
+// Entry pack (llm_device.h "kernel entry"): x, the attention norm weight, the state, K = n_embd,
+// g_qk; the earlier list follows (its norm_w and g_qk are the pack's now and stay unnamed).
 template <int NP, int TQ, int TV, int SU, bool DG, bool FS>
-__global__ __launch_bounds__(MT) void k_attn_in(LlmDims d, const float *norm_w, QMat wq, QMat wk, QMat wv,
-                                                int g_qk, LlmBuffers b, QMat emb, int nblk) {
+__global__ __launch_bounds__(MT) void k_attn_in(float *x, const float *norm_w, StepState *st, int K, int g_qk,
+                                                LlmDims d, const float *, QMat wq, QMat wk, QMat wv, int, LlmBuffers b,
+                                                QMat emb, int nblk) {
     constexpr bool kDiag = DG;
-    const int o1 = wq.rows, o2 = wq.rows + wk.rows;
-    const int GW = matvec_grid_n(d.n_wg, o2 + wv.rows);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ float rs_[MW];
     __shared__ int ri_[MW];
-    const int K = d.n_embd;
-    const Smem s = carve(smem, K);
-    MIO_TRACE(b, 0);
-    MIO_TL_BEGIN(b);
-    if (blockIdx.x == 2 && MIO_TIDX < 2 * kFfnShards)  // the previous k_ffn's h counters (kernel boundary ordered)
-        __hip_atomic_store((__attribute__((address_space(1))) int *)(b.att_cnt + kFfnOff + kFfnStride * MIO_TIDX), 0,
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    MIO_ENTRY_STAMPS();
     int pend = 0, step = 0;
     if constexpr (FS) {
         // after an end token every decode launch returns at entry (test-to-speech.cpp:168-170
-        // breaks before the next llama_decode); layer 0 reads the flag with pending / step
-        pend = b.st->pending;
-        step = b.st->step;
-        if (b.st->done) return;
+        // breaks before the next llama_decode); layer 0 reads the flag with pending / step, all
+        // three as vector loads through the pack (state_issue). The exit stands in front of the
+        // counter zeroing and the entry stamps, which need the other arguments: the k_ffn counters
+        // it skips were zeroed by the k_lm_head that ran before this launch, and no k_ffn runs
+        // between that and an end token's exit; a diagnostic run of such a step has no marks.
+        const StateRegs sr = state_issue(st);
+        pend = state_pending(sr);
+        step = state_step(sr);
+        if (state_done(sr)) return;
     }
     uint32_t dn = 0;
-    if constexpr (!FS) dn = done_issue(b);
+    if constexpr (!FS) dn = done_issue_st(st);
     XRegs<NP> xr;
-    load_x(pend ? nullptr : b.x, norm_w, K, xr);
+    load_x(pend ? nullptr : x, norm_w, K, xr);
+    const bool qk = (int)blockIdx.x < g_qk;
+    MIO_ENTRY_REST(MIO_PIN_QMAT(wq), MIO_PIN_QMAT(wk), MIO_PIN_QMAT(wv), "s"(d.n_wg), "s"(b.att_cnt), "s"(b.qkv),
+                   "s"(d.eps));
+    MIO_ENTRY_COMMIT(b);
+    zero_ffn_counters(b.att_cnt);
+    const int o1 = wq.rows, o2 = wq.rows + wk.rows;
+    const int GW = matvec_grid_n(d.n_wg, o2 + wv.rows);
+    const Smem s = carve(smem, K);
     // returns true when the sampled token ends generation (the rest of the step is skipped)
     auto sample_prologue = [&]() -> bool {
         if constexpr (FS) {
@@ -54,12 +62,12 @@ __global__ __launch_bounds__(MT) void k_attn_in(LlmDims d, const float *norm_w, 
 #pragma unroll
                     for (int i = 0; i < NP; ++i) {
                         const int e = (MIO_TIDX + i * MT) * 4;
-                        if (e < K) *reinterpret_cast<float4 *>(b.x + e) = xr.v[i];
+                        if (e < K) *reinterpret_cast<float4 *>(x + e) = xr.v[i];
                     }
                     if (MIO_TIDX == 0) {
                         if (step < sc.max_steps) sc.out_tokens[step] = tok;
-                        if (tok == sc.eos0 || tok == sc.eos1) b.st->done = 1, signal_host_done(sc);
-                        b.st->token = tok;
+                        if (tok == sc.eos0 || tok == sc.eos1) st->done = 1, signal_host_done(sc);
+                        st->token = tok;
                     }
                 }
                 return tok == sc.eos0 || tok == sc.eos1;
@@ -70,7 +78,7 @@ __global__ __launch_bounds__(MT) void k_attn_in(LlmDims d, const float *norm_w, 
     auto put = [&](int row, float v) { b.qkv[row] = v; };
     Frag ga[Cfg<NP, SU>::U], gb[Cfg<NP, SU>::U];
     int lo, hi;
-    if ((int)blockIdx.x < g_qk) {
+    if (qk) {
         wave_range(o2, lo, hi, blockIdx.x, g_qk);
         load_first<TQ, NP, 1, SU, MIO_SMALL_AUX>(wq, wk, lo, hi, ga, gb, o1);
         if (sample_prologue()) return;
@@ -115,11 +123,13 @@ void launch(const LlmDims &d, const LayerW &L, int il, const QMat &tok_embd, con
         auto go = [&]<int TV>() {
             dispatch_su<NP>(pick_su(un, NP), [&]<int SU>() {
                 if (il == 0)
-                    hipLaunchKernelGGL((k_attn_in<NP, TQ, TV, SU, DG, true>), dim3(grid), dim3(MT), lds, s, d,
-                                       L.attn_norm, L.wq, L.wk, L.wv, g_qk, b, tok_embd, nblk);
+                    hipLaunchKernelGGL((k_attn_in<NP, TQ, TV, SU, DG, true>), dim3(grid), dim3(MT), lds, s, b.x,
+                                       L.attn_norm, b.st, d.n_embd, g_qk, d, L.attn_norm, L.wq, L.wk, L.wv, g_qk, b,
+                                       tok_embd, nblk);
                 else
-                    hipLaunchKernelGGL((k_attn_in<NP, TQ, TV, SU, DG, false>), dim3(grid), dim3(MT), lds, s, d,
-                                       L.attn_norm, L.wq, L.wk, L.wv, g_qk, b, tok_embd, nblk);
+                    hipLaunchKernelGGL((k_attn_in<NP, TQ, TV, SU, DG, false>), dim3(grid), dim3(MT), lds, s, b.x,
+                                       L.attn_norm, b.st, d.n_embd, g_qk, d, L.attn_norm, L.wq, L.wk, L.wv, g_qk, b,
+                                       tok_embd, nblk);
             });
         };
         dispatch_v<TQ>(L.wv.type, go);

@@ -1394,11 +1394,80 @@ __device__ __forceinline__ int cur_pos(const StepState *st, const LlmDims &d) {
 // launches read the flag with a VECTOR load issued in front of their activation loads:
 // vmcnt retires in order, so the wait for x covers it and a decoding step pays no extra
 // round trip (a scalar load of the flag behind the weight group cost 82 us per 1.7B token).
+__device__ __forceinline__ uint32_t done_issue_st(const StepState *st) {
+    return __builtin_amdgcn_raw_buffer_load_b32(rsrc(&st->done, 4), 0, 0, 0);
+}
 template <class B>
 __device__ __forceinline__ uint32_t done_issue(const B &b) {
-    return __builtin_amdgcn_raw_buffer_load_b32(rsrc(&b.st->done, 4), 0, 0, 0);
+    return done_issue_st(b.st);
 }
+
 __device__ __forceinline__ bool done_now(uint32_t v) { return __builtin_amdgcn_readfirstlane(v) != 0; }
+// Where a launch takes its work from the state (the attention chunks and O workgroups of k_att_o /
+// k_layer_att from the position, layer 0's k_attn_in its x from `pending`): pos, step, token, done
+// and pending as two vector loads too, issued at entry through the entry pack's pointer, so that no
+// scalar round trip stands in front of the role's first loads and the state is in flight beside
+// the batch of the other arguments.
+struct StateRegs {
+    u32x4 a;     // pos, step, token, done
+    uint32_t p;  // pending
+};
+__device__ __forceinline__ StateRegs state_issue(const StepState *st) {
+    static_assert(sizeof(StepState) == 20, "StepState: pos, step, token, done, pending");
+    const auto r = rsrc(st, sizeof(StepState));
+    return {__builtin_amdgcn_raw_buffer_load_b128(r, 0, 0, 0), __builtin_amdgcn_raw_buffer_load_b32(r, 16, 0, 0)};
+}
+__device__ __forceinline__ int state_pending(const StateRegs &s) { return (int)__builtin_amdgcn_readfirstlane(s.p); }
+__device__ __forceinline__ int state_step(const StateRegs &s) { return (int)__builtin_amdgcn_readfirstlane(s.a.y); }
+__device__ __forceinline__ int state_pos(const StateRegs &s, int n_ctx) {  // cur_pos
+    return min((int)__builtin_amdgcn_readfirstlane(s.a.x) + state_pending(s), n_ctx - 1);
+}
+__device__ __forceinline__ bool state_done(const StateRegs &s) { return __builtin_amdgcn_readfirstlane(s.a.w) != 0; }
+
+// ------------------------------------------------------------------ kernel entry
+// The fused decode launches (k_attn_in, k_att_o, k_layer_att, k_ffn, k_lm_head) begin their
+// parameter lists with an entry pack: plain pointers and ints, no struct, holding what the first
+// instructions need (x, the norm weight, the StepState, K, the role split). The pack is the head
+// of the kernarg segment's first cache line, so the `done` load and the x / norm-weight loads go
+// out after at most one scalar round trip and wait for no other argument. MIO_ENTRY_REST then
+// pins everything else the role loads from in ONE batch of scalar loads behind them (k_attention's
+// pinning; left to itself the compiler fetched the arguments in three to five dependent rounds
+// before the first weight group was complete). The earlier parameter list follows the pack
+// unchanged, so every later argument moved by exactly the pack's size.
+// The diagnostic instantiations read their entry stamps into registers (MIO_ENTRY_STAMPS) and
+// store them behind the batch (MIO_ENTRY_COMMIT): the timeline and trace pointers are arguments
+// like any other and put no scalar round in front of x either.
+#define MIO_ENTRY_REST(...)                       \
+    do {                                          \
+        __builtin_amdgcn_sched_barrier(0);        \
+        asm volatile("" ::__VA_ARGS__ : "memory"); \
+    } while (0)
+#define MIO_PIN_QMAT(w) "s"((w).rows), "s"((w).k), "s"((w).p0), "s"((w).p1), "s"((w).p2), "s"((w).p3)
+#define MIO_PIN_QPTRS(w) "s"((w).p0), "s"((w).p1), "s"((w).p2), "s"((w).p3)
+#define MIO_ENTRY_STAMPS()                                                                   \
+    const unsigned long long entry_rt_ = kDiag ? __builtin_amdgcn_s_memrealtime() : 0ull, \
+                             entry_cc_ = kDiag ? __builtin_readcyclecounter() : 0ull
+#ifdef MIO_TL_DIAG
+#define MIO_ENTRY_COMMIT_DIAG_(bufs) \
+    if ((bufs).tl && MIO_TIDX == blockDim.x - 64) MIO_TL_SLOT(bufs)[6] = entry_rt_
+#else
+#define MIO_ENTRY_COMMIT_DIAG_(bufs)
+#endif
+#define MIO_ENTRY_COMMIT(bufs)                                                              \
+    do {                                                                                    \
+        if constexpr (kDiag) {                                                              \
+            if ((bufs).trace && blockIdx.x == 0 && blockIdx.y == 0 && MIO_TIDX == 0)        \
+                (bufs).trace[0] = entry_cc_, (bufs).trace[16] = entry_rt_;                  \
+            if ((bufs).tl && MIO_TIDX == 0) MIO_TL_SLOT(bufs)[0] = entry_rt_;               \
+            MIO_ENTRY_COMMIT_DIAG_(bufs);                                                   \
+        }                                                                                   \
+    } while (0)
+// The previous k_ffn's h counters, zeroed by the launch after it (kernel boundary ordered)
+__device__ __forceinline__ void zero_ffn_counters(int *att_cnt) {
+    if (blockIdx.x == 2 && MIO_TIDX < 2 * kFfnShards)
+        __hip_atomic_store((__attribute__((address_space(1))) int *)(att_cnt + kFfnOff + kFfnStride * MIO_TIDX), 0,
+                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
 // An end token was sampled: besides StepState.done (which the step's own launches read), one
 // system-scope vector store to the host's mapped word, so the host stops enqueuing steps
 // without a blocking poll (once per utterance, over PCIe)

@@ -213,19 +213,23 @@ __global__ __launch_bounds__(MT) void k_ffn_down(LlmDims d, QMat down, LlmBuffer
 // producer has signalled, i.e. after every producer's read of x. Arithmetic = the two
 // launches' (bit-identical). The counter is zeroed by the next launch (attn_in / layer_att /
 // lm_head), the timeout flag is k_att_o's (kRdyFlag).
+// Entry pack (llm_device.h "kernel entry"): x, the FFN norm weight, the state, K = n_embd, GI; the
+// earlier list follows (its norm_w and GI are the pack's now and stay unnamed).
 template <int NP, int T, int SU, int NPD, int TD, int SUD, bool DG>
-__global__ __launch_bounds__(MT) void k_ffn(LlmDims d, const float *norm_w, QMat gate, QMat up, QMat down,
-                                            LlmBuffers b, int adv, int GI) {
+__global__ __launch_bounds__(MT) void k_ffn(float *x, const float *norm_w, StepState *st, int K, int GI, LlmDims d,
+                                            const float *, QMat gate, QMat up, QMat down, LlmBuffers b, int adv,
+                                            int) {
     constexpr bool kDiag = DG;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    MIO_TRACE(b, 0);
-    MIO_TL_BEGIN(b);
-    const uint32_t dn = done_issue(b);
+    MIO_ENTRY_STAMPS();
+    const uint32_t dn = done_issue_st(st);
     if ((int)blockIdx.x < GI) {
-        const int K = d.n_embd;
-        const Smem s = carve(smem, K);
         XRegs<NP> xr;
-        load_x(b.x, norm_w, K, xr);
+        load_x(x, norm_w, K, xr);
+        MIO_ENTRY_REST(MIO_PIN_QMAT(gate), MIO_PIN_QPTRS(up), "s"(b.att_cnt), "s"(b.h), "s"(d.n_kv), "s"(d.eps),
+                       "s"(adv));
+        MIO_ENTRY_COMMIT(b);
+        const Smem s = carve(smem, K);
         if (blockIdx.x == 0 && MIO_TIDX < kRdyShards)
             __hip_atomic_store((__attribute__((address_space(1))) int *)(b.att_cnt + kRdyOff + kRdyStride * MIO_TIDX),
                                0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -238,7 +242,7 @@ __global__ __launch_bounds__(MT) void k_ffn(LlmDims d, const float *norm_w, QMat
         load_first<T, NP, 2, SU>(gate, up, lo, hi, ga, gb);
         x_after_weights(xr);
         if (done_now(dn)) {  // layer 0 still folds the end token's step (the host counts it)
-            if (adv && blockIdx.x == 0 && MIO_TIDX == 0) advance_state(b.st, d);
+            if (adv && blockIdx.x == 0 && MIO_TIDX == 0) advance_state(st, d);
             return;
         }
         MIO_TL_MARK1(b);
@@ -247,7 +251,7 @@ __global__ __launch_bounds__(MT) void k_ffn(LlmDims d, const float *norm_w, QMat
         stream_rows_lanes<T, NP, 2, SU>(gate, up, lo, hi, ga, gb, s.a, [&](int row, float g, float u) {
             st1_sc1(b.h, (uint32_t)row * 4u, silu_f(g) * u);
         });
-        if (adv && blockIdx.x == 0 && MIO_TIDX == 0) advance_state(b.st, d);
+        if (adv && blockIdx.x == 0 && MIO_TIDX == 0) advance_state(st, d);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (MIO_TIDX < 64) {
@@ -264,12 +268,15 @@ __global__ __launch_bounds__(MT) void k_ffn(LlmDims d, const float *norm_w, QMat
                                        1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     } else {
-        const int K = down.k;
-        const Smem s = carve(smem, K);
+        // the plain role: the residual rows and the first weight group need the batch itself
         const int GD = (int)gridDim.x - GI, ob = (int)blockIdx.x - GI;
+        MIO_ENTRY_REST(MIO_PIN_QMAT(down), "s"(GD), "s"(b.att_cnt), "s"(b.h));
+        MIO_ENTRY_COMMIT(b);
+        const int Kd = down.k;
+        const Smem s = carve(smem, Kd);
         int lo, hi;
         wave_range(down.rows, lo, hi, ob, GD);
-        const float xres = load_resid(b.x, lo, hi);
+        const float xres = load_resid(x, lo, hi);
         Frag ga[Cfg<NPD, SUD>::U], gb[Cfg<NPD, SUD>::U];
         load_first<TD, NPD, 1, SUD>(down, down, lo, hi, ga, gb);
         if (done_now(dn)) return;  // the producers return too: nobody signals, nobody waits
@@ -279,13 +286,13 @@ __global__ __launch_bounds__(MT) void k_ffn(LlmDims d, const float *norm_w, QMat
         asm volatile("s_barrier" ::: "memory");
         MIO_TL_MARK(b, 3);
         XRegs<NPD> xr;
-        load_x_plain<NPD, 16>(b.h, K, xr);
+        load_x_plain<NPD, 16>(b.h, Kd, xr);
         x_after_weights_plain(xr);
         MIO_TL_MARK1(b);
-        plain_quant(xr, K, akind(TD), s, MIO_TL_DIAGSLOT(b));
+        plain_quant(xr, Kd, akind(TD), s, MIO_TL_DIAGSLOT(b));
         MIO_TL_MARK(b, 2);
         stream_rows_lanes<TD, NPD, 1, SUD>(down, down, lo, hi, ga, gb, s.a, [&](int row, float v, float) {
-            b.x[row] = v + xres;  // lane i: row lo + i, its residual value
+            x[row] = v + xres;  // lane i: row lo + i, its residual value
         });
     }
     MIO_TL_END(b);
@@ -334,8 +341,9 @@ bool launch_ffn(const LlmDims &d, const LayerW &L, const LlmBuffers &b, int adv,
     if (!found && f.np == NP && f.t == T && f.su == SU && f.npd == NPD && f.td == TD && f.sud == SUD) {          \
         found = true;                                                                                            \
         if (!dry)                                                                                                \
-            hipLaunchKernelGGL((k_ffn<NP, T, SU, NPD, TD, SUD, DG>), dim3(f.GI + f.GD), dim3(MT), lds, st, d,       \
-                               L.ffn_norm, L.gate, L.up, L.down, b, adv, f.GI);                                  \
+            hipLaunchKernelGGL((k_ffn<NP, T, SU, NPD, TD, SUD, DG>), dim3(f.GI + f.GD), dim3(MT), lds, st, b.x,     \
+                               L.ffn_norm, b.st, d.n_embd, f.GI, d, L.ffn_norm, L.gate, L.up, L.down, b, adv,    \
+                               f.GI);                                                                            \
     }
     MIO_FFN_SHAPES(MIO_FFN_CASE)
 #undef MIO_FFN_CASE
@@ -345,23 +353,31 @@ bool launch_ffn(const LlmDims &d, const LayerW &L, const LlmBuffers &b, int adv,
 // final RMSNorm (once per CU) + logits + per-workgroup Gumbel-max partial. A wave's rows
 // (<= 128) are parked one per lane (two registers) and the noise is drawn for 64 rows at
 // a time after the stream.
+// Entry pack (llm_device.h "kernel entry"): x, the output norm weight, the state, K = n_embd, the
+// workgroups of the launch (lm_head_blocks: the grid and the row split are the same number).
 template <int NP, int T, bool DG>
-__global__ __launch_bounds__(MT) void k_lm_head(LlmDims d, const float *norm_w, QMat lm, LlmBuffers b) {
+__global__ __launch_bounds__(MT) void k_lm_head(const float *x, const float *norm_w, StepState *st, int K, int G,
+                                                LlmDims d, const float *, QMat lm, LlmBuffers b) {
     constexpr bool kDiag = DG;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ float bs_[MW];
     __shared__ int bi_[MW];
-    const int K = d.n_embd;
-    MIO_TRACE(b, 0);
-    MIO_TL_BEGIN(b);
-    if (blockIdx.x == 2 && MIO_TIDX < 2 * kFfnShards)  // the previous k_ffn's h counters (kernel boundary ordered)
-        __hip_atomic_store((__attribute__((address_space(1))) int *)(b.att_cnt + kFfnOff + kFfnStride * MIO_TIDX), 0,
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const Smem s = carve(smem, K);
+    MIO_ENTRY_STAMPS();
     XRegs<NP> xr;
-    load_x(b.x, norm_w, K, xr);
+    load_x(x, norm_w, K, xr);
+    // a workgroup past the row split has no rows (the grid is G; the split below relies on it). The
+    // exit, taken on a value the compiler sees only behind the x loads, also ends the entry block
+    // there: the loads of the other arguments and the copies made of them sink below it (in one
+    // block with x, the output matrix's pointers were fetched and waited for in front of x)
+    int ng = G;
+    asm volatile("" : "+s"(ng)::"memory");
+    if ((int)blockIdx.x >= ng) return;
+    MIO_ENTRY_REST(MIO_PIN_QMAT(lm), "s"(b.att_cnt), "s"(b.cfg), "s"(d.eps));
+    MIO_ENTRY_COMMIT(b);
+    zero_ffn_counters(b.att_cnt);
+    const Smem s = carve(smem, K);
     int lo, hi;
-    wave_range(d, lm.rows, lo, hi);
+    wave_range(lm.rows, lo, hi, blockIdx.x, ng);
     Frag ga[Cfg<NP>::U], gb[Cfg<NP>::U];
     load_first<T, NP, 1, 0, MIO_LM_AUX>(lm, lm, lo, hi, ga, gb);
     x_after_weights(xr);
@@ -369,8 +385,8 @@ __global__ __launch_bounds__(MT) void k_lm_head(LlmDims d, const float *norm_w, 
     // first weight group (in front of it, their scalar-load wait held the weight stream back)
     asm volatile("" ::: "memory");
     const SampleCfg sc = *b.cfg;
-    const int step = b.st->step;
-    if (b.st->done) return;  // no pending sample: the next step's attn_in returns too
+    const int step = st->step;
+    if (st->done) return;  // no pending sample: the next step's attn_in returns too
     MIO_TRACE(b, 1);
     MIO_TL_MARK1(b);
     rmsnorm_quant(xr, K, d.eps, akind(T), s, MIO_TL_DIAGSLOT(b));
@@ -413,7 +429,7 @@ __global__ __launch_bounds__(MT) void k_lm_head(LlmDims d, const float *norm_w, 
             if (bs_[w] > best || (bs_[w] == best && bi_[w] < bi)) best = bs_[w], bi = bi_[w];
         b.smp[2 * blockIdx.x] = best;
         b.smp[2 * blockIdx.x + 1] = __int_as_float(bi);
-        if (blockIdx.x == 0) b.st->pending = 1;  // sampled by the next step's attn_in or the flush
+        if (blockIdx.x == 0) st->pending = 1;  // sampled by the next step's attn_in or the flush
     }
     MIO_TL_END(b);
     MIO_TRACE(b, 15);
@@ -439,7 +455,9 @@ __global__ __launch_bounds__(AttCfg<HD>::NT) void k_attention(LlmDims d, const f
     asm volatile("" ::"s"(kc), "s"(vc), "s"(d.n_ctx), "s"(b.qkv), "s"(b.rope), "s"(q_norm), "s"(k_norm),
                  "s"(b.part), "s"(d.max_splits), "s"(bqkv), "s"(b.att), "s"(b.att_cnt));
     const int pos = cur_pos(b.st, d);
-    if (!attention_wg<HD, G, DG>(d, q_norm, k_norm, bqkv, kc, vc, b, blockIdx.x, blockIdx.y, pos, nullptr)) return;
+    if (!attention_wg<HD, G, DG>(d, q_norm, k_norm, bqkv, kc, vc, b, b.st->done != 0, blockIdx.x, blockIdx.y, pos,
+                                 nullptr))
+        return;
     MIO_TL_END(b);
     MIO_TRACE(b, 15);
 }
@@ -458,26 +476,31 @@ void launch_attention(int G, dim3 grid, hipStream_t s, const LlmDims &d, const L
     }
 }
 
+// Entry pack (llm_device.h "kernel entry"): the state, K = wo.k, n_kv (the role split is
+// (pos / ATT_CHUNK + 1) * n_kv), the O workgroups, n_ctx. pos and the end-token flag are vector
+// loads through the pack (state_issue), in flight beside the batch of the other arguments.
 template <int HD, int G, int NP, int T, int SU, bool DG>
-__global__ __launch_bounds__(MT) void k_att_o(LlmDims d, const float *q_norm, const float *k_norm, const float *bqkv,
+__global__ __launch_bounds__(MT) void k_att_o(StepState *st, int K, int n_kv, int no, int n_ctx, LlmDims d,
+                                              const float *q_norm, const float *k_norm, const float *bqkv,
                                               _Float16 *kc, _Float16 *vc, QMat wo, LlmBuffers b) {
     constexpr bool kDiag = DG;
-    MIO_TRACE(b, 0);
-    MIO_TL_BEGIN(b);
-    asm volatile("" ::"s"(kc), "s"(vc), "s"(d.n_ctx), "s"(b.qkv), "s"(b.rope), "s"(q_norm), "s"(k_norm),
-                 "s"(b.part), "s"(d.max_splits), "s"(bqkv), "s"(b.att), "s"(b.att_cnt));
-    const int pos = cur_pos(b.st, d);
-    if (b.st->done) return;  // no merge is signalled after an end token: nobody may wait
-    const int bid = blockIdx.x, n_act = (pos / ATT_CHUNK + 1) * d.n_kv;
+    MIO_ENTRY_STAMPS();
+    const StateRegs sr = state_issue(st);
+    MIO_ENTRY_REST("s"(kc), "s"(vc), "s"(d.n_ctx), "s"(b.qkv), "s"(b.rope), "s"(q_norm), "s"(k_norm), "s"(b.part),
+                   "s"(d.max_splits), "s"(bqkv), "s"(b.att), "s"(b.att_cnt), MIO_PIN_QMAT(wo), "s"(b.x));
+    MIO_ENTRY_COMMIT(b);
+    const int pos = state_pos(sr, n_ctx);
+    if (state_done(sr)) return;  // no merge is signalled after an end token: nobody may wait
+    const int bid = blockIdx.x, n_act = (pos / ATT_CHUNK + 1) * n_kv;
     if (bid < n_act) {
         if (MIO_TIDX >= AttCfg<HD>::NT) return;  // whole waves; s_barrier counts the live ones
-        if (!attention_wg<HD, G, DG>(d, q_norm, k_norm, bqkv, kc, vc, b, bid / d.n_kv, bid % d.n_kv, pos,
+        if (!attention_wg<HD, G, DG>(d, q_norm, k_norm, bqkv, kc, vc, b, false, bid / n_kv, bid % n_kv, pos,
                                      b.att_cnt + kRdyOff))
             return;
     } else {
-        const int no = matvec_grid_n(d.n_wg, wo.rows), ob = bid - n_act;
+        const int ob = bid - n_act;
         if (ob >= no) return;
-        o_consumer<NP, T, SU, DG>(d, wo, b, ob, no);
+        o_consumer<NP, T, SU, DG>(d, wo, K, b, ob, no);
     }
     MIO_TL_END(b);
     MIO_TRACE(b, 15);
@@ -488,7 +511,8 @@ void launch_att_o(int G, int grid, size_t lds, hipStream_t s, const LlmDims &d, 
                   _Float16 *vc, const LlmBuffers &b) {
     const float *qn = L.q_norm, *kn = L.k_norm, *bi = L.bqkv;
 #define MIO_ATT_O(HH, GG) \
-    hipLaunchKernelGGL((k_att_o<HH, GG, NP, T, SU, DG>), dim3(grid), dim3(MT), lds, s, d, qn, kn, bi, kc, vc, L.wo, b)
+    hipLaunchKernelGGL((k_att_o<HH, GG, NP, T, SU, DG>), dim3(grid), dim3(MT), lds, s, b.st, L.wo.k, d.n_kv,        \
+                       matvec_grid_n(d.n_wg, L.wo.rows), d.n_ctx, d, qn, kn, bi, kc, vc, L.wo, b)
     if (d.hd == 128 && G == 2) MIO_ATT_O(128, 2);
     if (d.hd == 64 && G == 3) MIO_ATT_O(64, 3);
     if (d.hd == 64 && G == 4) MIO_ATT_O(64, 4);
@@ -686,8 +710,8 @@ void launch_step_kernel(StepKind which, const StepCtx &c, int il, const LlmBuffe
         case kLmHead: {
             const LlmDims dl = lm_dims(d);
             dispatch_nt<true, false>(d.n_embd, lm.type, [&]<int NP, int T>() {
-                hipLaunchKernelGGL((k_lm_head<NP, T, DG>), dim3(lm_head_blocks(d)), dim3(MT), smem_bytes(d.n_embd), s, dl,
-                                   out_norm, lm, b);
+                hipLaunchKernelGGL((k_lm_head<NP, T, DG>), dim3(lm_head_blocks(d)), dim3(MT), smem_bytes(d.n_embd), s, b.x,
+                                   out_norm, b.st, d.n_embd, lm_head_blocks(d), dl, out_norm, lm, b);
             });
             break;
         }

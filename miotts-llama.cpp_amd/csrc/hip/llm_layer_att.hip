@@ -24,16 +24,20 @@ namespace mio {
 namespace {
 
 template <int NP, int TQ, int TV, int SU, int HD, int G, bool DG>
-__device__ __forceinline__ void qkv_producer(const LlmDims &d, const float *norm_w, const QMat &wq, const QMat &wk,
-                                             const QMat &wv, int g_qk, int GW, const LlmBuffers &b) {
+__device__ __forceinline__ void qkv_producer(const float *x, const float *norm_w, const StepState *st, int K,
+                                             const LlmDims &d, const QMat &wq, const QMat &wk, const QMat &wv, int g_qk,
+                                             int GW, const LlmBuffers &b, unsigned long long entry_rt_,
+                                             unsigned long long entry_cc_) {
     constexpr bool kDiag = DG;
-    const int o1 = wq.rows, o2 = wq.rows + wk.rows;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int K = d.n_embd;
-    const Smem s = carve(smem, K);
-    const uint32_t dn = done_issue(b);
+    const uint32_t dn = done_issue_st(st);
     XRegs<NP> xr;
-    load_x(b.x, norm_w, K, xr);
+    load_x(x, norm_w, K, xr);
+    MIO_ENTRY_REST(MIO_PIN_QMAT(wq), MIO_PIN_QMAT(wk), MIO_PIN_QMAT(wv), "s"(b.att_cnt), "s"(b.qkv), "s"(d.eps));
+    MIO_ENTRY_COMMIT(b);
+    zero_ffn_counters(b.att_cnt);
+    const int o1 = wq.rows, o2 = wq.rows + wk.rows;
+    const Smem s = carve(smem, K);
     auto put = [&](int row, float v) { st1_sc1(b.qkv, (uint32_t)row * 4, v); };
     Frag ga[Cfg<NP, SU>::U], gb[Cfg<NP, SU>::U];
     int lo, hi, ra, rb;
@@ -84,34 +88,39 @@ __device__ __forceinline__ void qkv_producer(const LlmDims &d, const float *norm
     }
 }
 
+// Entry pack (llm_device.h "kernel entry"): x, the attention norm weight, the state, K = n_embd,
+// the role split (g_qk, GW) and n_kv ((pos / ATT_CHUNK + 1) * n_kv attention workgroups); the
+// earlier list follows (its norm_w, g_qk and GW are the pack's now and stay unnamed).
 template <int NP, int TQ, int TV, int SU, int HD, int G, int TO, int SUO, bool DG>
-__global__ __launch_bounds__(MT) void k_layer_att(LlmDims d, const float *norm_w, QMat wq, QMat wk, QMat wv, int g_qk,
-                                                  int GW, const float *q_norm, const float *k_norm, const float *bqkv,
+__global__ __launch_bounds__(MT) void k_layer_att(const float *x, const float *norm_w, StepState *st, int K, int g_qk,
+                                                  int GW, int n_kv, LlmDims d, const float *, QMat wq, QMat wk, QMat wv,
+                                                  int, int, const float *q_norm, const float *k_norm, const float *bqkv,
                                                   _Float16 *kc, _Float16 *vc, QMat wo, LlmBuffers b) {
     constexpr bool kDiag = DG;
-    MIO_TRACE(b, 0);
-    MIO_TL_BEGIN(b);
-    if (blockIdx.x == 2 && MIO_TIDX < 2 * kFfnShards)  // the previous k_ffn's h counters (kernel boundary ordered)
-        __hip_atomic_store((__attribute__((address_space(1))) int *)(b.att_cnt + kFfnOff + kFfnStride * MIO_TIDX), 0,
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    MIO_ENTRY_STAMPS();
     const int bid = blockIdx.x;
     if (bid < GW) {
-        qkv_producer<NP, TQ, TV, SU, HD, G, DG>(d, norm_w, wq, wk, wv, g_qk, GW, b);
+        qkv_producer<NP, TQ, TV, SU, HD, G, DG>(x, norm_w, st, K, d, wq, wk, wv, g_qk, GW, b, entry_rt_, entry_cc_);
     } else {
-        asm volatile("" ::"s"(kc), "s"(vc), "s"(d.n_ctx), "s"(b.qkv), "s"(b.rope), "s"(q_norm), "s"(k_norm),
-                     "s"(b.part), "s"(d.max_splits), "s"(bqkv), "s"(b.att), "s"(b.att_cnt));
-        const int pos = cur_pos(b.st, d);
-        if (b.st->done) return;  // the producers return too: nobody signals, nobody waits
-        const int ab = bid - GW, n_act = (pos / ATT_CHUNK + 1) * d.n_kv;
+        // pos and the end-token flag through the pack (state_issue): beside the batch, not behind it
+        const StateRegs sr = state_issue(st);
+        MIO_ENTRY_REST("s"(kc), "s"(vc), "s"(d.n_ctx), "s"(b.qkv), "s"(b.rope), "s"(q_norm), "s"(k_norm), "s"(b.part),
+                       "s"(d.max_splits), "s"(bqkv), "s"(b.att), "s"(b.att_cnt), MIO_PIN_QMAT(wo), "s"(d.n_wg),
+                       "s"(b.x));
+        MIO_ENTRY_COMMIT(b);
+        zero_ffn_counters(b.att_cnt);
+        const int pos = state_pos(sr, d.n_ctx);
+        if (state_done(sr)) return;  // the producers return too: nobody signals, nobody waits
+        const int ab = bid - GW, n_act = (pos / ATT_CHUNK + 1) * n_kv;
         if (ab < n_act) {
             if (MIO_TIDX >= AttCfg<HD>::NT) return;  // whole waves; s_barrier counts the live ones
-            if (!attention_wg<HD, G, DG, true>(d, q_norm, k_norm, bqkv, kc, vc, b, ab / d.n_kv, ab % d.n_kv, pos,
+            if (!attention_wg<HD, G, DG, true>(d, q_norm, k_norm, bqkv, kc, vc, b, false, ab / n_kv, ab % n_kv, pos,
                                                b.att_cnt + kRdyOff))
                 return;
         } else {
             const int no = matvec_grid_n(d.n_wg, wo.rows), ob = ab - n_act;
             if (ob >= no) return;
-            o_consumer<1, TO, SUO, DG>(d, wo, b, ob, no);
+            o_consumer<1, TO, SUO, DG>(d, wo, wo.k, b, ob, no);
         }
     }
     MIO_TL_END(b);
@@ -173,9 +182,9 @@ bool launch(const LlmDims &d, const LayerW &L, _Float16 *kc, _Float16 *vc, const
         s.suo == SUO) {                                                                                                \
         found = true;                                                                                                  \
         if (!dry)                                                                                                      \
-            hipLaunchKernelGGL((k_layer_att<NP, TQ, TV, SU, HD, G, TO, SUO, DG>), dim3(grid), dim3(MT), lds, st, d,   \
-                               L.attn_norm, L.wq, L.wk, L.wv, s.g_qk, s.GW, L.q_norm, L.k_norm, L.bqkv, kc, vc, L.wo, \
-                               b);                                                                                     \
+            hipLaunchKernelGGL((k_layer_att<NP, TQ, TV, SU, HD, G, TO, SUO, DG>), dim3(grid), dim3(MT), lds, st, b.x, \
+                               L.attn_norm, b.st, d.n_embd, s.g_qk, s.GW, d.n_kv, d, L.attn_norm, L.wq, L.wk, L.wv,    \
+                               s.g_qk, s.GW, L.q_norm, L.k_norm, L.bqkv, kc, vc, L.wo, b);                             \
     }
     MIO_LAYER_ATT_SHAPES(MIO_LA_CASE)
 #undef MIO_LA_CASE

@@ -1,7 +1,10 @@
 """Diagnostic: timeline of one graph-replayed decode step (1.7B preset by default): per
 kernel the duration (first workgroup start -> last workgroup end), the spread of workgroup
 start and end times, and the gaps between consecutive launches. Run on the GPU box:
-    python tools/step_timeline.py [--preset 3] [--pos 700]"""
+    python tools/step_timeline.py [--preset 3] [--pos 700]
+--diag, on a library built with -DMIO_TL_DIAG (make BUILD=build_x EXTRA=-DMIO_TL_DIAG, MIO_BUILD_DIR):
+the prologue stamps of the RMSNorm roles instead (k_ffn's gate|up and k_layer_att's q|k|v producers):
+"x arrived" (stamp 3 of rmsnorm_quant: the activation consumed), reduced, normalized, quantized."""
 import argparse
 import os
 import sys
@@ -14,6 +17,7 @@ import miotts_amd as m  # noqa: E402
 p = argparse.ArgumentParser()
 p.add_argument("--preset", type=int, default=3)
 p.add_argument("--pos", type=int, default=700)
+p.add_argument("--diag", action="store_true")
 a = p.parse_args()
 path = f"/tmp/trace_llm{a.preset}.gguf"
 if not os.path.exists(path):
@@ -25,6 +29,20 @@ llm.generate([256, 257, 65, 258, 257], a.pos, 0.8, 1, allow=(m.SYNTH_SPEECH0, m.
 t = llm.timeline()
 nl = t.shape[0]
 names = [m.STEP_KIND_NAMES[k] for k in llm.step_kinds()]
+if a.diag:
+    # the producers are the first workgroups of the grid: matvec_grid of the role's rows
+    cu = dev.cu_count()
+    n_prod = {"ffn": min(llm.n_ff // 8, cu), "layer_att": min((llm.n_head + 2 * llm.n_kv) * llm.head_dim // 8, cu)}
+    for kind, n in n_prod.items():
+        idx = [i for i, k in enumerate(names) if k == kind]
+        if not idx:
+            continue
+        T = t[idx][:, :n]
+        base = np.nanmin(t[idx][:, :, 0], axis=1)[:, None, None]
+        for k, what in ((3, "x arrived"), (4, "reduced"), (5, "normalized"), (2, "quantized")):
+            print(f"  {kind:10s} {n} producers {what:10s} {np.nanmedian(T[:, :, k] - base[:, :, 0]):.2f} us after the "
+                  f"launch's first start, {np.nanmedian(T[:, :, k] - T[:, :, 0]):.2f} after the workgroup's own")
+    sys.exit(0)
 s0 = np.nanmin(t[:, :, 0], axis=1)
 s1 = np.nanmax(t[:, :, 0], axis=1)
 e0 = np.nanmin(t[:, :, 7], axis=1)
