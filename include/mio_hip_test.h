@@ -47,6 +47,14 @@ int mio_dequantize_rows(uint32_t type, const void *rows_bytes, int rows, int k, 
  * *nbytes = its size, off[4] = the planes' byte offsets; out NULL returns those alone. */
 int mio_debug_to_split(uint32_t type, const void *rows_bytes, int rows, int k, uint8_t *out, uint64_t *nbytes,
                        uint64_t *off);
+/* The weight-type table (csrc/weight_types.h) as the host reads it, no GPU: for a [rows][k] matrix
+ * of a device weight type (8, 11..14, 30), stride[4] = the split layout's plane row strides in
+ * bytes (0: no such plane), off[4] = the planes' offsets, moved[4] = the bytes by which taking
+ * rows [r0, r0 + n) (qmat_rows) moves each plane pointer. */
+int mio_debug_weight_layout(uint32_t type, int rows, int k, int r0, int n, uint64_t *stride, uint64_t *off,
+                            uint64_t *moved);
+/* 1 where the q|k|v launches exist for attn_v of ggml type tv beside q|k of type tq, else 0. */
+int mio_debug_attn_v_supported(int tq, int tv);
 /* The decode step's activation quantizer (one 512-thread workgroup, the kernels' own prologue
  * code) on x[k]: type 12 -> Q8_K, 8 -> Q8_0, 30 -> bf16 rounding; w != NULL: RMSNorm(x, eps) * w
  * first; sc1 != 0: the activation loaded the way an in-launch hand-off loads it. Out, the

@@ -57,7 +57,7 @@ __global__ __launch_bounds__(MT) void k_attn_in(float *x, const float *norm_w, S
             if (pend) {
                 const SampleCfg sc = *b.cfg;
                 const int tok = sample_token<MT>(b.smp, nblk, sc, step, rs_, ri_);
-                embed_regs<NP, TQ == 11>(emb, tok, K, xr);  // a Q3_K table: in a Q3_K file only (llm_load)
+                embed_regs<NP, TQ == GGML_Q3_K>(emb, tok, K, xr);  // a Q3_K table: in a Q3_K file only (llm_load)
                 if (blockIdx.x == 0) {
 #pragma unroll
                     for (int i = 0; i < NP; ++i) {

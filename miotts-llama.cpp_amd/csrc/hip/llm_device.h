@@ -442,7 +442,7 @@ __device__ __forceinline__ void x_after_weights_plain(XRegs<XV> &xr) {
 
 // Activation kind of a weight type (ggml's vec_dot_type): 0 Q8_0 (Q8_0 weights), 1 Q8_K
 // (Q3_K / Q4_K / Q5_K / Q6_K), 2 BF16 (BF16 weights: the activation rounded to bf16, ggml_fp32_to_bf16).
-__host__ __device__ constexpr int akind(int T) { return T == 30 ? 2 : (T == 8 ? 0 : 1); }
+__host__ __device__ constexpr int akind(int T) { return T == GGML_BF16 ? 2 : (T == GGML_Q8_0 ? 0 : 1); }
 
 // ggml_compute_fp32_to_bf16: round to nearest even, NaN kept quiet
 __device__ __forceinline__ uint32_t f32_to_bf16(float f) {
@@ -741,43 +741,50 @@ __device__ __forceinline__ Frag load_frag(const QMat W, int row, int pass) {
     const uint32_t R = (uint32_t)W.rows,
                    r = (uint32_t)__builtin_amdgcn_readfirstlane(min(max(row, 0), W.rows - 1));
     Frag f;
-    if constexpr (T == 12) {
+    if constexpr (T == GGML_Q4_K) {
         const int nsb = W.k >> 8, sb = min(pass * 8 + (lane >> 3), nsb - 1), pc = lane & 7;
         const uint32_t qb = (uint32_t)(W.k / 2), hb = (uint32_t)nsb * 16;
+        static_assert(stride_is(T, 0, 1, 2) && stride_is(T, 1, 16, 256), "Q4_K row strides");
         f.a = bld16<AUX>(W.p0, R * qb, sb * 128 + pc * 16, r * qb);
         // header dword (lane & 3) only: both quads of the superblock's 8 lanes hold all four,
         // broadcast by DPP in dot_frag (a quarter of the load-return traffic of 16 B per lane)
         f.c = bld4<AUX>(W.p1, R * hb, sb * 16 + 4 * (pc & 3), r * hb);
         f.b = make_uint4(0, 0, 0, 0);
         f.e = 0;
-    } else if constexpr (T == 13) {
+    } else if constexpr (T == GGML_Q5_K) {
         const int nsb = W.k >> 8, sb = min(pass * 8 + (lane >> 3), nsb - 1), pc = lane & 7;
         const uint32_t qb = (uint32_t)(W.k / 2), fb = (uint32_t)(W.k / 8), hb = (uint32_t)nsb * 16;
+        static_assert(stride_is(T, 0, 1, 2) && stride_is(T, 1, 1, 8) && stride_is(T, 2, 16, 256), "Q5_K row strides");
         f.a = bld16<AUX>(W.p0, R * qb, sb * 128 + pc * 16, r * qb);
         f.b = bld16<AUX>(W.p1, R * fb, sb * 32 + 16 * (pc & 1), r * fb);
         f.c = bld4<AUX>(W.p2, R * hb, sb * 16 + 4 * (pc & 3), r * hb);
         f.e = 0;
-    } else if constexpr (T == 14) {
+    } else if constexpr (T == GGML_Q6_K) {
         const int nsb = W.k >> 8, sb = min(pass * 8 + (lane >> 3), nsb - 1), pc = lane & 7;
         const uint32_t lb = (uint32_t)(W.k / 2), hb = (uint32_t)(W.k / 4), sbb = (uint32_t)(W.k / 16),
                        db = (uint32_t)nsb * 2;
+        static_assert(stride_is(T, 0, 1, 2) && stride_is(T, 1, 1, 4) && stride_is(T, 2, 1, 16) && stride_is(T, 3, 2, 256),
+                      "Q6_K row strides");
         f.a = bld16<AUX>(W.p0, R * lb, sb * 128 + pc * 16, r * lb);
         f.b = bld16<AUX>(W.p1, R * hb, sb * 64 + 32 * (pc >> 2) + 16 * (pc & 1), r * hb);
         f.c = bld2<AUX>(W.p2, R * sbb, sb * 16 + 2 * pc, r * sbb);
         f.e = bld2<AUX>(W.p3, R * db, sb * 2, r * db);
-    } else if constexpr (T == 11) {
+    } else if constexpr (T == GGML_Q3_K) {
         const int nsb = W.k >> 8, sb = min(pass * 8 + (lane >> 3), nsb - 1), pc = lane & 7;
         const int P = 4 * (pc & 1) + (pc >> 1);
         const uint32_t qb = (uint32_t)(W.k / 4), hb = (uint32_t)(W.k / 8), sbb = (uint32_t)(W.k / 16),
                        db = (uint32_t)nsb * 2;
+        static_assert(stride_is(T, 0, 1, 4) && stride_is(T, 1, 1, 8) && stride_is(T, 2, 1, 16) && stride_is(T, 3, 2, 256),
+                      "Q3_K row strides");
         const uint2 q = bld8<AUX>(W.p0, R * qb, sb * 64 + P * 8, r * qb);
         f.a = make_uint4(q.x, q.y, 0, 0);
         f.b = make_uint4(bld4<AUX>(W.p1, R * hb, sb * 32 + P * 4, r * hb), 0, 0, 0);
         f.c = bld2<AUX>(W.p2, R * sbb, sb * 16 + 2 * P, r * sbb);
         f.e = bld2<AUX>(W.p3, R * db, sb * 2, r * db);
-    } else if constexpr (T == 30) {
+    } else if constexpr (T == GGML_BF16) {
         // element offsets clamped into the row (past K: another valid piece, zeroed in dot_frag)
         const uint32_t rb = (uint32_t)W.k * 2;
+        static_assert(stride_is(T, 0, 2, 1), "BF16 row stride");
         auto off = [&](int i) { return (uint32_t)min(pass * 2048 + 512 * i + 8 * lane, W.k - 8) * 2u; };
         f.a = bld16<AUX>(W.p0, R * rb, off(0), r * rb);
         f.b = bld16<AUX>(W.p0, R * rb, off(1), r * rb);
@@ -788,6 +795,7 @@ __device__ __forceinline__ Frag load_frag(const QMat W, int row, int pass) {
     } else {
         const int nb = W.k >> 5, b = min(pass * 64 + lane, nb - 1);
         const uint32_t qb = (uint32_t)W.k, db = (uint32_t)nb * 2;
+        static_assert(stride_is(GGML_Q8_0, 0, 1, 1) && stride_is(GGML_Q8_0, 1, 2, 32), "Q8_0 row strides");
         f.a = bld16<AUX>(W.p0, R * qb, 32 * b, r * qb);
         f.b = bld16<AUX>(W.p0, R * qb, 32 * b + 16, r * qb);
         f.c = 0;
@@ -800,11 +808,11 @@ template <int T>
 __device__ __forceinline__ ALane load_alane(const ActL &a, int K, int pass) {
     const int lane = MIO_TIDX & 63;
     ALane r;
-    if constexpr (T == 11 || T == 12 || T == 13 || T == 14) {
+    if constexpr (is_kquant(T)) {
         const int nsb = K >> 8, sb = pass * 8 + (lane >> 3), pc = lane & 7;
         const int sbc = sb < nsb ? sb : 0;
         int e, e2;
-        if constexpr (T == 11 || T == 12 || T == 13) {
+        if constexpr (T == GGML_Q3_K || has_mins(T)) {
             e = sbc * 256 + 64 * (pc >> 1) + 16 * (pc & 1);
             e2 = e + 32;
         } else {
@@ -817,7 +825,7 @@ __device__ __forceinline__ ALane load_alane(const ActL &a, int K, int pass) {
         r.b0 = a.bs[e >> 4];
         r.b1 = a.bs[e2 >> 4];
         r.d = a.d[sbc];
-    } else if constexpr (T == 30) {
+    } else if constexpr (T == GGML_BF16) {
         auto at = [&](int i) {
             const int e = min(pass * 2048 + 512 * i + 8 * lane, K - 8);
             return *reinterpret_cast<const int4 *>(a.qs + 2 * e);
@@ -845,10 +853,10 @@ struct LaneTerms {
 };
 template <int T>
 __device__ __forceinline__ LaneTerms lane_terms(const Frag &f, const ALane &al) {
-    static_assert(T == 11 || T == 12 || T == 13 || T == 14, "K-quants");
+    static_assert(is_kquant(T), "K-quants");
     const int lane = MIO_TIDX & 63;
     LaneTerms t;
-    if constexpr (T == 11) {
+    if constexpr (T == GGML_Q3_K) {
         // the codes of a run's elements 4 k .. 4 k + 3 are (q >> 2 k) & 0x03030303; their high bits
         // sit at bit hb = k (run lo) or 4 + k (run hi) of each byte of h and move to bit 2. The
         // codes enter as 0 .. 7; their - 4 comes off through the activation's 16-element bsums
@@ -870,13 +878,13 @@ __device__ __forceinline__ LaneTerms lane_terms(const Frag &f, const ALane &al) 
         t.isum = __mul24(sa, dlo - 4 * al.b0) + __mul24(sb, dhi - 4 * al.b1);
         t.imin = 0;
         t.hd = f.e;
-    } else if constexpr (T == 12 || T == 13) {
+    } else if constexpr (has_mins(T)) {
         const int jj = (lane & 7) >> 1;
         uint4 h;  // the superblock header {d|dmin, scale/min words} from the quad's four dwords
         // Q4_K: broadcasts without an `old` operand (four zeroing moves less per unit). Q5_K keeps
         // the zeroed form: without it k_pf_ffn_in<6, 13, 0> spills one more dword.
         auto bc = [&]<int CTRL>() {
-            if constexpr (T == 12) return (uint32_t)dpp_perm<CTRL>((int)f.c);
+            if constexpr (T == GGML_Q4_K) return (uint32_t)dpp_perm<CTRL>((int)f.c);
             else return (uint32_t)dpp_i<CTRL>((int)f.c);
         };
         h.x = bc.template operator()<0x00>();
@@ -890,11 +898,11 @@ __device__ __forceinline__ LaneTerms lane_terms(const Frag &f, const ALane &al) 
         // Q5_K: the fifth bit of sub-block 2 jj (low nibbles) is bit 2 jj of each qh byte, of
         // sub-block 2 jj + 1 (high nibbles) the next one; moved to bit 4 of the code
         auto lo = [&](uint32_t q, uint32_t h) {
-            if constexpr (T == 13) return (int)((q & M4) | (((h >> (2 * jj)) & 0x01010101u) << 4));
+            if constexpr (T == GGML_Q5_K) return (int)((q & M4) | (((h >> (2 * jj)) & 0x01010101u) << 4));
             else return (int)(q & M4);
         };
         auto hi = [&](uint32_t q, uint32_t h) {
-            if constexpr (T == 13) return (int)(((q >> 4) & M4) | (((h >> (2 * jj + 1)) & 0x01010101u) << 4));
+            if constexpr (T == GGML_Q5_K) return (int)(((q >> 4) & M4) | (((h >> (2 * jj + 1)) & 0x01010101u) << 4));
             else return (int)((q >> 4) & M4);
         };
         int dlo = 0, dhi = 0;
@@ -936,7 +944,7 @@ __device__ __forceinline__ LaneTerms lane_terms(const Frag &f, const ALane &al) 
 // semantics; every caller runs these operations in this order).
 template <int T>
 __device__ __forceinline__ float sb_term(int isum, int imin, uint32_t hd, float ad) {
-    if constexpr (T == 14 || T == 11) {
+    if constexpr (scale_only(T)) {
         const float d = h2f(hd) * ad;
         return d * (float)isum;
     } else {
@@ -955,13 +963,13 @@ __device__ __forceinline__ float sb_term(int isum, int imin, uint32_t hd, float 
 template <int T>
 __device__ __forceinline__ float dot_frag(const Frag &f, const ALane &al, int K, int pass) {
     const int lane = MIO_TIDX & 63;
-    if constexpr (T == 11 || T == 12 || T == 13 || T == 14) {
+    if constexpr (is_kquant(T)) {
         const LaneTerms t = lane_terms<T>(f, al);
         const int isum = sum8_i(t.isum);
-        const int imin = T == 14 || T == 11 ? 0 : sum8_i(t.imin);
+        const int imin = scale_only(T) ? 0 : sum8_i(t.imin);
         const float v = sb_term<T>(isum, imin, t.hd, al.d);
         return pass * 8 + (lane >> 3) < (K >> 8) ? v : 0.0f;
-    } else if constexpr (T == 30) {
+    } else if constexpr (T == GGML_BF16) {
         // ggml_vec_dot_bf16 on the bf16-rounded activation: products of bf16 pairs are exact
         // in f32; 8 weights per register, summed by v_dot2 in register order (pieces past K
         // zeroed on both sides)
@@ -1000,7 +1008,7 @@ __device__ __forceinline__ float dot_frag(const Frag &f, const ALane &al, int K,
 // Row total of the per-lane partials (accumulated over the row's passes), wave-uniform.
 template <int T>
 __device__ __forceinline__ float row_total(float acc) {
-    if constexpr (T == 8 || T == 30) acc = sum8_f(acc);
+    if constexpr (lane_blocks(T)) acc = sum8_f(acc);
     return sum_lanes7(acc);
 }
 
@@ -1025,7 +1033,7 @@ template <int T>
 __device__ __forceinline__ float pair_term(const Frag &fa, const Frag &fb, const ALane &al, bool side_b, bool in_k) {
     const LaneTerms a = lane_terms<T>(fa, al), b = lane_terms<T>(fb, al);
     const int isum = pair_sum8(a.isum, b.isum, side_b);
-    const int imin = T == 14 || T == 11 ? 0 : pair_sum8(a.imin, b.imin, side_b);
+    const int imin = scale_only(T) ? 0 : pair_sum8(a.imin, b.imin, side_b);
     const float v = sb_term<T>(isum, imin, side_b ? b.hd : a.hd, al.d);
     return in_k ? v : 0.0f;
 }
@@ -1053,7 +1061,7 @@ __device__ __forceinline__ float swapadd32(float a, float b) {
 // whose instantiations would lose an occupancy step to the joint form's registers (k_ffn<1, 13,
 // 6, 3, 13, 3> 80 -> 81 VGPRs, k_attn_in<1, 12, 12, 6> 64 -> 65, k_attn_out<1, 14, 6> 79 -> 84)
 template <int T, int NP, int NM, int SU>
-constexpr bool joint_rows = (T == 11 || T == 12 || T == 14) && NP == 1 && SU >= 2 && (NM == 2 || SU <= 4);
+constexpr bool joint_rows = (T == GGML_Q3_K || T == GGML_Q4_K || T == GGML_Q6_K) && NP == 1 && SU >= 2 && (NM == 2 || SU <= 4);
 
 // The rows of one group F (SU one-pass units: unit u = row lo + u / NM, matrix u % NM; units
 // past the share are clamped duplicates, computed and dropped) reduced pairwise, fin(row, dot0,
@@ -1287,14 +1295,18 @@ __device__ inline void wave_range(const LlmDims &d, int R, int &lo, int &hi) {
 // ------------------------------------------------------------------ embedding rows
 // Q3: the table may be Q3_K too (an untied token_embd of a Q3_K_S / _M / _L file). Only the kernels
 // of such a model are built with it, so the others' embedding lookups stay the code they were.
+// The launches of the embedding kernels pick the Q3 form by this and nothing else.
+inline bool q3_table(const QMat &tok_embd) { return tok_embd.type == GGML_Q3_K; }
 template <bool Q3 = false>
 __device__ float dequant_elem(const QMat &W, int row, int e) {
     if constexpr (Q3) {
-        if (W.type == 11) {
+        if (W.type == GGML_Q3_K) {
             // quant.h: element c of the superblock lies in piece pc's run t at index i
             const int nsb = W.k >> 8, sb = e >> 8, c = e & 255, pc = 2 * (c >> 6) + ((c >> 4) & 1), t = (c >> 5) & 1,
                       i = c & 15;
             const int P = 4 * (pc & 1) + (pc >> 1);
+            static_assert(stride_is(GGML_Q3_K, 0, 1, 4) && stride_is(GGML_Q3_K, 1, 1, 8) && stride_is(GGML_Q3_K, 2, 1, 16) &&
+                          stride_is(GGML_Q3_K, 3, 2, 256), "Q3_K row strides (p3 in f16 units)");
             const uint8_t qb = W.p0[(size_t)row * (W.k / 4) + sb * 64 + 8 * P + 4 * t + (i & 3)];
             const uint8_t hb = W.p1[(size_t)row * (W.k / 8) + sb * 32 + 4 * P + (i & 3)];
             const int q = (int)(((qb >> (2 * (i >> 2))) & 3) | (((hb >> (4 * t + (i >> 2))) & 1) << 2)) - 4;
@@ -1303,19 +1315,23 @@ __device__ float dequant_elem(const QMat &W, int row, int e) {
             return dd * (float)sc * (float)q;  // dequantize_row_q3_K: dl = d * (scale - 32), y = dl * q
         }
     }
-    if (W.type == 12 || W.type == 13) {
+    if (W.type == GGML_Q4_K || W.type == GGML_Q5_K) {
         const int nsb = W.k >> 8, sb = e >> 8, c = e & 255, j = c >> 6, w = c & 63, hi = w >> 5, l = w & 31;
+        static_assert(stride_is(GGML_Q4_K, 0, 1, 2) && stride_is(GGML_Q4_K, 1, 16, 256) && stride_is(GGML_Q5_K, 0, 1, 2) &&
+                      stride_is(GGML_Q5_K, 1, 1, 8) && stride_is(GGML_Q5_K, 2, 16, 256), "Q4_K / Q5_K row strides");
         const uint8_t q = W.p0[(size_t)row * (W.k / 2) + sb * 128 + 32 * j + l];
-        const uint8_t *hd = (W.type == 13 ? W.p2 : W.p1) + ((size_t)row * nsb + sb) * 16;
+        const uint8_t *hd = (W.type == GGML_Q5_K ? W.p2 : W.p1) + ((size_t)row * nsb + sb) * 16;
         const uint32_t F = (uint32_t)hd[4 + 3 * j] | ((uint32_t)hd[5 + 3 * j] << 8) | ((uint32_t)hd[6 + 3 * j] << 16);
         const int sc = (F >> (12 * hi)) & 63, m = (F >> (12 * hi + 6)) & 63;
         const float d1 = h2f(hd[0] | (hd[1] << 8)) * sc, m1 = h2f(hd[2] | (hd[3] << 8)) * m;
         int code = hi ? (q >> 4) : (q & 0xF);
         // Q5_K: sub-block 2 j + hi's fifth bit of weight l is bit 2 j + hi of qh[l]
-        if (W.type == 13) code += ((W.p1[(size_t)row * (W.k / 8) + sb * 32 + l] >> (2 * j + hi)) & 1) << 4;
+        if (W.type == GGML_Q5_K) code += ((W.p1[(size_t)row * (W.k / 8) + sb * 32 + l] >> (2 * j + hi)) & 1) << 4;
         return d1 * (float)code - m1;
-    } else if (W.type == 14) {
+    } else if (W.type == GGML_Q6_K) {
         const int nsb = W.k >> 8, sb = e >> 8, c = e & 255, n = c >> 7, w = c & 127, g = w >> 5, l = w & 31;
+        static_assert(stride_is(GGML_Q6_K, 0, 1, 2) && stride_is(GGML_Q6_K, 1, 1, 4) && stride_is(GGML_Q6_K, 2, 1, 16) &&
+                      stride_is(GGML_Q6_K, 3, 2, 256), "Q6_K row strides (p3 in f16 units)");
         const uint8_t ql = W.p0[(size_t)row * (W.k / 2) + sb * 128 + 64 * n + l + 32 * (g & 1)];
         const uint8_t qh = W.p1[(size_t)row * (W.k / 4) + sb * 64 + 32 * n + l];
         const int q = (int)((g < 2 ? (ql & 0xF) : (ql >> 4)) | (((qh >> (2 * g)) & 3) << 4)) - 32;
@@ -1323,11 +1339,13 @@ __device__ float dequant_elem(const QMat &W, int row, int e) {
         const int sc = ((const int8_t *)W.p2)[(size_t)row * (W.k / 16) + sb * 16 + 2 * (4 * sn + (sw & 3)) + (sw >> 2)];
         const float dd = h2f(((const uint16_t *)W.p3)[(size_t)row * nsb + sb]);
         return dd * (float)sc * (float)q;
-    } else if (W.type == 30) {
+    } else if (W.type == GGML_BF16) {
+        static_assert(stride_is(GGML_BF16, 0, 2, 1), "BF16 row stride (in bf16 units)");
         const uint16_t h = ((const uint16_t *)W.p0)[(size_t)row * W.k + e];
         return __uint_as_float((uint32_t)h << 16);
     } else {
         const int nb = W.k >> 5;
+        static_assert(stride_is(GGML_Q8_0, 0, 1, 1) && stride_is(GGML_Q8_0, 1, 2, 32), "Q8_0 row strides (p1 in f16 units)");
         const int8_t q = ((const int8_t *)W.p0)[(size_t)row * W.k + e];
         return (float)q * h2f(((const uint16_t *)W.p1)[(size_t)row * nb + (e >> 5)]);
     }
@@ -1533,38 +1551,63 @@ __device__ inline void embed_regs(const QMat &emb, int tok, int K, XRegs<XV> &xr
 // Calls f.template operator()<NP, T>() for the matrix's pass count and weight type. BF = false:
 // the int8 types only (the multi-token engine: BF16 models prefill token by token). Q3 = false:
 // without Q3_K (the lm_head launches: the loader refuses a Q3_K output matrix).
+// The helpers below return true when a case matched and f ran. The cases of a list run in the
+// list's order, which is the order the kernels are first used in and so their place in the code
+// object: append to a list, do not sort it. For the same reason they return `auto`: a function
+// with a deduced return type is instantiated where it is first called, as the chains of `if`
+// they replace were, not after the rest of the file; and their folds are left folds, whose
+// operands the compiler instantiates first to last.
+template <int NP, int... TS, class F>
+auto nt_types(int np, int type, F &&f) {
+    return (... || (np == NP && type == TS ? (f.template operator()<NP, TS>(), true) : false));
+}
+template <int... TS, class F>
+auto nt_cases(int np, int type, F &&f) {
+    return nt_types<1, TS...>(np, type, f) || nt_types<3, TS...>(np, type, f) || nt_types<6, TS...>(np, type, f);
+}
 template <bool BF = true, bool Q3 = true, class F>
 void dispatch_nt(int K, int type, F &&f) {
     const int np = pick_np(K);
-#define NT_CASE(NPV, TV) \
-    if (np == NPV && type == TV) return f.template operator()<NPV, TV>();
-    NT_CASE(1, 8) NT_CASE(1, 12) NT_CASE(1, 13) NT_CASE(1, 14) NT_CASE(3, 8) NT_CASE(3, 12) NT_CASE(3, 13)
-    NT_CASE(3, 14) NT_CASE(6, 8) NT_CASE(6, 12) NT_CASE(6, 13) NT_CASE(6, 14)
+    if (nt_cases<GGML_Q8_0, GGML_Q4_K, GGML_Q5_K, GGML_Q6_K>(np, type, f)) return;
     if constexpr (BF) {
-        NT_CASE(1, 30) NT_CASE(3, 30) NT_CASE(6, 30)
+        if (nt_cases<GGML_BF16>(np, type, f)) return;
     }
     if constexpr (Q3) {
-        NT_CASE(1, 11) NT_CASE(3, 11) NT_CASE(6, 11)
+        if (nt_cases<GGML_Q3_K>(np, type, f)) return;
     }
-#undef NT_CASE
     no_kernel("matvec", type, K);
+}
+
+// Calls f.template operator()<QK, V>() for the pairs of kQkvTypes in turn until one returns true.
+template <class F, size_t... I>
+auto for_qkv_types(F &&f, std::index_sequence<I...>) {
+    return (... || f.template operator()<kQkvTypes[I].qk, kQkvTypes[I].v>());
+}
+template <class F>
+auto for_qkv_types(F &&f) {
+    return for_qkv_types(f, std::make_index_sequence<kNumQkvTypes>{});
 }
 
 // attn_v's type beside q|k of type TQ (attn_v_supported): calls f.template operator()<TV>().
 template <int TQ, class F>
 void dispatch_v(int tv, F &&f) {
-    if (tv == TQ) return f.template operator()<TQ>();
-    if constexpr (TQ == 12 || TQ == 13) {
-        if (tv == 14) return f.template operator()<14>();
-    }
-    if constexpr (TQ == 14) {
-        if (tv == 12) return f.template operator()<12>();
-    }
-    if constexpr (TQ == 11) {
-        if (tv == 12) return f.template operator()<12>();
-        if (tv == 13) return f.template operator()<13>();
-    }
-    no_kernel("attn_v beside q|k", tv, TQ);
+    const bool hit = for_qkv_types([&]<int QK, int V>() {
+        if constexpr (QK == TQ) {
+            if (tv == V) return f.template operator()<V>(), true;
+        }
+        return false;
+    });
+    if (!hit) no_kernel("attn_v beside q|k", tv, TQ);
+}
+
+// Calls f.template operator()<T>() for a K-quant type; false: `type` is none.
+template <class F>
+auto dispatch_kquant(int type, F &&f) {
+    if (type == GGML_Q4_K) return f.template operator()<GGML_Q4_K>(), true;
+    if (type == GGML_Q5_K) return f.template operator()<GGML_Q5_K>(), true;
+    if (type == GGML_Q6_K) return f.template operator()<GGML_Q6_K>(), true;
+    if (type == GGML_Q3_K) return f.template operator()<GGML_Q3_K>(), true;
+    return false;
 }
 
 // Calls f.template operator()<NP>() for the pass count of K.

@@ -5,6 +5,8 @@
 
 #include <cstdint>
 
+#include "weight_types.h"
+
 namespace mio {
 
 // attention positions per chunk (one attention workgroup), = LlmDims::split. Every path
@@ -19,37 +21,20 @@ constexpr int kAttChunk = MIO_ATT_CHUNK;
 constexpr int kTlSlots = 2048;
 static_assert(kAttChunk == 32 || kAttChunk == 64 || kAttChunk == 128, "attention chunk");
 
-// One quantized matrix in the split layout (csrc/host/quant.h), rows x k.
+// One quantized matrix in the split layout (csrc/weight_types.h), rows x k.
 struct QMat {
-    int type;  // ggml type id: 8 Q8_0, 11 Q3_K, 12 Q4_K, 13 Q5_K, 14 Q6_K, 30 BF16
+    int type;  // GgmlType, one of kWeightTypes (weight_types.h)
     int rows, k;
     const uint8_t *p0, *p1, *p2, *p3;
 };
 
 // Rows [r0, r0 + n) of q as a matrix of its own (every split-layout stream is row-major).
 inline QMat qmat_rows(const QMat &q, int r0, int n) {
-    size_t rb[4] = {0, 0, 0, 0};
-    switch (q.type) {
-        case 8: rb[0] = (size_t)q.k, rb[1] = (size_t)q.k / 32 * 2; break;
-        case 11: rb[0] = (size_t)q.k / 4, rb[1] = (size_t)q.k / 8, rb[2] = (size_t)q.k / 16, rb[3] = (size_t)q.k / 256 * 2; break;
-        case 12: rb[0] = (size_t)q.k / 2, rb[1] = (size_t)q.k / 256 * 16; break;
-        case 13: rb[0] = (size_t)q.k / 2, rb[1] = (size_t)q.k / 8, rb[2] = (size_t)q.k / 256 * 16; break;
-        case 14: rb[0] = (size_t)q.k / 2, rb[1] = (size_t)q.k / 4, rb[2] = (size_t)q.k / 16, rb[3] = (size_t)q.k / 256 * 2; break;
-        case 30: rb[0] = (size_t)q.k * 2; break;
-        default: break;
-    }
     QMat v = q;
     v.rows = n;
-    v.p0 = q.p0 + rb[0] * r0, v.p1 = q.p1 + rb[1] * r0, v.p2 = q.p2 + rb[2] * r0, v.p3 = q.p3 + rb[3] * r0;
+    v.p0 = q.p0 + plane_row_bytes(q.type, q.k, 0) * r0, v.p1 = q.p1 + plane_row_bytes(q.type, q.k, 1) * r0;
+    v.p2 = q.p2 + plane_row_bytes(q.type, q.k, 2) * r0, v.p3 = q.p3 + plane_row_bytes(q.type, q.k, 3) * r0;
     return v;
-}
-
-// attn_v types the q|k|v launches are instantiated for beside q|k of type tq: its own, Q6_K
-// beside Q4_K / Q5_K (the *_K_M mixes' use_more_bits layers), Q4_K beside Q6_K, Q4_K / Q5_K
-// beside Q3_K (Q3_K_M / Q3_K_L).
-inline bool attn_v_supported(int tq, int tv) {
-    return tv == tq || ((tq == 12 || tq == 13) && tv == 14) || (tq == 14 && tv == 12) ||
-           (tq == 11 && (tv == 12 || tv == 13));
 }
 
 // Device-resident decode state (read by every kernel of a step; advanced by the sampler),

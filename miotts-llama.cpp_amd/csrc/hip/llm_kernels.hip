@@ -304,19 +304,19 @@ __global__ __launch_bounds__(MT) void k_ffn(float *x, const float *norm_w, StepS
 // or Q6_K: its Q6_K file), 2.6B Q8_0 (and LFM2-2.6B) and Q6_K, the tiny test presets' shapes; last,
 // the 1.7B shape as Q3_K_S / Q3_K_M / Q3_K_L (gate|up Q3_K, down Q3_K, Q4_K or Q5_K)
 #define MIO_FFN_SHAPES(X) \
-    X(1, 12, 6, 3, 12, 3)  \
-    X(1, 12, 6, 3, 14, 3)  \
-    X(1, 13, 6, 3, 13, 3)  \
-    X(1, 13, 6, 3, 14, 3)  \
-    X(1, 14, 6, 3, 14, 3)  \
-    X(1, 30, 6, 3, 30, 3)  \
-    X(1, 8, 2, 1, 8, 1)    \
-    X(1, 8, 2, 1, 14, 1)   \
-    X(1, 8, 0, 6, 8, 0)    \
-    X(1, 14, 0, 6, 14, 0)  \
-    X(1, 11, 6, 3, 11, 3)  \
-    X(1, 11, 6, 3, 12, 3)  \
-    X(1, 11, 6, 3, 13, 3)
+    X(1, GGML_Q4_K, 6, 3, GGML_Q4_K, 3)            \
+    X(1, GGML_Q4_K, 6, 3, GGML_Q6_K, 3)            \
+    X(1, GGML_Q5_K, 6, 3, GGML_Q5_K, 3)            \
+    X(1, GGML_Q5_K, 6, 3, GGML_Q6_K, 3)            \
+    X(1, GGML_Q6_K, 6, 3, GGML_Q6_K, 3)            \
+    X(1, GGML_BF16, 6, 3, GGML_BF16, 3)            \
+    X(1, GGML_Q8_0, 2, 1, GGML_Q8_0, 1)            \
+    X(1, GGML_Q8_0, 2, 1, GGML_Q6_K, 1)            \
+    X(1, GGML_Q8_0, 0, 6, GGML_Q8_0, 0)            \
+    X(1, GGML_Q6_K, 0, 6, GGML_Q6_K, 0)            \
+    X(1, GGML_Q3_K, 6, 3, GGML_Q3_K, 3)            \
+    X(1, GGML_Q3_K, 6, 3, GGML_Q4_K, 3)            \
+    X(1, GGML_Q3_K, 6, 3, GGML_Q5_K, 3)
 
 struct FfnShape {
     int np, t, su, npd, td, sud, GI, GD;
@@ -591,7 +591,7 @@ int lm_head_blocks(const LlmDims &d) { const LlmDims l = lm_dims(d); return matv
 size_t matvec_lds(int K) { return smem_bytes(K); }
 
 void launch_embed_token(const LlmDims &d, const QMat &tok_embd, const LlmBuffers &b, hipStream_t s) {
-    hipLaunchKernelGGL(tok_embd.type == 11 ? k_embed<true> : k_embed<false>, dim3(1), dim3(ST), 0, s, d, tok_embd, b);
+    hipLaunchKernelGGL(q3_table(tok_embd) ? k_embed<true> : k_embed<false>, dim3(1), dim3(ST), 0, s, d, tok_embd, b);
 }
 
 inline size_t mv_lds(int K) { return smem_bytes(K); }
@@ -719,7 +719,7 @@ void launch_step_kernel(StepKind which, const StepCtx &c, int il, const LlmBuffe
             launch_sample_chain(ChainArgs{b.logits, 0, b.st, b.cfg, b.smp, lm_head_blocks(d), nullptr, 0}, 1, s);
             break;
         case kSample:
-            hipLaunchKernelGGL((tok_embd.type == 11 ? k_sample<DG, true> : k_sample<DG, false>), dim3(1), dim3(ST), 0, s, d,
+            hipLaunchKernelGGL((q3_table(tok_embd) ? k_sample<DG, true> : k_sample<DG, false>), dim3(1), dim3(ST), 0, s, d,
                                tok_embd, lm_head_blocks(d), b);
             break;
         default: break;

@@ -132,19 +132,19 @@ __global__ __launch_bounds__(MT) void k_layer_att(const float *x, const float *n
 // 2.6B Q8_0 (and the LFM2-2.6B attention layers) and Q6_K; last, the 1.7B shape as Q3_K_S (every
 // matrix Q3_K), Q3_K_M (v Q4_K or Q5_K, o Q4_K) and Q3_K_L (v, o Q5_K)
 #define MIO_LAYER_ATT_SHAPES(X)   \
-    X(1, 12, 12, 2, 128, 2, 12, 1) \
-    X(1, 12, 14, 2, 128, 2, 12, 1) \
-    X(1, 13, 13, 2, 128, 2, 13, 1) \
-    X(1, 13, 14, 2, 128, 2, 13, 1) \
-    X(1, 14, 14, 2, 128, 2, 14, 1) \
-    X(1, 30, 30, 2, 128, 2, 30, 1) \
-    X(1, 8, 8, 1, 64, 3, 8, 1)     \
-    X(1, 8, 8, 2, 64, 4, 8, 1)     \
-    X(1, 14, 14, 2, 64, 4, 14, 1)  \
-    X(1, 11, 11, 2, 128, 2, 11, 1) \
-    X(1, 11, 12, 2, 128, 2, 12, 1) \
-    X(1, 11, 13, 2, 128, 2, 12, 1) \
-    X(1, 11, 13, 2, 128, 2, 13, 1)
+    X(1, GGML_Q4_K, GGML_Q4_K, 2, 128, 2, GGML_Q4_K, 1)              \
+    X(1, GGML_Q4_K, GGML_Q6_K, 2, 128, 2, GGML_Q4_K, 1)              \
+    X(1, GGML_Q5_K, GGML_Q5_K, 2, 128, 2, GGML_Q5_K, 1)              \
+    X(1, GGML_Q5_K, GGML_Q6_K, 2, 128, 2, GGML_Q5_K, 1)              \
+    X(1, GGML_Q6_K, GGML_Q6_K, 2, 128, 2, GGML_Q6_K, 1)              \
+    X(1, GGML_BF16, GGML_BF16, 2, 128, 2, GGML_BF16, 1)              \
+    X(1, GGML_Q8_0, GGML_Q8_0, 1, 64, 3, GGML_Q8_0, 1)               \
+    X(1, GGML_Q8_0, GGML_Q8_0, 2, 64, 4, GGML_Q8_0, 1)               \
+    X(1, GGML_Q6_K, GGML_Q6_K, 2, 64, 4, GGML_Q6_K, 1)               \
+    X(1, GGML_Q3_K, GGML_Q3_K, 2, 128, 2, GGML_Q3_K, 1)              \
+    X(1, GGML_Q3_K, GGML_Q4_K, 2, 128, 2, GGML_Q4_K, 1)              \
+    X(1, GGML_Q3_K, GGML_Q5_K, 2, 128, 2, GGML_Q4_K, 1)              \
+    X(1, GGML_Q3_K, GGML_Q5_K, 2, 128, 2, GGML_Q5_K, 1)
 
 struct Shape {
     int np, tq, tv, su, hd, g, to, suo;

@@ -156,6 +156,8 @@ __device__ __forceinline__ int q6s(uint32_t q) {
 __device__ __forceinline__ v16f sb_q6k(const QMat &W, int row, int s, const int8_t *aq, const float *da_lds) {
     const int lane = threadIdx.x & 63, h = lane >> 5;
     const int nsb = W.k >> 8;
+    static_assert(stride_is(GGML_Q6_K, 0, 1, 2) && stride_is(GGML_Q6_K, 1, 1, 4) && stride_is(GGML_Q6_K, 2, 1, 16) &&
+                  stride_is(GGML_Q6_K, 3, 2, 256), "Q6_K row strides (drow in f16 units)");
     const uint8_t *qlrow = W.p0 + (size_t)row * (W.k / 2);
     const uint8_t *qhrow = W.p1 + (size_t)row * (W.k / 4);
     const int8_t *screw = (const int8_t *)W.p2 + (size_t)row * (W.k / 16);
@@ -225,6 +227,8 @@ __device__ __forceinline__ constexpr int q3_sc_at(int j) { return 2 * (4 * (j & 
 __device__ __forceinline__ v16f sb_q3k(const QMat &W, int row, int s, const int8_t *aq, const float *da_lds) {
     const int lane = threadIdx.x & 63, h = lane >> 5;
     const int nsb = W.k >> 8;
+    static_assert(stride_is(GGML_Q3_K, 0, 1, 4) && stride_is(GGML_Q3_K, 1, 1, 8) && stride_is(GGML_Q3_K, 2, 1, 16) &&
+                  stride_is(GGML_Q3_K, 3, 2, 256), "Q3_K row strides (drow in f16 units)");
     const uint8_t *qrow = W.p0 + (size_t)row * (W.k / 4);
     const uint8_t *hrow = W.p1 + (size_t)row * (W.k / 8);
     const int8_t *screw = (const int8_t *)W.p2 + (size_t)row * (W.k / 16);
@@ -280,12 +284,14 @@ __device__ v16f slot_kq(const QMat &W, int row, int k, const int8_t *aq, const f
         const int s = p * 8 + k;
         v16f v = {};
         if (s < nsb) {
-            static_assert(T == 11 || T == 12 || T == 13 || T == 14, "slot_kq: K-quant types");
-            if constexpr (T == 11)
+            static_assert(is_kquant(T), "slot_kq: K-quant types");
+            static_assert(stride_is(GGML_Q4_K, 0, 1, 2) && stride_is(GGML_Q4_K, 1, 16, 256) && stride_is(GGML_Q5_K, 0, 1, 2) &&
+                          stride_is(GGML_Q5_K, 1, 1, 8) && stride_is(GGML_Q5_K, 2, 16, 256), "Q4_K / Q5_K row strides");
+            if constexpr (T == GGML_Q3_K)
                 v = sb_q3k(W, row, s, aq, da_lds);
-            else if constexpr (T == 12)
+            else if constexpr (T == GGML_Q4_K)
                 v = sb_q4k(W.p0 + (size_t)row * (W.k / 2), W.p1 + (size_t)row * nsb * 16, s, aq, da_lds);
-            else if constexpr (T == 13)
+            else if constexpr (T == GGML_Q5_K)
                 v = sb_q4k<true>(W.p0 + (size_t)row * (W.k / 2), W.p2 + (size_t)row * nsb * 16, s, aq, da_lds,
                                  W.p1 + (size_t)row * (W.k / 8));
             else
@@ -311,6 +317,7 @@ struct Q80Regs {
 __device__ __forceinline__ void q80_load(const QMat &W, int row, int k, const int8_t *aq, Q80Regs &q) {
     const int h = (threadIdx.x & 63) >> 5;
     const int nb = W.k >> 5;
+    static_assert(stride_is(GGML_Q8_0, 0, 1, 1) && stride_is(GGML_Q8_0, 1, 2, 32), "Q8_0 row strides (p1 in f16 units)");
     const int8_t *qrow = (const int8_t *)W.p0 + (size_t)row * W.k;
     const uint16_t *drow = (const uint16_t *)W.p1 + (size_t)row * nb;
 #pragma unroll
@@ -349,6 +356,7 @@ __device__ __forceinline__ v16f q80_sum(const Q80Regs &q, int nb, int k, const f
 __device__ v16f slot_q80(const QMat &W, int row, int k, const int8_t *aq, const float *da_lds) {
     const int lane = threadIdx.x & 63, h = lane >> 5;
     const int nb = W.k >> 5, NP = (nb + 63) / 64;
+    static_assert(stride_is(GGML_Q8_0, 0, 1, 1) && stride_is(GGML_Q8_0, 1, 2, 32), "Q8_0 row strides (p1 in f16 units)");
     const int8_t *qrow = (const int8_t *)W.p0 + (size_t)row * W.k;
     const uint16_t *drow = (const uint16_t *)W.p1 + (size_t)row * nb;
     Tree<3> inner;
@@ -398,8 +406,8 @@ __device__ v16f slot_q80(const QMat &W, int row, int k, const int8_t *aq, const 
 
 template <int T>
 __device__ __forceinline__ v16f slot_val(const QMat &W, int row, int k, const int8_t *aq, const float *da_lds) {
-    static_assert(T == 8 || T == 11 || T == 12 || T == 13 || T == 14, "slot_val: weight type");
-    if constexpr (T == 8) return slot_q80(W, row, k, aq, da_lds);
+    static_assert(T == GGML_Q8_0 || is_kquant(T), "slot_val: weight type");
+    if constexpr (T == GGML_Q8_0) return slot_q80(W, row, k, aq, da_lds);
     else return slot_kq<T>(W, row, k, aq, da_lds);
 }
 
@@ -407,7 +415,7 @@ __device__ __forceinline__ v16f slot_val(const QMat &W, int row, int k, const in
 // Q8_0: one per 32; the whole workgroup, then a barrier); returns this lane's token's codes.
 template <int T>
 __device__ __forceinline__ const int8_t *stage_act(const MmqArgs &a, int t0, int K, float *da_lds) {
-    const int ng = T == 8 ? K >> 5 : K >> 8;
+    const int ng = T == GGML_Q8_0 ? K >> 5 : K >> 8;
     const size_t ab = a.act_stride;
     for (int e = threadIdx.x; e < ng * TT; e += MMQ_NT) {
         const int g = e / TT, t = min(t0 + e % TT, a.nt - 1);
@@ -485,7 +493,7 @@ __global__ __launch_bounds__(MMQ_NT) void k_mmq(MmqSeg s0, MmqSeg s1, MmqSeg s2,
     auto run = [&]<int T>(const MmqSeg &sg, int ti) {
         const int row0 = ti * RT, row = min(row0 + (lane & 31), sg.w.rows - 1);
         v16f y = {}, u = {};
-        if (T == 8 && a.K <= 2048) {
+        if (T == GGML_Q8_0 && a.K <= 2048) {
             // one pass: the slot's weight / code / scale loads go out before the activation
             // scales' staging barrier (same values, same order of every float operation)
             const int k = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -493,7 +501,7 @@ __global__ __launch_bounds__(MMQ_NT) void k_mmq(MmqSeg s0, MmqSeg s1, MmqSeg s2,
             Q80Regs qw, qu;
             q80_load(sg.w, row, k, aq, qw);
             if constexpr (MODE == MMQ_SWIGLU) q80_load(a.w_up, row, k, aq, qu);
-            stage_act<8>(a, t0, a.K, da);
+            stage_act<GGML_Q8_0>(a, t0, a.K, da);
             slot_store(q80_sum(qw, sg.w.k >> 5, k, da), red);
             if constexpr (MODE == MMQ_SWIGLU) slot_store(q80_sum(qu, a.w_up.k >> 5, k, da), red + MMQ_NT * 16);
             __syncthreads();
@@ -710,6 +718,8 @@ struct Q6Pass {
 __device__ __forceinline__ void q6p_load(const QMat &W, int row, int s, Q6Pass &p) {
     const int lane = threadIdx.x & 63, g = lane >> 4;
     const int nsb = W.k >> 8;
+    static_assert(stride_is(GGML_Q6_K, 0, 1, 2) && stride_is(GGML_Q6_K, 1, 1, 4) && stride_is(GGML_Q6_K, 2, 1, 16) &&
+                  stride_is(GGML_Q6_K, 3, 2, 256), "Q6_K row strides (drow in f16 units)");
     const uint8_t *qlrow = W.p0 + (size_t)row * (W.k / 2);
     const uint8_t *qhrow = W.p1 + (size_t)row * (W.k / 4);
     const int8_t *screw = (const int8_t *)W.p2 + (size_t)row * (W.k / 16);
@@ -794,6 +804,8 @@ struct Q3Pass {
 __device__ __forceinline__ void q3p_load(const QMat &W, int row, int s, Q3Pass &p) {
     const int lane = threadIdx.x & 63, g = lane >> 4;
     const int nsb = W.k >> 8;
+    static_assert(stride_is(GGML_Q3_K, 0, 1, 4) && stride_is(GGML_Q3_K, 1, 1, 8) && stride_is(GGML_Q3_K, 2, 1, 16) &&
+                  stride_is(GGML_Q3_K, 3, 2, 256), "Q3_K row strides (drow in f16 units)");
     const uint8_t *qrow = W.p0 + (size_t)row * (W.k / 4);
     const uint8_t *hrow = W.p1 + (size_t)row * (W.k / 8);
     const int8_t *screw = (const int8_t *)W.p2 + (size_t)row * (W.k / 16);
@@ -847,16 +859,18 @@ __device__ __forceinline__ v4f q3p_val(const Q3Pass &p, const v4i (&x)[4], int s
 }
 
 template <int T>
-using KqPass = std::conditional_t<T == 11, Q3Pass,
-                                  std::conditional_t<T == 12, Q4Pass, std::conditional_t<T == 13, Q5Pass, Q6Pass>>>;
+using KqPass = std::conditional_t<T == GGML_Q3_K, Q3Pass,
+                                  std::conditional_t<T == GGML_Q4_K, Q4Pass, std::conditional_t<T == GGML_Q5_K, Q5Pass, Q6Pass>>>;
 template <int T>
 __device__ __forceinline__ void kqp_load(const QMat &W, int row, int s, KqPass<T> &p) {
-    static_assert(T == 11 || T == 12 || T == 13 || T == 14, "kqp_load: K-quant types");
-    if constexpr (T == 11)
+    static_assert(is_kquant(T), "kqp_load: K-quant types");
+    static_assert(stride_is(GGML_Q4_K, 0, 1, 2) && stride_is(GGML_Q4_K, 1, 16, 256) && stride_is(GGML_Q5_K, 0, 1, 2) &&
+                  stride_is(GGML_Q5_K, 1, 1, 8) && stride_is(GGML_Q5_K, 2, 16, 256), "Q4_K / Q5_K row strides");
+    if constexpr (T == GGML_Q3_K)
         q3p_load(W, row, s, p);
-    else if constexpr (T == 12)
+    else if constexpr (T == GGML_Q4_K)
         q4p_load(W.p0 + (size_t)row * (W.k / 2), W.p1 + (size_t)row * (W.k >> 8) * 16, s, p);
-    else if constexpr (T == 13)
+    else if constexpr (T == GGML_Q5_K)
         q5p_load(W.p0 + (size_t)row * (W.k / 2), W.p1 + (size_t)row * (W.k / 8),
                  W.p2 + (size_t)row * (W.k >> 8) * 16, s, p);
     else
@@ -864,9 +878,9 @@ __device__ __forceinline__ void kqp_load(const QMat &W, int row, int s, KqPass<T
 }
 template <int T>
 __device__ __forceinline__ v4f kqp_val(const KqPass<T> &p, const v4i (&x)[4], int s, const float *da) {
-    if constexpr (T == 11)
+    if constexpr (T == GGML_Q3_K)
         return q3p_val(p, x, s, da);
-    else if constexpr (T == 14)
+    else if constexpr (T == GGML_Q6_K)
         return q6p_val(p, x, s, da);
     else
         return q4p_val(p, x, s, da);
@@ -880,18 +894,19 @@ __device__ v4f slot16_kq(const QMat &W, int row, int k, const AP &aq, const floa
         const int s = p * 8 + k;
         v4f v = {};
         if (s < nsb) {
-            static_assert(T == 11 || T == 12 || T == 13 || T == 14, "slot16_kq: K-quant types");
-            if constexpr (T == 11) {
+            static_assert(is_kquant(T), "slot16_kq: K-quant types");
+            if constexpr (T == GGML_Q3_K) {
                 Q3Pass ps;
                 q3p_load(W, row, s, ps);
                 v4i x[4];
                 kq_act(aq, s, x);
                 v = q3p_val(ps, x, s, da_lds);
-            } else if constexpr (T == 12) {
+            } else if constexpr (T == GGML_Q4_K) {
                 v = sb16_q4k(W.p0 + (size_t)row * (W.k / 2), W.p1 + (size_t)row * nsb * 16, s, aq, da_lds);
-            } else if constexpr (T == 13) {
+                static_assert(stride_is(GGML_Q4_K, 0, 1, 2) && stride_is(GGML_Q4_K, 1, 16, 256), "Q4_K row strides");
+            } else if constexpr (T == GGML_Q5_K) {
                 Q5Pass ps;
-                kqp_load<13>(W, row, s, ps);
+                kqp_load<GGML_Q5_K>(W, row, s, ps);
                 v4i x[4];
                 kq_act(aq, s, x);
                 v = q4p_val(ps, x, s, da_lds);
@@ -909,6 +924,7 @@ __device__ v4f slot16_kq(const QMat &W, int row, int k, const AP &aq, const floa
 __device__ v4f slot16_q80(const QMat &W, int row, int k, const int8_t *aq, const float *da_lds) {
     const int lane = threadIdx.x & 63, g = lane >> 4;
     const int nb = W.k >> 5, NP = (nb + 63) / 64;
+    static_assert(stride_is(GGML_Q8_0, 0, 1, 1) && stride_is(GGML_Q8_0, 1, 2, 32), "Q8_0 row strides (p1 in f16 units)");
     const int8_t *qrow = (const int8_t *)W.p0 + (size_t)row * W.k;
     const uint16_t *drow = (const uint16_t *)W.p1 + (size_t)row * nb;
     v4f acc[8];
@@ -957,6 +973,7 @@ struct Q80Pass {
 __device__ __forceinline__ void q80p_load(const QMat &W, int row, int p, int k, Q80Pass &q) {
     const int g = (threadIdx.x & 63) >> 4, nb = W.k >> 5;
     const int b0 = min(p * 64 + 8 * k, nb - 8);
+    static_assert(stride_is(GGML_Q8_0, 0, 1, 1) && stride_is(GGML_Q8_0, 1, 2, 32), "Q8_0 row strides (p1 in f16 units)");
     const int8_t *qrow = (const int8_t *)W.p0 + (size_t)row * W.k;
 #pragma unroll
     for (int i = 0; i < 4; ++i) q.w[i] = *reinterpret_cast<const v4i *>(qrow + (size_t)(b0 + 2 * i) * 32 + 16 * g);
@@ -1027,8 +1044,8 @@ __device__ __forceinline__ void slot16_q80p(const QMat &W, const QMat &U, int ro
 
 template <int T, class AP>
 __device__ __forceinline__ v4f slot16_val(const QMat &W, int row, int k, const AP &aq, const float *da_lds) {
-    static_assert(T == 8 || T == 11 || T == 12 || T == 13 || T == 14, "slot16_val: weight type");
-    if constexpr (T == 8) {
+    static_assert(T == GGML_Q8_0 || is_kquant(T), "slot16_val: weight type");
+    if constexpr (T == GGML_Q8_0) {
         // the 8-B Q8_0 path (K % 256 != 0) never runs in an in-launch-quantization launch
         // (launch_mmq_q takes K % 256 == 0 only): no kernel with producers instantiates it
         static_assert(!std::is_same_v<AP, ActSc1>, "slot16_val: the 8-B Q8_0 path reads plain records only");
@@ -1053,7 +1070,7 @@ __device__ __forceinline__ auto act16_codes(const MmqArgs &a, int t0) {
 // token's codes (A operand: token lane & 15)
 template <int T, bool SC = false>
 __device__ __forceinline__ auto stage_act16(const MmqArgs &a, int t0, int K, float *da_lds) {
-    const int ng = T == 8 ? K >> 5 : K >> 8;
+    const int ng = T == GGML_Q8_0 ? K >> 5 : K >> 8;
     const size_t ab = a.act_stride;
     // token-major walk: consecutive threads read consecutive scales of one record
     for (int e = threadIdx.x; e < ng * TT16; e += MMQ_NT) {
@@ -1150,10 +1167,10 @@ __global__ __launch_bounds__(MMQ_NT) void k_mmq16(MmqSeg s0, MmqSeg s1, MmqSeg s
     if constexpr (QF) {
         if ((int)blockIdx.x < nq) {
             if (chunked)
-                chunk_quant_producer(q.src, a.K, T0 != 8, (a.K + 2047) / 2048, const_cast<char *>(a.act), q.cnt,
+                chunk_quant_producer(q.src, a.K, T0 != GGML_Q8_0, (a.K + 2047) / 2048, const_cast<char *>(a.act), q.cnt,
                                      q.other, lds);
             else
-                mmq_quant_producer<T0 == 8 ? 0 : 1, QNP, QM>(a, q, lds);
+                mmq_quant_producer<T0 == GGML_Q8_0 ? 0 : 1, QNP, QM>(a, q, lds);
             return;
         }
     }
@@ -1188,7 +1205,7 @@ __global__ __launch_bounds__(MMQ_NT) void k_mmq16(MmqSeg s0, MmqSeg s1, MmqSeg s
         // the slot index must be wave-uniform (divergent branches around the MFMAs would run
         // them with a partial EXEC)
         const int k = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-        if (T == 8 && (KP != 0 || a.K % 256 == 0)) {
+        if (T == GGML_Q8_0 && (KP != 0 || a.K % 256 == 0)) {
             const auto aq = act16_codes<QF>(a, t0);
             v4f y = {}, u = {};
             if (KP == 1 || (KP == 0 && a.K <= 2048)) {
@@ -1201,7 +1218,7 @@ __global__ __launch_bounds__(MMQ_NT) void k_mmq16(MmqSeg s0, MmqSeg s1, MmqSeg s
                 if constexpr (NV == 2) q80p_load(a.w_up, row, 0, k, qu);
                 wait_act();
                 act_load(aq, a.K, 0, k, x);
-                stage_act16<8, QF>(a, t0, a.K, da);
+                stage_act16<GGML_Q8_0, QF>(a, t0, a.K, da);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) swap_halves(x[i]);
                 v4f aw[8], au[8];
@@ -1215,13 +1232,13 @@ __global__ __launch_bounds__(MMQ_NT) void k_mmq16(MmqSeg s0, MmqSeg s1, MmqSeg s
                 }
             } else {
                 wait_act();
-                stage_act16<8, QF>(a, t0, a.K, da);
+                stage_act16<GGML_Q8_0, QF>(a, t0, a.K, da);
                 slot16_q80p<NV>(sg.w, a.w_up, row, k, aq, da, y, u);
             }
             slot16_store(y, red);
             if constexpr (NV == 2) slot16_store(u, red + MMQ_NT * 4);
         } else {
-            if constexpr (NV == 1 && (T == 11 || T == 12 || T == 13 || T == 14)) {
+            if constexpr (NV == 1 && is_kquant(T)) {
                 // up to three passes' weights (K <= 6144, the 1.7B down) are in flight before
                 // the activations are read (with in-launch quantization: while the producers
                 // quantize); then slot16_kq's arithmetic. The activation codes of
@@ -1262,7 +1279,7 @@ __global__ __launch_bounds__(MMQ_NT) void k_mmq16(MmqSeg s0, MmqSeg s1, MmqSeg s
                     goto reduce;
                 }
             }
-            if constexpr (T == 8 && QF) {
+            if constexpr (T == GGML_Q8_0 && QF) {
                 // a Q8_0 launch with producers is compiled for the pair path alone (KP != 0, taken
                 // above): the 8-B path of slot16_val has no sc1 record loads and is not built in
                 static_assert(KP != 0, "k_mmq16: Q8_0 with in-launch quantization needs the pair path (KP 1 / 2)");
@@ -1351,7 +1368,7 @@ __global__ __launch_bounds__(MMQ_NT) void k_mmq16_loop(MmqSeg s0, MmqArgs a, Mmq
     const auto aq = act16_codes<QF>(a, 0);
     v4i x[4];
     act_load(aq, a.K, 0, k, x);
-    stage_act16<8, QF>(a, 0, a.K, da);
+    stage_act16<GGML_Q8_0, QF>(a, 0, a.K, da);
 #pragma unroll
     for (int i = 0; i < 4; ++i) swap_halves(x[i]);
     // one tile: the loads of the tile D - 1 ahead go out first, into the set the previous
@@ -1437,7 +1454,7 @@ __global__ __launch_bounds__(MMQ_NT) void k_mmq16_loop_kq(MmqSeg s0, MmqArgs a, 
     // hold the 2.6B gate|up's <= 3 tiles per workgroup, two of them before the producers' wait)
     // Q3_K W | U pairs: 2, the ping-pong (a Q3Pass is as many registers as a Q6Pass, 17 per lane, and
     // its unpacking holds more temporaries: three pairs spill 64 dwords per lane)
-    constexpr int D = (T == 11 && NV == 2 && MIO_LOOP_D > 2) ? 2 : ((T == 14 && NV == 2 && MIO_LOOP_D > 3) ? 3 : MIO_LOOP_D);
+    constexpr int D = (T == GGML_Q3_K && NV == 2 && MIO_LOOP_D > 2) ? 2 : ((T == GGML_Q6_K && NV == 2 && MIO_LOOP_D > 3) ? 3 : MIO_LOOP_D);
     KqPass<T> w[D], u[D];
 #pragma unroll
     for (int d = 0; d < D - 1; ++d) {
@@ -1508,7 +1525,7 @@ __global__ __launch_bounds__(MMQ_NT) void k_mmq16_loop_kq(MmqSeg s0, MmqArgs a, 
 
 size_t mmq_lds(int type, int K, int mode) {
     return (size_t)(mode == MMQ_SWIGLU ? 2 : 1) * MMQ_NT * 16 * sizeof(float) +
-           (size_t)(type == 8 ? K / 32 : K / 256) * TT * sizeof(float);
+           (size_t)(type == GGML_Q8_0 ? K / 32 : K / 256) * TT * sizeof(float);
 }
 
 int mmq_tiles(int rows) { return (rows + RT - 1) / RT; }
@@ -1547,7 +1564,7 @@ static int n_cu() {
 // LDS of the 16 x 16 tiles (k_mmq16 and the walks)
 static size_t mmq16_lds(int type, int K, int mode) {
     return (size_t)(mode == MMQ_SWIGLU ? 2 : 1) * MMQ_NT * 4 * sizeof(float) +
-           (size_t)(type == 8 ? K / 32 : K / 256) * TT16 * sizeof(float);
+           (size_t)(type == GGML_Q8_0 ? K / 32 : K / 256) * TT16 * sizeof(float);
 }
 
 // dynamic LDS above 64 KB (Q8_0 activation scales of a long K) needs the per-kernel opt-in
@@ -1562,7 +1579,7 @@ static void launch_tiles(Kern kern, dim3 grid, size_t lds, hipStream_t s, const 
 // K-quants' bit of MIO_MMQ_LOOP_KQ.
 static bool walks(int type, int K, int tiles, int n_wg, int kq_bit) {
     const MmqSwitches &sw = switches();
-    return K % 256 == 0 && K <= 2048 && tiles > n_wg && n_wg > 0 && sw.loop && (type == 8 || (sw.loop_kq & kq_bit));
+    return K % 256 == 0 && K <= 2048 && tiles > n_wg && n_wg > 0 && sw.loop && (type == GGML_Q8_0 || (sw.loop_kq & kq_bit));
 }
 template <class Kern>
 static void launch_walk(Kern kern, int n_wg, size_t lds, hipStream_t s, const MmqSeg &sg, const MmqArgs &a,
@@ -1600,14 +1617,14 @@ void launch_mmq(const MmqSeg *seg, const int *types, int nseg, int mode, const M
             if constexpr (B < 0) {
                 if (walks(A, a.K, tiles, n_cu(), 1))
                     return dispatch_mode(mode, [&]<int M>() {
-                        if constexpr (A == 8)
+                        if constexpr (A == GGML_Q8_0)
                             launch_walk(k_mmq16_loop<M, 0, 0>, n_cu(), lds, s, sg[0], a, MmqQuant{}, tiles);
                         else
                             launch_walk(k_mmq16_loop_kq<A, M, 0, 0>, n_cu(), lds, s, sg[0], a, MmqQuant{}, tiles);
                     });
             }
             // Q8_0 over whole superblocks: the 16-B pair path, one pass (KP 1) or several (2)
-            const bool q8 = A == 8 && (B < 0 || B == 8) && (C < 0 || C == 8) && a.K % 256 == 0;
+            const bool q8 = A == GGML_Q8_0 && (B < 0 || B == GGML_Q8_0) && (C < 0 || C == GGML_Q8_0) && a.K % 256 == 0;
             const int kp = q8 ? (a.K <= 2048 ? 1 : 2) : 0;
             return dispatch_mode(mode, [&]<int M>() {
                 if (kp == 1) tile(k_mmq16<A, B, C, M, 1>);
@@ -1619,22 +1636,21 @@ void launch_mmq(const MmqSeg *seg, const int *types, int nseg, int mode, const M
     };
     auto one = [&]<int A>() {
         if (nseg == 1) return go.template operator()<A, -1, -1>();
-        // attention input: q, k share a type; v has it too, or is Q6_K beside Q4_K / Q5_K (the
-        // *_K_M mixes) or Q4_K beside Q6_K (attn_v_supported)
-        if (types[1] != A || !attn_v_supported(A, types[2])) no_kernel("q|k|v matmul: v", types[2], types[1]);
-        if (types[2] == A) return go.template operator()<A, A, A>();
-        if constexpr (A == 12 || A == 13) return go.template operator()<A, A, 14>();
-        if constexpr (A == 14) return go.template operator()<A, A, 12>();
-        if constexpr (A == 11) {  // Q3_K_M / Q3_K_L: v Q4_K or Q5_K
-            if (types[2] == 12) return go.template operator()<A, A, 12>();
-            return go.template operator()<A, A, 13>();
-        }
+        // attention input: q, k share a type; v's is one of kQkvTypes beside it
+        const bool hit = for_qkv_types([&]<int QK, int V>() {
+            if constexpr (QK == A) {
+                if (types[1] == A && types[2] == V) return go.template operator()<A, A, V>(), true;
+            }
+            return false;
+        });
+        if (!hit) no_kernel("q|k|v matmul: v", types[2], types[1]);
     };
-    if (types[0] == 12) one.template operator()<12>();
-    else if (types[0] == 13) one.template operator()<13>();
-    else if (types[0] == 14) one.template operator()<14>();
-    else if (types[0] == 8) one.template operator()<8>();
-    else if (types[0] == 11) one.template operator()<11>();  // last: the earlier types' kernels keep their places
+    // (Q8_0 between Q6_K and Q3_K, as first used)
+    if (types[0] == GGML_Q4_K) one.template operator()<GGML_Q4_K>();
+    else if (types[0] == GGML_Q5_K) one.template operator()<GGML_Q5_K>();
+    else if (types[0] == GGML_Q6_K) one.template operator()<GGML_Q6_K>();
+    else if (types[0] == GGML_Q8_0) one.template operator()<GGML_Q8_0>();
+    else if (types[0] == GGML_Q3_K) one.template operator()<GGML_Q3_K>();
     else no_kernel("matmul", types[0], a.K);
 }
 
@@ -1661,20 +1677,20 @@ bool launch_mmq_q(const MmqSeg *seg, const int *types, int nseg, int mode, const
         return true;
     };
     const int np = pick_np(a.K), T = types[0];
-    const bool q8_one_pass = T == 8 && a.K % 256 == 0 && a.K <= 2048;
+    const bool q8_one_pass = T == GGML_Q8_0 && a.K % 256 == 0 && a.K <= 2048;
     if (mode == MMQ_STORE && nseg == 3 && q.mode == 0 && np == 1 && types[1] == T) {
-        // q|k|v (RMSNorm input, one pass): every K-quant model, v of q's type or the *_K_M mixes' Q6_K
-        if (T == 12 && types[2] == 12) return go(k_mmq16<12, 12, 12, MMQ_STORE, 0, 1, 0>);
-        if (T == 12 && types[2] == 14) return go(k_mmq16<12, 12, 14, MMQ_STORE, 0, 1, 0>);
-        if (T == 13 && types[2] == 13) return go(k_mmq16<13, 13, 13, MMQ_STORE, 0, 1, 0>);
-        if (T == 13 && types[2] == 14) return go(k_mmq16<13, 13, 14, MMQ_STORE, 0, 1, 0>);
-        if (T == 14 && types[2] == 14) return go(k_mmq16<14, 14, 14, MMQ_STORE, 0, 1, 0>);  // all-Q6_K files
-        if (T == 11 && types[2] == 11) return go(k_mmq16<11, 11, 11, MMQ_STORE, 0, 1, 0>);  // Q3_K_S
-        if (T == 11 && types[2] == 12) return go(k_mmq16<11, 11, 12, MMQ_STORE, 0, 1, 0>);  // Q3_K_M
-        if (T == 11 && types[2] == 13) return go(k_mmq16<11, 11, 13, MMQ_STORE, 0, 1, 0>);  // Q3_K_M / _L
+        // q|k|v (RMSNorm input, one pass): the K-quant pairs of kQkvTypes, but for Q4_K v beside
+        // Q6_K q|k, which no file type mixes so and which has no fused shape
+        const bool hit = for_qkv_types([&]<int QK, int V>() {
+            if constexpr (is_kquant(QK) && !(QK == GGML_Q6_K && V == GGML_Q4_K)) {
+                if (T == QK && types[2] == V) return go(k_mmq16<QK, QK, V, MMQ_STORE, 0, 1, 0>);
+            }
+            return false;
+        });
+        if (hit) return true;
         // Q8_0 models whose n_embd is a multiple of 256 up to 2048 (the others keep q|k|v on the
         // dot4 engine, quantizing in that launch)
-        if (q8_one_pass && types[2] == 8) return go(k_mmq16<8, 8, 8, MMQ_STORE, 1, 1, 0>);
+        if (q8_one_pass && types[2] == GGML_Q8_0) return go(k_mmq16<GGML_Q8_0, GGML_Q8_0, GGML_Q8_0, MMQ_STORE, 1, 1, 0>);
     }
     if (mode == MMQ_SWIGLU && nseg == 1 && q.mode == 0 && np == 1) {
         // gate|up (RMSNorm input, one pass): every K-quant model, and Q8_0 where both of the
@@ -1690,26 +1706,21 @@ bool launch_mmq_q(const MmqSeg *seg, const int *types, int nseg, int mode, const
         };
         const bool w = walks(T, a.K, tiles, nl, 2);
         auto kq_up = [&]<int TK>() {
-            return w ? walk(k_mmq16_loop_kq<TK, MMQ_SWIGLU, 1, 0>) : go(k_mmq16<TK, -1, -1, MMQ_SWIGLU, 0, 1, 0>);
+            if (w) walk(k_mmq16_loop_kq<TK, MMQ_SWIGLU, 1, 0>);
+            else go(k_mmq16<TK, -1, -1, MMQ_SWIGLU, 0, 1, 0>);
         };
-        if (T == 12) return kq_up.template operator()<12>();
-        if (T == 13) return kq_up.template operator()<13>();
-        if (T == 14) return kq_up.template operator()<14>();
-        if (T == 11) return kq_up.template operator()<11>();
-        if (q8_one_pass) return w ? walk(k_mmq16_loop<MMQ_SWIGLU, 1, 0>) : go(k_mmq16<8, -1, -1, MMQ_SWIGLU, 1, 1, 0>);
+        if (dispatch_kquant(T, kq_up)) return true;
+        if (q8_one_pass) return w ? walk(k_mmq16_loop<MMQ_SWIGLU, 1, 0>) : go(k_mmq16<GGML_Q8_0, -1, -1, MMQ_SWIGLU, 1, 1, 0>);
     }
     if (mode == MMQ_RESID && nseg == 1 && q.mode == 1 && np == 3) {
         // down (plain h rows of 3 passes): every K-quant model
-        if (T == 12) return go(k_mmq16<12, -1, -1, MMQ_RESID, 0, 3, 1>);
-        if (T == 13) return go(k_mmq16<13, -1, -1, MMQ_RESID, 0, 3, 1>);
-        if (T == 14) return go(k_mmq16<14, -1, -1, MMQ_RESID, 0, 3, 1>);
-        if (T == 11) return go(k_mmq16<11, -1, -1, MMQ_RESID, 0, 3, 1>);  // Q3_K_S
+        if (dispatch_kquant(T, [&]<int TK>() { go(k_mmq16<TK, -1, -1, MMQ_RESID, 0, 3, 1>); })) return true;
     }
     // Q8_0 down (multi-pass pair path): at 9 to 16 streams, or with MIO_MMQ=1 (up to 8 it stays on
     // the dot4 engine: 2.010 vs 1.984 ms and 171.2 vs 179.4x with it here)
-    if (mode == MMQ_RESID && nseg == 1 && q.mode == 1 && T == 8 && a.K % 256 == 0 && a.K > 2048) {
-        if (np == 3) return go(k_mmq16<8, -1, -1, MMQ_RESID, 2, 3, 1>);
-        if (np == 6) return go(k_mmq16<8, -1, -1, MMQ_RESID, 2, 6, 1>);
+    if (mode == MMQ_RESID && nseg == 1 && q.mode == 1 && T == GGML_Q8_0 && a.K % 256 == 0 && a.K > 2048) {
+        if (np == 3) return go(k_mmq16<GGML_Q8_0, -1, -1, MMQ_RESID, 2, 3, 1>);
+        if (np == 6) return go(k_mmq16<GGML_Q8_0, -1, -1, MMQ_RESID, 2, 6, 1>);
     }
     return false;
 }

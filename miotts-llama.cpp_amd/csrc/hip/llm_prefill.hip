@@ -42,7 +42,7 @@ namespace {
 // K of the act record layout for a weight type: BF16 weights take the activation as K bf16
 // values (ggml's vec_dot_bf16 operand, 2 bytes each), stored in the qs area of a record laid out
 // for 2K (the d / bs areas then go unused)
-__host__ __device__ constexpr int rec_k(int K, int type) { return type == 30 ? 2 * K : K; }
+__host__ __device__ constexpr int rec_k(int K, int type) { return bf16_records(type) ? 2 * K : K; }
 __host__ __device__ inline size_t pf_lds_bytes(int K, int nt, int rpw) {
     return act_base(K) + act_bytes(K) * nt + (size_t)MW * nt * rpw * 4;
 }
@@ -73,10 +73,10 @@ __device__ inline float *resid_lds(char *base, int K, int nt, int rpw) {
 // batched kernels spill
 template <int T, int NP, int NM>
 struct CfgB {
-    static constexpr int UN = T == 8 ? MIO_BT_UNITS_Q8 : (T == 30 ? 1 : MIO_BT_UNITS);
+    static constexpr int UN = T == GGML_Q8_0 ? MIO_BT_UNITS_Q8 : (T == GGML_BF16 ? 1 : MIO_BT_UNITS);
     static constexpr int RU = NP * NM >= UN ? 1 : UN / (NP * NM);
     static constexpr int U = RU * NP * NM;
-    static constexpr int NG = (NP >= 6 || T == 30) ? 1 : 2;
+    static constexpr int NG = (NP >= 6 || T == GGML_BF16) ? 1 : 2;
 };
 
 template <int T, int NP, int NM>
@@ -186,7 +186,7 @@ __device__ __forceinline__ void stream_rows_bx(const QMat W0, const QMat W1, int
     constexpr int RU = CfgB<T, NP, NM>::RU, U = CfgB<T, NP, NM>::U;
     constexpr int TT = XRedCfg<NP>::TT, TB = XRedCfg<NP>::TB;
     constexpr int N = TB * RU * NM;             // totals per group: index ((t * RU + ri) * NM + m)
-    constexpr int LB = (T == 8 || T == 30) ? 0 : 3;  // first tree level (K-quants: lanes 8k+7)
+    constexpr int LB = lane_blocks(T) ? 0 : 3;  // first tree level (K-quants: lanes 8k+7)
     constexpr int NF = N >> (6 - LB) > NM ? N >> (6 - LB) : NM;  // totals per lane at the end
     constexpr int SL = __builtin_ctz(N / NF);   // scatter levels
     const int K = W0.k, KR = rec_k(K, T);
@@ -269,7 +269,7 @@ __device__ __forceinline__ void stream_rows_bu(const QMat W0, const QMat W1, int
     // / reduction chains interleave (the weight decode is shared); rows of the group past hi
     // (a wave owning fewer rows than RU) are not dotted
     // (BF16: one token at a time, its activation slice alone is 16 registers)
-    constexpr int TT = T == 30 ? 1 : (NP == 1 ? 4 : (NP == 3 ? 2 : 1));
+    constexpr int TT = T == GGML_BF16 ? 1 : (NP == 1 ? 4 : (NP == 3 ? 2 : 1));
     auto consume = [&](const Frag (&F)[U], int r) {
         const int nr = min(RU, hi - r);
         for (int t0 = 0; t0 < nt; t0 += TT) {
@@ -338,7 +338,7 @@ __device__ __forceinline__ void stream_rows_b(const QMat W0, const QMat W1, int 
                                               int nt, Epi &&epi, int split = INT_MAX) {
     // BF16: the per-total trees (its 64-B units and 16-register activation slices leave no
     // room for the transposed reduction's token groups)
-    if constexpr (T != 30)
+    if constexpr (T != GGML_BF16)
         stream_rows_bx<T, NP, NM>(W0, W1, lo, hi, A, B, smem, nt, epi, split);
     else
         stream_rows_bu<T, NP, NM>(W0, W1, lo, hi, A, B, smem, nt, epi, split);
@@ -533,7 +533,7 @@ __global__ __launch_bounds__(MT) void k_pf_attn_in(LlmDims d, const float *norm_
     if constexpr (FQ == 2) xpre_issue(pb.x, norm_w, K, nt, xp);
     auto prologue = [&]() {
         if constexpr (FQ == 2)
-            xpre_quant(xp, K, d.eps, TQ != 8, smem, nt);
+            xpre_quant(xp, K, d.eps, TQ != GGML_Q8_0, smem, nt);
         else
             prologue_copy(pb.act, KR, smem, nt);
     };
@@ -752,7 +752,7 @@ __global__ __launch_bounds__(MT, 1) void k_pf_ffn_in(LlmDims d, const float *nor
     Frag ga[CfgB<T, NP, 2>::U], gb[CfgB<T, NP, 2>::U];
     load_first_b<T, NP, 2>(gate, up, lo, hi, ga, gb);
     if constexpr (FQ == 2)
-        xpre_quant(xp, K, d.eps, T != 8, smem, nt);
+        xpre_quant(xp, K, d.eps, T != GGML_Q8_0, smem, nt);
     else
         act_store<NP>(ap, pb.act, KR, smem, nt);
     stream_rows_b<T, NP, 2>(gate, up, lo, hi, ga, gb, smem, nt, [&](int row, int t, float g, float u) {
@@ -796,7 +796,7 @@ __global__ __launch_bounds__(MT) void k_pf_ffn_down_q(LlmDims d, QMat down, Pref
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int K = down.k, E = d.n_embd, KR = rec_k(K, T), npr = nt * nch;
     if ((int)blockIdx.x < npr) {
-        chunk_quant_producer(q.src, K, T != 8, nch, pb.act, q.cnt, q.other, smem);
+        chunk_quant_producer(q.src, K, T != GGML_Q8_0, nch, pb.act, q.cnt, q.other, smem);
         return;
     }
     int lo, hi;
@@ -1159,8 +1159,8 @@ bool q8_one_pass(int K) { return K % 256 == 0 && K <= 2048; }
 // are whole quantization blocks (0: Q8_0 blocks, 1: Q8_K superblocks), else (-1) a k_bt_quant
 // launch; BF16 always the launch.
 int merger_records(const LayerSwitches &sw, int o_type, int gh) {
-    if (!sw.att_q || o_type == 30) return -1;
-    if (o_type == 8) return gh % 32 == 0 ? 0 : -1;
+    if (!sw.att_q || o_type == GGML_BF16) return -1;
+    if (o_type == GGML_Q8_0) return gh % 32 == 0 ? 0 : -1;
     return gh % 256 == 0 ? 1 : -1;
 }
 
@@ -1191,8 +1191,8 @@ struct LayerRun {
     // count; the matrix-core matmuls are int8.
     bool use_mmq(int kind, int type) const {
         const bool q8_o_gateup_one_pass = q8_one_pass(d.n_embd) && q8_one_pass(d.n_head * d.hd);
-        const int mask = type == 8 ? (q8_o_gateup_one_pass ? 7 : 1) : 15;
-        return type != 30 && (mmq_all() || (nt <= 8 && sw.mmq < 0 && ((mask >> kind) & 1)));
+        const int mask = type == GGML_Q8_0 ? (q8_o_gateup_one_pass ? 7 : 1) : 15;
+        return type != GGML_BF16 && (mmq_all() || (nt <= 8 && sw.mmq < 0 && ((mask >> kind) & 1)));
     }
     // xpre (bit 0 q|k|v, 1 gate|up). Default: Q8_0 only; q|k|v where the matrix cores cannot
     // quantize it in the launch themselves (r05: C4 169.0-169.3x with q|k|v on k_mmq16 + producers
@@ -1201,8 +1201,8 @@ struct LayerRun {
     bool xpre(int bit, int type) const {
         const bool qkv_producers = producers() && q8_one_pass(d.n_embd);
         const bool on = sw.fq >= 0 ? ((sw.fq >> bit) & 1) != 0
-                                   : (type == 8 && (bit == 0 ? !qkv_producers : !q8_one_pass(d.n_embd)));
-        return !mmq_all() && nt <= MW && pick_np(d.n_embd) == 1 && on && type != 30;
+                                   : (type == GGML_Q8_0 && (bit == 0 ? !qkv_producers : !q8_one_pass(d.n_embd)));
+        return !mmq_all() && nt <= MW && pick_np(d.n_embd) == 1 && on && type != GGML_BF16;
     }
 
     Plan plan(const Site &st) const {
@@ -1225,11 +1225,11 @@ struct LayerRun {
             // bit-exact with the decode step's matvec at any token count; the loader's bf16_mt keeps
             // a BF16 matrix beside an int8 one off this engine)
             case kSiteConvIn:
-            case kSiteConvOut: return {W.type == 30 ? kDot4 : kMmq, st.in != kInRecords};
+            case kSiteConvOut: return {W.type == GGML_BF16 ? kDot4 : kMmq, st.in != kInRecords};
             // k_bt_lm_head (kDot4) is launch_batch_step's own
             case kSiteLmHead: break;
         }
-        return {sw.lm_mmq && W.type != 30 ? kMmq : kDot4, true};
+        return {sw.lm_mmq && W.type != GGML_BF16 ? kMmq : kDot4, true};
     }
 
     void quant(const Site &st) const {
@@ -1273,7 +1273,7 @@ struct LayerRun {
                 const size_t lds = pf_lds_bytes(KR, n, 0);
                 dispatch_nt<true>(st.K, W.type, [&]<int NP, int TQ>() {
                     dispatch_v<TQ>(V.wv.type, [&]<int TV>() {
-                        if constexpr (NP == 1 && TQ != 30) {
+                        if constexpr (NP == 1 && TQ != GGML_BF16) {
                             if (xp)
                                 return launch_lds(k_pf_attn_in<NP, TQ, TV, 2>, GW, lds, s, d, st.norm_w, V.wq, V.wk, V.wv,
                                                   g_qk, q, n, st.ld);
@@ -1288,7 +1288,7 @@ struct LayerRun {
             over_tokens(KR, 0, st.qs, [&](int n, const PrefillBuffers &q) {
                 const size_t lds = pf_lds_bytes(KR, n, 0);
                 dispatch_nt<true>(st.K, W.type, [&]<int NP, int T>() {
-                    if constexpr (NP == 1 && T != 30) {
+                    if constexpr (NP == 1 && T != GGML_BF16) {
                         if (xp) return launch_lds(k_pf_ffn_in<NP, T, 2>, grid, lds, s, d, st.norm_w, W, st.up, q, n);
                     }
                     launch_lds(k_pf_ffn_in<NP, T>, grid, lds, s, d, st.norm_w, W, st.up, q, n);
@@ -1400,7 +1400,7 @@ void launch_prefill_chunk(const LlmDims &d, const LayerW *layers, int n_layer, _
                           _Float16 *vcache, const QMat &tok_embd, const PrefillBuffers &pb, int p0, int nt,
                           int n_chunks, hipStream_t s) {
     if (nt <= 0) return;
-    hipLaunchKernelGGL(tok_embd.type == 11 ? k_pf_embed<true> : k_pf_embed<false>, dim3(nt), dim3(ST), 0, s, d, tok_embd,
+    hipLaunchKernelGGL(q3_table(tok_embd) ? k_pf_embed<true> : k_pf_embed<false>, dim3(nt), dim3(ST), 0, s, d, tok_embd,
                        pb, p0);
     launch_layers(d, layers, n_layer, kcache, vcache, pb, nt, n_chunks, false, s);
 }
@@ -1447,13 +1447,13 @@ void launch_batch_step(const LlmDims &d, const LayerW *layers, int n_layer, _Flo
         });
     }
     if (chain) launch_sample_chain(ChainArgs{bb.logits, (size_t)lm.rows, bb.st, bb.cfg, bb.smp, nblk, nullptr, 0}, B, s);
-    hipLaunchKernelGGL(tok_embd.type == 11 ? k_bt_sample<true> : k_bt_sample<false>, dim3(B), dim3(ST), 0, s, d, tok_embd,
+    hipLaunchKernelGGL(q3_table(tok_embd) ? k_bt_sample<true> : k_bt_sample<false>, dim3(B), dim3(ST), 0, s, d, tok_embd,
                        nblk, pb, bb);
 }
 
 void launch_batch_embed(const LlmDims &d, const QMat &tok_embd, const PrefillBuffers &pb, const BatchBuffers &bb,
                         int B, hipStream_t s) {
-    hipLaunchKernelGGL(tok_embd.type == 11 ? k_bt_embed<true> : k_bt_embed<false>, dim3(B), dim3(ST), 0, s, d, tok_embd, pb,
+    hipLaunchKernelGGL(q3_table(tok_embd) ? k_bt_embed<true> : k_bt_embed<false>, dim3(B), dim3(ST), 0, s, d, tok_embd, pb,
                        bb);
 }
 

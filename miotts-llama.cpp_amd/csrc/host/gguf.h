@@ -11,25 +11,9 @@
 #include <string>
 #include <vector>
 
-namespace mio {
+#include "weight_types.h"  // GgmlType: the ggml tensor type ids
 
-// ggml tensor type ids (public ggml enum values).
-enum GgmlType : uint32_t {
-    GGML_F32 = 0,
-    GGML_F16 = 1,
-    GGML_Q4_0 = 2,
-    GGML_Q5_0 = 6,
-    GGML_Q8_0 = 8,
-    GGML_Q3_K = 11,
-    GGML_Q4_K = 12,
-    GGML_Q5_K = 13,
-    GGML_Q6_K = 14,
-    GGML_Q8_K = 15,
-    GGML_I8 = 24,
-    GGML_I16 = 25,
-    GGML_I32 = 26,
-    GGML_BF16 = 30,
-};
+namespace mio {
 
 // bytes per block / elements per block for the supported types
 size_t ggml_type_block_bytes(uint32_t t);

@@ -256,11 +256,8 @@ struct DiagStateGuard {
 // parts.
 uint64_t kind_bytes(const mio_hip_llm *m, mio::StepKind kind, const mio::LayerW &L, uint64_t pos) {
     const mio::LlmDims &D = m->dims;
-    // (Q3_K: the 114 B per superblock its split layout streams, as mio_hip_llm_weight_bytes counts them)
-    auto qbytes = [](const mio::QMat &q) {
-        if (q.type == mio::GGML_Q3_K) return (uint64_t)(q.k / 256) * mio::kQ3KSplitBytes * (uint64_t)q.rows;
-        return (uint64_t)mio::ggml_row_bytes(q.type, q.k) * (uint64_t)q.rows;
-    };
+    // the bytes the split layout streams (weight_types.h), as mio_hip_llm_weight_bytes counts them
+    auto qbytes = [](const mio::QMat &q) { return (uint64_t)mio::row_bytes(q.type, q.k) * (uint64_t)q.rows; };
     const uint64_t nch = pos / mio::kAttChunk + 1, qkv = (uint64_t)(D.n_head + 2 * D.n_kv) * D.hd;
     // chunk partial records {O, m, l}: written by the chunk workgroups, read back by the
     // merging one (attn_merge_last), which writes the n_head * hd outputs

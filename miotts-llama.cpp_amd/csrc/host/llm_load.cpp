@@ -76,10 +76,11 @@ bool upload_qmat(mio_hip_llm *m, const mio::GgufTensor *t, mio::QMat &q) {
         return false;
     }
     const bool repack = mio::repacks_to_q8_0(t->type);
-    if (t->type != mio::GGML_Q8_0 && t->type != mio::GGML_Q3_K && t->type != mio::GGML_Q4_K &&
-        t->type != mio::GGML_Q5_K && t->type != mio::GGML_Q6_K && t->type != mio::GGML_BF16 && !repack) {
-        mio::set_error("llm: tensor %s has type %s; supported: bf16, q8_0, q3_K, q4_K, q5_K, q6_K, q5_0 / q4_0 (run as q8_0)",
-                       t->name.c_str(), mio::ggml_type_name(t->type));
+    if (!mio::is_weight_type((int)t->type) && !repack) {
+        std::string names;  // every weight type of the table, by its ggml name
+        for (int wt : mio::kWeightTypes) names += std::string(mio::ggml_type_name(wt)) + ", ";
+        mio::set_error("llm: tensor %s has type %s; supported: %sq5_0 / q4_0 (run as q8_0)", t->name.c_str(),
+                       mio::ggml_type_name(t->type), names.c_str());
         return false;
     }
     if (t->type == mio::GGML_BF16 && t->ne[0] % 32) {
@@ -127,9 +128,9 @@ bool upload_qmat(mio_hip_llm *m, const mio::GgufTensor *t, mio::QMat &q) {
     q.p1 = dp + L.off[1];
     q.p2 = dp + L.off[2];
     q.p3 = dp + L.off[3];
-    // Q3_K streams its split layout's 114 B per superblock, not the GGUF's 110 (quant.h)
-    m->weight_bytes += type == mio::GGML_Q3_K ? (uint64_t)t->ne[1] * (uint64_t)(t->ne[0] / 256) * mio::kQ3KSplitBytes
-                                              : t->nbytes;
+    // the bytes the split layout streams (Q3_K: 114 B per superblock, not the GGUF's 110). Q4_0 /
+    // Q5_0 files keep counting their GGUF bytes although they stream as Q8_0
+    m->weight_bytes += repack ? t->nbytes : (uint64_t)t->ne[1] * mio::row_bytes((int)type, t->ne[0]);
     return true;
 }
 

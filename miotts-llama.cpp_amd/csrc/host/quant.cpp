@@ -432,24 +432,14 @@ SplitLayout split_layout(uint32_t type, int64_t R, int64_t K) {
         L.off[i] = o;
         o = a16(o + n);
     };
-    switch (type) {
-        case GGML_Q8_0: take(0, (size_t)R * K), take(1, (size_t)R * (K / 32) * 2); break;
-        case GGML_Q4_K: take(0, (size_t)R * K / 2), take(1, (size_t)R * (K / 256) * 16); break;
-        case GGML_Q5_K:
-            take(0, (size_t)R * K / 2), take(1, (size_t)R * K / 8), take(2, (size_t)R * (K / 256) * 16);
-            break;
-        case GGML_Q6_K:
-            take(0, (size_t)R * K / 2), take(1, (size_t)R * K / 4), take(2, (size_t)R * K / 16),
-                take(3, (size_t)R * (K / 256) * 2);
-            break;
-        case GGML_Q3_K:
-            take(0, (size_t)R * K / 4), take(1, (size_t)R * K / 8), take(2, (size_t)R * K / 16),
-                take(3, (size_t)R * (K / 256) * 2);
-            break;
-        case GGML_F32: take(0, (size_t)R * K * 4); break;
-        case GGML_F16:
-        case GGML_BF16: take(0, (size_t)R * K * 2); break;
-        default: return L;
+    if (is_weight_type((int)type)) {  // the planes of weight_types.h, each rounded up to 256 B
+        for (int p = 0; p < num_planes((int)type); ++p) take(p, (size_t)R * plane_row_bytes((int)type, K, p));
+    } else if (type == GGML_F32) {
+        take(0, (size_t)R * K * 4);
+    } else if (type == GGML_F16) {
+        take(0, (size_t)R * K * 2);
+    } else {
+        return L;
     }
     L.bytes = o;
     return L;
@@ -486,27 +476,28 @@ bool to_split(uint32_t type, const void *src, int64_t R, int64_t K, uint8_t *dst
 #pragma omp parallel for schedule(static)
     for (int64_t r = 0; r < R; ++r) {
         const uint8_t *row = (const uint8_t *)src + (size_t)r * row_bytes;
+        auto plane = [&](int p) { return dst + L.off[p] + (size_t)r * plane_row_bytes((int)type, K, p); };
         if (type == GGML_Q8_0) {
             const BlockQ8_0 *b = (const BlockQ8_0 *)row;
-            int8_t *qs = (int8_t *)(dst + L.off[0]) + (size_t)r * K;
-            uint16_t *d = (uint16_t *)(dst + L.off[1]) + (size_t)r * (K / 32);
+            int8_t *qs = (int8_t *)plane(0);
+            uint16_t *d = (uint16_t *)plane(1);
             for (int64_t i = 0; i < K / 32; ++i) {
                 std::memcpy(qs + 32 * i, b[i].qs, 32);
                 d[i] = b[i].d;
             }
         } else if (type == GGML_Q4_K) {
             const BlockQ4_K *b = (const BlockQ4_K *)row;
-            uint8_t *qs = dst + L.off[0] + (size_t)r * K / 2;
-            uint8_t *hd = dst + L.off[1] + (size_t)r * (K / 256) * 16;
+            uint8_t *qs = plane(0);
+            uint8_t *hd = plane(1);
             for (int64_t i = 0; i < K / 256; ++i) {
                 std::memcpy(qs + 128 * i, b[i].qs, 128);
                 split_header_k4(b[i].d, b[i].dmin, b[i].scales, hd + 16 * i);
             }
         } else if (type == GGML_Q5_K) {
             const BlockQ5_K *b = (const BlockQ5_K *)row;
-            uint8_t *qs = dst + L.off[0] + (size_t)r * K / 2;
-            uint8_t *qh = dst + L.off[1] + (size_t)r * K / 8;
-            uint8_t *hd = dst + L.off[2] + (size_t)r * (K / 256) * 16;
+            uint8_t *qs = plane(0);
+            uint8_t *qh = plane(1);
+            uint8_t *hd = plane(2);
             for (int64_t i = 0; i < K / 256; ++i) {
                 std::memcpy(qs + 128 * i, b[i].qs, 128);
                 std::memcpy(qh + 32 * i, b[i].qh, 32);
@@ -516,10 +507,10 @@ bool to_split(uint32_t type, const void *src, int64_t R, int64_t K, uint8_t *dst
             // quant.h: piece pc at position P = 4 (pc & 1) + (pc >> 1); run t (0 lo, 1 hi) = elements
             // 64 (pc >> 1) + 16 (pc & 1) + 32 t + i, i < 16
             const BlockQ3_K *b = (const BlockQ3_K *)row;
-            uint8_t *q = dst + L.off[0] + (size_t)r * K / 4;
-            uint8_t *h = dst + L.off[1] + (size_t)r * K / 8;
-            int8_t *sc = (int8_t *)(dst + L.off[2]) + (size_t)r * K / 16;
-            uint16_t *d = (uint16_t *)(dst + L.off[3]) + (size_t)r * (K / 256);
+            uint8_t *q = plane(0);
+            uint8_t *h = plane(1);
+            int8_t *sc = (int8_t *)plane(2);
+            uint16_t *d = (uint16_t *)plane(3);
             for (int64_t i = 0; i < K / 256; ++i) {
                 std::memset(q + 64 * i, 0, 64);
                 std::memset(h + 32 * i, 0, 32);
@@ -541,10 +532,10 @@ bool to_split(uint32_t type, const void *src, int64_t R, int64_t K, uint8_t *dst
             }
         } else {  // Q6_K
             const BlockQ6_K *b = (const BlockQ6_K *)row;
-            uint8_t *ql = dst + L.off[0] + (size_t)r * K / 2;
-            uint8_t *qh = dst + L.off[1] + (size_t)r * K / 4;
-            int8_t *sc = (int8_t *)(dst + L.off[2]) + (size_t)r * K / 16;
-            uint16_t *d = (uint16_t *)(dst + L.off[3]) + (size_t)r * (K / 256);
+            uint8_t *ql = plane(0);
+            uint8_t *qh = plane(1);
+            int8_t *sc = (int8_t *)plane(2);
+            uint16_t *d = (uint16_t *)plane(3);
             for (int64_t i = 0; i < K / 256; ++i) {
                 std::memcpy(ql + 128 * i, b[i].ql, 128);
                 std::memcpy(qh + 64 * i, b[i].qh, 64);

@@ -1,13 +1,9 @@
 // ggml block quant formats (public ggml spec) on the host:
 // fp16 conversion, row quantizers (used to make synthetic Q8_0 / Q4_K_M / Q5_K_M models),
 // row dequantizers (embedding get_rows), and the re-layout of a GGUF quantized matrix
-// into the "split" layout the gfx950 matvec kernels stream:
-//
-//   Q8_0 : qs [R][K]      int8          | d  [R][K/32]  f16
-//   Q4_K : qs [R][K/2]    u8 nibbles    | hd [R][K/256] 16 B = {d, dmin, 4 x 24-bit scale pairs}
-//   Q5_K : qs [R][K/2]    u8 nibbles    | qh [R][K/8] u8 fifth-bit plane | hd [R][K/256] 16 B as Q4_K's
-//   Q6_K : ql [R][K/2]    u8            | qh [R][K/4] u8 | sc [R][K/16] i8 (lane-pair order) | d [R][K/256] f16
-//   Q3_K : q  [R][K/4]    u8            | h  [R][K/8] u8 | sc [R][K/16] i8 (piece order)     | d [R][K/256] f16
+// into the "split" layout the gfx950 matvec kernels stream. The layout's planes and their row
+// strides are the table of csrc/weight_types.h (plane_row_bytes); the order of the bytes inside
+// a plane is to_split's, restated by the dequantizers of the kernels (llm_device.h dequant_elem).
 //
 // Same bytes per weight as GGUF (algorithmic bytes unchanged; Q3_K: 114 B per superblock for
 // the GGUF's 110, below); each row's quant payload becomes one contiguous, 16-B aligned run, so
@@ -35,6 +31,8 @@
 #include <cstddef>
 #include <cstdint>
 #include <vector>
+
+#include "weight_types.h"
 
 namespace mio {
 
@@ -120,8 +118,6 @@ struct SplitLayout {
     size_t bytes = 0;
 };
 SplitLayout split_layout(uint32_t type, int64_t rows, int64_t k);
-// Bytes of one split-layout superblock of Q3_K (the GGUF block has 110)
-constexpr size_t kQ3KSplitBytes = 114;
 // GGUF rows -> split layout (dst has layout.bytes). Returns false on unsupported type.
 bool to_split(uint32_t type, const void *src, int64_t rows, int64_t k, uint8_t *dst);
 

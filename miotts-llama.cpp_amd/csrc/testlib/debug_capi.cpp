@@ -48,11 +48,8 @@ struct GuardedY {
 int debug_matvec(mio_hip_device *d, uint32_t type, const void *gguf_rows, const void *gguf_up, int rows, int k,
                  const float *x, float *y, int su = 0, int grid = 0) {
     MIO_REQUIRE(d && gguf_rows && x && y && rows > 0 && k > 0, MIO_ERR_INVALID, "debug_matvec: bad args");
-    MIO_REQUIRE(type == mio::GGML_Q8_0 || type == mio::GGML_Q3_K || type == mio::GGML_Q4_K || type == mio::GGML_Q5_K ||
-                    type == mio::GGML_Q6_K || type == mio::GGML_BF16 || (!gguf_up && mio::repacks_to_q8_0(type)),
-                MIO_ERR_UNSUPPORTED, "debug_matvec: type %u", type);
-    const bool k32 = type == mio::GGML_Q8_0 || type == mio::GGML_BF16 || mio::repacks_to_q8_0(type);
-    MIO_REQUIRE(k % (k32 ? 32 : 256) == 0, MIO_ERR_INVALID, "debug_matvec: k %d", k);
+    MIO_REQUIRE(mio::is_weight_type((int)type) || (!gguf_up && mio::repacks_to_q8_0(type)), MIO_ERR_UNSUPPORTED, "debug_matvec: type %u", type);
+    MIO_REQUIRE(k % (mio::is_kquant((int)type) ? 256 : 32) == 0, MIO_ERR_INVALID, "debug_matvec: k %d", k);
     int rc = mio::bind(d);
     if (rc) return rc;
     // Q4_0 / Q5_0 run as the Q8_0 rows they equal (llm_load does the same)
@@ -115,9 +112,7 @@ extern "C" int mio_hip_debug_matvec_group(mio_hip_device *d, uint32_t type, cons
                                           const void *gguf_up, int rows, int k, int su, int grid, const float *x,
                                           float *y) {
     MIO_REQUIRE(su > 0 && grid > 0 && grid <= 4096, MIO_ERR_INVALID, "debug_matvec_group: su %d / grid %d", su, grid);
-    MIO_REQUIRE(type == mio::GGML_Q8_0 || type == mio::GGML_Q3_K || type == mio::GGML_Q4_K || type == mio::GGML_Q5_K ||
-                    type == mio::GGML_Q6_K || type == mio::GGML_BF16,
-                MIO_ERR_UNSUPPORTED, "debug_matvec_group: type %u", type);
+    MIO_REQUIRE(mio::is_weight_type((int)type), MIO_ERR_UNSUPPORTED, "debug_matvec_group: type %u", type);
     return debug_matvec(d, type, gguf_gate, gguf_up, rows, k, x, y, su, grid);
 }
 
@@ -157,10 +152,8 @@ extern "C" int mio_hip_debug_mmq(mio_hip_device *d, uint32_t type, const void *g
     MIO_REQUIRE(d && gguf_rows && x && y && rows > 0 && k > 0 && nt > 0 && nt <= 4096 && mode >= 0 && mode <= 2 &&
                     (mode != 2 || gguf_up),
                 MIO_ERR_INVALID, "debug_mmq: bad args");
-    MIO_REQUIRE(type == mio::GGML_Q8_0 || type == mio::GGML_Q3_K || type == mio::GGML_Q4_K || type == mio::GGML_Q5_K ||
-                    type == mio::GGML_Q6_K,
-                MIO_ERR_UNSUPPORTED, "debug_mmq: type %u", type);
-    MIO_REQUIRE(k % (type == mio::GGML_Q8_0 ? 32 : 256) == 0, MIO_ERR_INVALID, "debug_mmq: k %d", k);
+    MIO_REQUIRE(type == mio::GGML_Q8_0 || mio::is_kquant((int)type), MIO_ERR_UNSUPPORTED, "debug_mmq: type %u", type);
+    MIO_REQUIRE(k % mio::block_elems((int)type) == 0, MIO_ERR_INVALID, "debug_mmq: k %d", k);
     int rc = mio::bind(d);
     if (rc) return rc;
     const mio::SplitLayout L = mio::split_layout(type, rows, k);
@@ -256,3 +249,28 @@ extern "C" int mio_debug_to_split(uint32_t type, const void *rows_bytes, int row
     if (out && !mio::to_split(type, rows_bytes, rows, k, out)) return MIO_ERR_UNSUPPORTED;
     return MIO_OK;
 }
+
+// The weight-type table (csrc/weight_types.h) as the host sites read it, host only: stride[4] =
+// the planes' row strides of a [rows][k] matrix, off[4] = split_layout's plane offsets,
+// moved[4] = the bytes qmat_rows(q, r0, n) moves each plane pointer by (0: no such plane).
+extern "C" int mio_debug_weight_layout(uint32_t type, int rows, int k, int r0, int n, uint64_t *stride, uint64_t *off,
+                                       uint64_t *moved) {
+    MIO_REQUIRE(stride && off && moved && rows > 0 && k > 0 && r0 >= 0 && n >= 0 && r0 + n <= rows, MIO_ERR_INVALID,
+                "debug_weight_layout: bad args");
+    MIO_REQUIRE(mio::is_weight_type((int)type), MIO_ERR_UNSUPPORTED, "debug_weight_layout: type %u", type);
+    const mio::SplitLayout L = mio::split_layout(type, rows, k);
+    std::vector<uint8_t> buf(L.bytes);
+    const mio::QMat q{(int)type, rows, k, buf.data() + L.off[0], buf.data() + L.off[1], buf.data() + L.off[2],
+                      buf.data() + L.off[3]};
+    const mio::QMat v = mio::qmat_rows(q, r0, n);
+    const uint8_t *qp[4] = {q.p0, q.p1, q.p2, q.p3}, *vp[4] = {v.p0, v.p1, v.p2, v.p3};
+    for (int p = 0; p < 4; ++p) {
+        stride[p] = mio::plane_row_bytes((int)type, k, p);
+        off[p] = L.off[p];
+        moved[p] = (uint64_t)(vp[p] - qp[p]);
+    }
+    return v.rows == n && v.k == k && v.type == (int)type ? MIO_OK : MIO_ERR_INVALID;
+}
+
+// attn_v_supported(tq, tv): 1 where the q|k|v launches exist for v of type tv beside q|k of type tq.
+extern "C" int mio_debug_attn_v_supported(int tq, int tv) { return mio::attn_v_supported(tq, tv) ? 1 : 0; }

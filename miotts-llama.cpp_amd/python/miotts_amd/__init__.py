@@ -165,6 +165,8 @@ def _declare(L: ctypes.CDLL) -> None:
         "mio_quantize_rows": (c_int, [ctypes.c_uint32, _vp, c_int, c_int, _vp]),
         "mio_dequantize_rows": (c_int, [ctypes.c_uint32, _vp, c_int, c_int, _vp]),
         "mio_debug_to_split": (c_int, [ctypes.c_uint32, _vp, c_int, c_int, _vp, _vp, _vp]),
+        "mio_debug_weight_layout": (c_int, [ctypes.c_uint32, c_int, c_int, c_int, c_int, _vp, _vp, _vp]),
+        "mio_debug_attn_v_supported": (c_int, [c_int, c_int]),
         "mio_hip_debug_mmq": (c_int, [_vp, ctypes.c_uint32, _vp, c_int, c_int, _vp, c_int, c_int, _vp, _vp]),
         "mio_hip_debug_codec_gemm": (c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(c_int)]),
         "mio_hip_debug_codec_conv": (c_int, [_vp, _vp, c_int, c_int, c_int, c_int, _vp, c_int, _vp, c_int, _vp, _vp,
@@ -772,6 +774,19 @@ def to_split(qtype: int, rows_bytes: np.ndarray, k: int):
     out = np.zeros(int(n[0]), np.uint8)
     check(lib().mio_debug_to_split(qtype, _ptr(rows_bytes), rows_bytes.shape[0], k, _ptr(out), _ptr(n), _ptr(off)))
     return out, [int(o) for o in off]
+
+
+def weight_layout(qtype: int, rows: int, k: int, r0: int = 0, n: int = 0):
+    """The weight-type table (csrc/weight_types.h) for a [rows][k] matrix, host only: (the planes' row
+    strides, split_layout's plane offsets, the bytes qmat_rows(q, r0, n) moves each plane pointer by)."""
+    stride, off, moved = (np.zeros(4, np.uint64) for _ in range(3))
+    check(lib().mio_debug_weight_layout(qtype, rows, k, r0, n, _ptr(stride), _ptr(off), _ptr(moved)))
+    return [int(v) for v in stride], [int(v) for v in off], [int(v) for v in moved]
+
+
+def attn_v_supported(tq: int, tv: int) -> bool:
+    """Do the q|k|v launches exist for attn_v of ggml type tv beside q|k of type tq?"""
+    return bool(lib().mio_debug_attn_v_supported(tq, tv))
 
 
 def debug_matvec(dev: Device, qtype: int, w_rows: np.ndarray, k: int, x: np.ndarray) -> np.ndarray:
