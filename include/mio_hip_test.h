@@ -82,6 +82,11 @@ int mio_hip_llm_set_kv_rows(mio_hip_llm *m, int il, int p0, int n_pos, const uin
  * their own). A short-conv layer is refused with MIO_ERR_INVALID. */
 int mio_hip_llm_debug_attention(mio_hip_llm *m, int il, int pos, int which, const float *qkv, float *att);
 
+/* The polled words of the fused attention launches' hand-offs: words[3 * n_kv] receives, per kv
+ * head, the q row counter, the q|k|v row counter and the chunk arrival word. Every one is 0 between
+ * decode steps. reset != 0: the runner's counter reset runs first. */
+int mio_hip_llm_handoff_words(mio_hip_llm *m, int reset, int32_t *words);
+
 /* ---------------- the sampler chain on an injected logits row ----------------
  * One launch of the chain kernel (penalties -> top-k -> top-p -> min-p -> draw, mio_hip.h
  * mio_sampling) followed by the flush sampler that takes its token: logits[n_vocab] is the row,

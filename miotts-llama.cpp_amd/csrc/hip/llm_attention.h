@@ -17,13 +17,18 @@ __device__ inline float lane_value(float v, int i) {
 }
 
 // The body of one (chunk ch, kv head kvh) workgroup at position pos (first AttCfg<HD>::NT
-// threads). rdy: the fused attention + O launch's merge counter (attn_merge_last), or null.
+// threads). rdy: the fused attention + O launch's merge counter (attn_merge_store), or null.
 // WQ (k_layer_att: q|k|v produced in the same launch): the K/V rows are loaded and staged
-// first, then one lane waits until the kv head's q|k|v row counter (b.att_cnt + kQkvOff +
-// kQkvStride * kvh) reaches (G + 2) * HD rows, and the head rows are loaded sc1.
+// first, then one lane waits for the head rows the workgroup loads (sc1) and for no others: the
+// chunk that owns `pos`, the only one that loads the new k and v rows, until the kv head's
+// q|k|v row counter (qkv_word) reaches (G + 2) * HD, every other chunk until the head's q row
+// counter reaches G * HD. Their K/V are cache rows of earlier positions, so they do not stand
+// behind the v producers, the last workgroups to be dispatched. One word to poll either way.
+// OM (the fused launches, rdy != null): the owning chunk merges (attn_merge_owner), else the
+// last chunk to arrive (attn_merge_last).
 // Returns false for a workgroup with no positions (or after an end token). done: StepState.done
 // as the caller read it.
-template <int HD, int G, bool DG, bool WQ = false>
+template <int HD, int G, bool DG, bool WQ = false, bool OM = false>
 __device__ __forceinline__ bool attention_wg(const LlmDims &d, const float *q_norm, const float *k_norm,
                                              const float *bqkv, _Float16 *kc, _Float16 *vc, const LlmBuffers &b,
                                              bool done, int ch, int kvh, int pos, int *rdy) {
@@ -59,9 +64,9 @@ __device__ __forceinline__ bool attention_wg(const LlmDims &d, const float *q_no
         kv_stage<HD>(kr, vr, owner ? pos - t0 : -1, img, img + A::IMG);
         MIO_TL_MARK(b, 4);  // K / V staged
         if (MIO_TIDX == 0)
-            wait_count(b.att_cnt + kQkvOff + kQkvStride * kvh, (G + 2) * HD, b.att_cnt + kRdyFlag);
+            wait_count(qkv_word(b.att_cnt, kvh, owner), owner ? (G + 2) * HD : G * HD, b.att_cnt + kRdyFlag);
         asm volatile("s_barrier" ::: "memory");
-        MIO_TL_MARK(b, 3);  // q|k|v rows of this kv head written
+        MIO_TL_MARK(b, 3);  // the head rows this chunk loads are written: q (owner: q|k|v)
         if (wave < G + (owner ? 1 : 0)) head_src(wave, hin);
     } else {
         if (wave < G + (owner ? 1 : 0)) head_src(wave, hin);
@@ -100,8 +105,14 @@ __device__ __forceinline__ bool attention_wg(const LlmDims &d, const float *q_no
     const uint32_t gs = (uint32_t)(d.max_splits * C::REC), head0 = (uint32_t)(kvh * G) * gs;
     attend_chunk_mfma<HD, G>(qh, img, img + A::IMG, t0, pos, d.scale, b.part + head0 + (uint32_t)ch * C::REC, gs,
                              DG ? b.trace : nullptr);
-    attn_merge_last<HD, G>(b.part, head0, gs, pos / ATT_CHUNK + 1, b.att_cnt + kvh, b.att + (size_t)kvh * G * HD, -1,
-                           {}, 0, rdy, (kDiag && b.tl) ? MIO_TL_SLOT(b) : nullptr);
+    if constexpr (OM)
+        attn_merge_owner<HD, G>(b.part, head0, gs, pos / ATT_CHUNK + 1, owner,
+                                b.att_cnt + kQkvOff + kQkvStride * kvh + kArrSub, b.att_cnt + kRdyFlag,
+                                b.att + (size_t)kvh * G * HD, rdy,
+                                (kDiag && b.tl) ? MIO_TL_SLOT(b) : nullptr);
+    else
+        attn_merge_last<HD, G>(b.part, head0, gs, pos / ATT_CHUNK + 1, b.att_cnt + kvh, b.att + (size_t)kvh * G * HD,
+                               -1, {}, 0, rdy, (kDiag && b.tl) ? MIO_TL_SLOT(b) : nullptr);
     return true;
 }
 
@@ -113,11 +124,13 @@ __device__ __forceinline__ bool attention_wg(const LlmDims &d, const float *q_no
 // (pos / ATT_CHUNK + 1) * n_kv are the attention chunks (chunk bid / n_kv, kv head bid % n_kv;
 // their first AttCfg::NT threads), the next matvec_grid(wo) are k_attn_out's workgroups, the
 // rest return. The n_kv merging workgroups store the head outputs write-through and add 1 to
-// each of the 8 counter shards at b.att_cnt + kRdyOff (attn_merge_last); an O workgroup issues
+// each of the 8 counter shards at b.att_cnt + kRdyOff (attn_merge_store); an O workgroup issues
 // its weight group, waits for n_kv on its shard (one lane, wait_count), then loads the outputs
-// sc1. Deadlock-free by dispatch
-// order: every producer has a lower workgroup index than every consumer and never waits, so
-// it is dispatched (and finishes) whatever the residency. The counter is zeroed by the next
+// sc1. The merging workgroup of a kv head is the chunk that owns pos (attn_merge_owner); it
+// waits for the head's other chunks. Deadlock-free by dispatch order: every workgroup that is
+// waited for has a lower index than the one that waits (chunk-major: the owner is its head's
+// highest chunk) and never waits itself, so it is dispatched (and finishes) whatever the
+// residency. The counter is zeroed by the next
 // launch, k_ffn_in (kernel boundary ordered), and by reset_tickets.
 // K = wo.k (k_att_o has it in its entry pack).
 template <int NP, int T, int SU, bool DG>

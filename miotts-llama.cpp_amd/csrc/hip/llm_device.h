@@ -1679,6 +1679,11 @@ __device__ __forceinline__ void st4_sc1(float *base, uint32_t off, float4 v) {
     u.x = __float_as_uint(v.x), u.y = __float_as_uint(v.y), u.z = __float_as_uint(v.z), u.w = __float_as_uint(v.w);
     __builtin_amdgcn_raw_buffer_store_b128(u, rsrc(base, 0x7FFFFFF0u), off, 0, 16);
 }
+// k_layer_att's row counters of kv head kvh: all = false the word that counts its q rows (G * hd),
+// true the word that counts its q, k and v rows ((G + 2) * hd)
+__device__ __forceinline__ int *qkv_word(int *att_cnt, int kvh, bool all) {
+    return att_cnt + kQkvOff + kQkvStride * kvh + (all ? kAllSub : 0);
+}
 // One lane waits until the agent-scope counter *c reaches target (relaxed loads, s_sleep
 // between polls: MI355X_MICROARCH "polling-cost"). Bounded: after ~2^16 polls (tens of ms) it
 // gives up and raises *flag, so a lost signal ends the launch instead of hanging the GPU. Once
@@ -2150,23 +2155,14 @@ __device__ __forceinline__ void q_to_f16(const float *src, _Float16 *dst) {
 // workgroups of the same launch, so they are stored sc1 (write-through), drained, and then
 // lanes 0..7 add 1 to each of the 8 counter shards rdy[64 i] (the O workgroups wait for n_kv
 // adds on theirs), the same hand-off form as the records'.
+// attn_merge_store is the merging workgroup's part once every record may be read (the merge and
+// the stores), shared with attn_merge_owner below.
 template <int HD, int G>
-__device__ void attn_merge_last(const float *part, uint32_t head0, uint32_t g_stride, int nch, int *cnt, float *out,
-                                int ak = -1, ActL rec = {}, int blk0 = 0, int *rdy = nullptr,
-                                unsigned long long *tl = nullptr) {
+__device__ __forceinline__ void attn_merge_store(const float *part, uint32_t head0, uint32_t g_stride, int nch,
+                                                 float *out, int ak, ActL rec, int blk0, int *rdy,
+                                                 unsigned long long *tl) {
     constexpr int NT = AttCfg<HD>::NT, REC = AttCfg<HD>::REC;
-    __shared__ int last_;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (MIO_TIDX == 0) {
-        auto *c = (__attribute__((address_space(1))) int *)cnt;
-        const int old = __hip_atomic_fetch_add(c, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last_ = old == nch - 1;
-        if (old == nch - 1) __hip_atomic_store(c, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    if (!last_) return;
-    if (tl && MIO_TIDX == 0) tl[5] = __builtin_amdgcn_s_memrealtime();  // step timeline: merger's ticket
+    if (tl && MIO_TIDX == 0) tl[5] = __builtin_amdgcn_s_memrealtime();  // step timeline: merger saw the records' count
     // one float4 of outputs per thread and pass (G * hd > 4 NT: several passes); in pass b,
     // wave w holds outputs 4 NT b + 256 w .. + 255 (one Q8_K superblock / eight Q8_0 blocks)
 #pragma unroll
@@ -2201,6 +2197,57 @@ __device__ void attn_merge_last(const float *part, uint32_t head0, uint32_t g_st
             __hip_atomic_fetch_add((__attribute__((address_space(1))) int *)(rdy + 64 * MIO_TIDX), 1,
                                    __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
+}
+
+template <int HD, int G>
+__device__ void attn_merge_last(const float *part, uint32_t head0, uint32_t g_stride, int nch, int *cnt, float *out,
+                                int ak = -1, ActL rec = {}, int blk0 = 0, int *rdy = nullptr,
+                                unsigned long long *tl = nullptr) {
+    __shared__ int last_;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (MIO_TIDX == 0) {
+        auto *c = (__attribute__((address_space(1))) int *)cnt;
+        const int old = __hip_atomic_fetch_add(c, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        last_ = old == nch - 1;
+        if (old == nch - 1) __hip_atomic_store(c, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+    if (!last_) return;
+    attn_merge_store<HD, G>(part, head0, g_stride, nch, out, ak, rec, blk0, rdy, tl);
+}
+
+// The decode step's fused launches (k_att_o, k_layer_att): the chunk that owns `pos` merges,
+// no ticket. It is the head's highest chunk, so its record merges last in chunk order anyway,
+// and chunk workgroups are chunk-major (chunk = index / n_kv): the owner has a higher workgroup
+// index than every chunk it waits for, and those chunks wait only for producers (or for
+// nothing), so in-order dispatch makes progress whatever the residency.
+// A non-owning chunk: records stored sc1 (attend_chunk_mfma), every wave's vmcnt(0), the
+// workgroup barrier, then ONE lane adds 1 to the head's arrival word arr with a no-return
+// agent-scope add (nothing waits for its round trip) and the workgroup ends.
+// The owning chunk: one lane waits (wait_count, bounded, raises *flag) until arr counts the
+// nch - 1 other chunks, while the other waves drain their own record stores; a barrier; every
+// add has landed then, so the same lane stores 0 to arr for the next launch; the merge, its
+// sc1 record loads all behind that barrier (MI355X_MICROARCH "Valid forms", first row: the
+// signal follows every storing wave's vmcnt(0), the reader loads sc1 after it saw the count).
+// The record bytes, merge_out4 and its float order are attn_merge_last's: the same bits.
+template <int HD, int G>
+__device__ __forceinline__ void attn_merge_owner(const float *part, uint32_t head0, uint32_t g_stride, int nch,
+                                                 bool owner, int *arr, int *flag, float *out, int *rdy,
+                                                 unsigned long long *tl) {
+    auto *c = (__attribute__((address_space(1))) int *)arr;
+    if (!owner) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (MIO_TIDX == 0) __hip_atomic_fetch_add(c, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return;
+    }
+    if (MIO_TIDX == 0 && nch > 1) wait_count(arr, nch - 1, flag);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    // behind the barrier: in flight beside the record loads, not a round trip ahead of them
+    if (MIO_TIDX == 0 && nch > 1) __hip_atomic_store(c, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    attn_merge_store<HD, G>(part, head0, g_stride, nch, out, -1, {}, 0, rdy, tl);
 }
 
 // ------------------------------------------------------------------ host-side dispatch

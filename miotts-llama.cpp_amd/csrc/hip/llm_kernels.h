@@ -103,8 +103,8 @@ struct LlmBuffers {
     float *h;          // [n_ff] ffn activation
     float *logits;     // [n_vocab]
     float *part;       // [H][max_splits][hd + 4] attention chunk partials {O, m, l}
-    float *att;        // [H * hd] attention output (chunks merged by the last chunk workgroup)
-    int *att_cnt;      // [Hkv] chunk arrival tickets (0 between launches); k_att_o's merge
+    float *att;        // [H * hd] attention output (chunks merged by one chunk workgroup per kv head)
+    int *att_cnt;      // [Hkv] chunk arrival tickets (0 between launches); the fused launches'
                        // counters and wait-timeout flag at kRdyOff.. (kAttCntInts in all)
     float *smp;        // sampler partials [2 * n_lm_blocks]
     const float2 *rope;  // [n_ctx][hd/2] (cos, sin)
@@ -255,10 +255,13 @@ void launch_layer_att(const LlmDims &d, const LayerW &L, _Float16 *kc, _Float16 
 // apart from int kRdyOff on (one per XCD: an O workgroup polls shard blockIdx % 8, so no word
 // has more than 1/8 of the pollers; MI355X_MICROARCH "dequeue": one word saturates near 88
 // accesses per us), then the wait-timeout flag. Needs n_kv <= kRdyOff.
-// Then k_layer_att's q|k|v row counters, one per kv head (at most kQkvMax), kQkvStride apart.
+// Then three polled words per kv head (at most kQkvMax heads, kQkvStride ints apart, the words
+// of a head 256 B apart): k_layer_att's q row counter (+ 0; the head's G * hd q rows) and q|k|v
+// row counter (+ kAllSub; all its (G + 2) * hd rows: a q row is counted in both), and the chunk
+// arrival word of the fused launches (+ kArrSub: attn_merge_owner; the owning chunk zeroes it).
 constexpr int kRdyOff = 64, kRdyShards = 8, kRdyStride = 64;
 constexpr int kRdyFlag = kRdyOff + kRdyShards * kRdyStride;
-constexpr int kQkvOff = kRdyFlag + 64, kQkvStride = 64, kQkvMax = 64;
+constexpr int kQkvOff = kRdyFlag + 64, kAllSub = 64, kArrSub = 128, kQkvStride = 192, kQkvMax = 64;
 // Then the fused FFN launch's h counters (k_ffn, which = 12), two levels, every word kFfnStride
 // ints apart: kFfnShards arrival shards (gate|up workgroup b adds 1 to shard b % 8: <= 32 adds
 // per word at 256 producers; the price list's fan-in on one word is 3.6-4.5 us), then

@@ -139,9 +139,10 @@ __global__ __launch_bounds__(MT) void k_ffn_in(LlmDims d, const float *norm_w, Q
     if (blockIdx.x == 0 && MIO_TIDX < kRdyShards)
         __hip_atomic_store((__attribute__((address_space(1))) int *)(b.att_cnt + kRdyOff + kRdyStride * MIO_TIDX), 0,
                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (blockIdx.x == 1 && MIO_TIDX < d.n_kv)
-        __hip_atomic_store((__attribute__((address_space(1))) int *)(b.att_cnt + kQkvOff + kQkvStride * MIO_TIDX), 0,
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (blockIdx.x == 1 && MIO_TIDX < 2 * d.n_kv)  // the q and the q|k|v word of each kv head
+        __hip_atomic_store((__attribute__((address_space(1))) int *)(b.att_cnt + kQkvOff + kQkvStride * (MIO_TIDX >> 1) +
+                                                                     kAllSub * (MIO_TIDX & 1)),
+                           0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     int lo, hi;
     wave_range(d, gate.rows, lo, hi);
     Frag ga[Cfg<NP, SU>::U], gb[Cfg<NP, SU>::U];
@@ -233,8 +234,10 @@ __global__ __launch_bounds__(MT) void k_ffn(float *x, const float *norm_w, StepS
         if (blockIdx.x == 0 && MIO_TIDX < kRdyShards)
             __hip_atomic_store((__attribute__((address_space(1))) int *)(b.att_cnt + kRdyOff + kRdyStride * MIO_TIDX),
                                0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (blockIdx.x == 1 && MIO_TIDX < d.n_kv)
-            __hip_atomic_store((__attribute__((address_space(1))) int *)(b.att_cnt + kQkvOff + kQkvStride * MIO_TIDX),
+        if (blockIdx.x == 1 && MIO_TIDX < 2 * d.n_kv)  // the q and the q|k|v word of each kv head
+            __hip_atomic_store((__attribute__((address_space(1))) int *)(b.att_cnt + kQkvOff +
+                                                                         kQkvStride * (MIO_TIDX >> 1) +
+                                                                         kAllSub * (MIO_TIDX & 1)),
                                0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         int lo, hi;
         wave_range(gate.rows, lo, hi, blockIdx.x, GI);
@@ -439,7 +442,8 @@ __global__ __launch_bounds__(MT) void k_lm_head(const float *x, const float *nor
 // One workgroup per (chunk of ATT_CHUNK positions, kv head): q/k RMSNorm (qwen3) + RoPE +
 // f16 rounding, the chunk owning `pos` appends the new k/v row to the F16 cache, then a
 // softmax over the chunk for the G q heads sharing the kv head, whose partial records
-// {O[HD], m, l} the last chunk workgroup to arrive merges into b.att (attn_merge_last):
+// {O[HD], m, l} the last chunk workgroup to arrive merges into b.att (attn_merge_last; in
+// k_att_o and k_layer_att the chunk that owns pos, attn_merge_owner):
 // ATT_CHUNK (64) -position chunks spread the K/V rows of position ~400 over 7 x n_kv
 // workgroups (32 KB each at hd 128), and k_attn_out (or the O workgroups of k_att_o) reads
 // the n_head * hd merged values.
@@ -494,8 +498,8 @@ __global__ __launch_bounds__(MT) void k_att_o(StepState *st, int K, int n_kv, in
     const int bid = blockIdx.x, n_act = (pos / ATT_CHUNK + 1) * n_kv;
     if (bid < n_act) {
         if (MIO_TIDX >= AttCfg<HD>::NT) return;  // whole waves; s_barrier counts the live ones
-        if (!attention_wg<HD, G, DG>(d, q_norm, k_norm, bqkv, kc, vc, b, false, bid / n_kv, bid % n_kv, pos,
-                                     b.att_cnt + kRdyOff))
+        if (!attention_wg<HD, G, DG, false, true>(d, q_norm, k_norm, bqkv, kc, vc, b, false, bid / n_kv, bid % n_kv,
+                                                  pos, b.att_cnt + kRdyOff))
             return;
     } else {
         const int ob = bid - n_act;

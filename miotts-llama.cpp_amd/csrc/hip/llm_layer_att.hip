@@ -4,14 +4,19 @@
 // k_attention and k_attn_out's bodies as three workgroup roles of one grid:
 //   [0, GW)                q|k|v producers (k_attn_in's body; rows stored write-through, then
 //                          the rows each workgroup wrote per kv head added to that head's
-//                          counter at b.att_cnt + kQkvOff + kQkvStride * kvh)
+//                          q|k|v row counter and, q rows, to its q row counter: qkv_word)
 //   [GW, GW + n_act)       attention chunks (n_act = (pos / ATT_CHUNK + 1) * n_kv): K/V rows
 //                          of the chunk loaded and staged in LDS first, then one lane waits
-//                          for the kv head's (G + 2) * hd rows, the head rows are loaded sc1
-//                          (attention_wg<..., WQ = true>); the mergers signal the O counters
+//                          for the head rows the chunk loads (the chunk that owns pos for the
+//                          kv head's (G + 2) * hd rows, the others for its G * hd q rows
+//                          only), which are loaded sc1 (attention_wg<..., WQ = true>); the
+//                          owning chunk waits for the head's other chunks, merges
+//                          (attn_merge_owner) and signals the O counters
 //   [GW + n_act, + no)     O workgroups (o_consumer, as in k_att_o)
 // Every consumer has a higher workgroup index than the producers it waits for, and producers
-// never wait, so in-order dispatch makes progress whatever the residency (MI355X_MICROARCH
+// never wait; chunk workgroups are chunk-major, so the owning chunk too has a higher index than
+// the chunks it waits for, which wait for producers only: in-order dispatch makes progress
+// whatever the residency (MI355X_MICROARCH
 // "Persistent kernels": hand-offs inside a launch instead of a ~1.2-1.5 us boundary each).
 // Layer 0 keeps k_attn_in (its sampler may end the step) + k_att_o. The counters are zeroed by
 // the next launch, k_ffn_in. Instantiated for the shipped head shapes and weight types only
@@ -68,13 +73,17 @@ __device__ __forceinline__ void qkv_producer(const float *x, const float *norm_w
             put(o2 + row, v);
         });
     }
-    // every row of the workgroup written through, then per kv head ONE add of the workgroup's
-    // row count there (runs of equal heads over rows ra .. rb - 1 <= 64, host-checked)
+    // every row of the workgroup written through, then per (kv head, q or k|v) ONE add of the
+    // workgroup's row count to the head's q|k|v word and, for q rows, one more to its q word
+    // (runs of equal keys over rows ra .. rb - 1 <= 64, host-checked): key 2 h for head h's q
+    // rows, 2 h + 1 for its k and its v row
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (MIO_TIDX < 64) {
         const int i = MIO_TIDX, r = ra + i;
-        auto head_of = [&](int rr) { return rr < o1 ? rr / (HD * G) : (rr < o2 ? (rr - o1) / HD : (rr - o2) / HD); };
+        auto head_of = [&](int rr) {
+            return rr < o1 ? 2 * (rr / (HD * G)) : 2 * ((rr < o2 ? rr - o1 : rr - o2) / HD) + 1;
+        };
         const bool ok = r < rb;
         const int h = ok ? head_of(r) : -1;
         const bool start = ok && (i == 0 || head_of(r - 1) != h);
@@ -82,8 +91,11 @@ __device__ __forceinline__ void qkv_producer(const float *x, const float *norm_w
         if (start) {
             const uint64_t nx = i < 63 ? m >> (i + 1) : 0;
             const int end = nx ? i + 1 + __builtin_ctzll(nx) : rb - ra;
-            __hip_atomic_fetch_add((__attribute__((address_space(1))) int *)(b.att_cnt + kQkvOff + kQkvStride * h),
-                                   end - i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (!(h & 1))
+                __hip_atomic_fetch_add((__attribute__((address_space(1))) int *)qkv_word(b.att_cnt, h >> 1, false),
+                                       end - i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_fetch_add((__attribute__((address_space(1))) int *)qkv_word(b.att_cnt, h >> 1, true), end - i,
+                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
 }
@@ -114,7 +126,7 @@ __global__ __launch_bounds__(MT) void k_layer_att(const float *x, const float *n
         const int ab = bid - GW, n_act = (pos / ATT_CHUNK + 1) * n_kv;
         if (ab < n_act) {
             if (MIO_TIDX >= AttCfg<HD>::NT) return;  // whole waves; s_barrier counts the live ones
-            if (!attention_wg<HD, G, DG, true>(d, q_norm, k_norm, bqkv, kc, vc, b, false, ab / n_kv, ab % n_kv, pos,
+            if (!attention_wg<HD, G, DG, true, true>(d, q_norm, k_norm, bqkv, kc, vc, b, false, ab / n_kv, ab % n_kv, pos,
                                                b.att_cnt + kRdyOff))
                 return;
         } else {

@@ -50,6 +50,9 @@ int llm_set_kv_rows(mio_hip_llm *m, int il, int p0, int n_pos, const uint16_t *k
 // which = 1 (k_attention) or 10 (k_att_o); att[H hd] receives LlmBuffers.att. Leaves the decode
 // state at pos and cache row pos written.
 int llm_debug_attention(mio_hip_llm *m, int il, int pos, int which, const float *qkv, float *att);
+// words[3 n_kv]: per kv head the q row counter, the q|k|v row counter and the chunk arrival word of
+// the fused attention launches (0 between steps); reset != 0: after reset_tickets.
+int llm_handoff_words(mio_hip_llm *m, int reset, int32_t *words);
 // One sampler chain launch (k_sample_chain) + the flush sampler on the injected row
 // logits[n_vocab], with history[n_history] as the tokens sampled before `step` and sp's
 // temperature, seed, window and chain knobs: the token, the kept count, the id at the cut and

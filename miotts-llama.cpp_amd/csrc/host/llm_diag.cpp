@@ -107,6 +107,24 @@ int mio::llm_set_kv_rows(mio_hip_llm *m, int il, int p0, int n_pos, const uint16
     return MIO_OK;
 }
 
+// The polled words of the attention hand-offs per kv head (tests of the counters' hygiene):
+// words[3 h + 0 .. 2] = head h's q row counter, q|k|v row counter and chunk arrival word. All are
+// 0 between steps. reset: reset_tickets first.
+int mio::llm_handoff_words(mio_hip_llm *m, int reset, int32_t *words) {
+    MIO_REQUIRE(m && words && m->dims.n_kv <= mio::kQkvMax, MIO_ERR_INVALID, "llm_handoff_words: bad args");
+    int rc = mio::bind(m->d);
+    if (rc) return rc;
+    if (reset && (rc = reset_tickets(m))) return rc;
+    hipStream_t s = m->d->stream;
+    const int sub[3] = {0, mio::kAllSub, mio::kArrSub};
+    for (int h = 0; h < m->dims.n_kv; ++h)
+        for (int j = 0; j < 3; ++j)
+            MIO_HIP_CHECK(hipMemcpyAsync(words + 3 * h + j, m->buf.att_cnt + mio::kQkvOff + mio::kQkvStride * h + sub[j],
+                                         sizeof(int), hipMemcpyDeviceToHost, s));
+    MIO_HIP_CHECK(hipStreamSynchronize(s));
+    return MIO_OK;
+}
+
 // One attention launch on an injected q|k|v row (parity tests): the state is set to pos, the
 // row replaces buf.qkv, launch_step_kernel(which) of layer il runs alone, and buf.att comes
 // back. kAttO also runs the O workgroups (buf.x += W_o att, on token 0's embedding).
@@ -260,7 +278,7 @@ uint64_t kind_bytes(const mio_hip_llm *m, mio::StepKind kind, const mio::LayerW 
     auto qbytes = [](const mio::QMat &q) { return (uint64_t)mio::row_bytes(q.type, q.k) * (uint64_t)q.rows; };
     const uint64_t nch = pos / mio::kAttChunk + 1, qkv = (uint64_t)(D.n_head + 2 * D.n_kv) * D.hd;
     // chunk partial records {O, m, l}: written by the chunk workgroups, read back by the
-    // merging one (attn_merge_last), which writes the n_head * hd outputs
+    // merging one (attn_merge_last / attn_merge_owner), which writes the n_head * hd outputs
     const uint64_t part = 4ull * D.n_head * nch * (D.hd + 2);
     // x in + the q|k|v weights; q|k|v out only where another launch reads it
     const uint64_t attn_in_bytes = qbytes(L.wq) + qbytes(L.wk) + qbytes(L.wv) + 4ull * D.n_embd;

@@ -200,6 +200,10 @@ extern "C" int mio_hip_llm_debug_attention(mio_hip_llm *m, int il, int pos, int 
     return mio::llm_debug_attention(m, il, pos, which, qkv, att);
 }
 
+extern "C" int mio_hip_llm_handoff_words(mio_hip_llm *m, int reset, int32_t *words) {
+    return mio::llm_handoff_words(m, reset, words);
+}
+
 extern "C" int mio_hip_llm_debug_sample_chain(mio_hip_llm *m, const float *logits, const int32_t *history,
                                               int n_history, const mio_sampling *s, float temperature, uint64_t seed,
                                               int step, int32_t lo, int32_t hi, int32_t *token, int32_t *kept,

@@ -152,6 +152,7 @@ def _declare(L: ctypes.CDLL) -> None:
         "mio_hip_llm_kv_rows": (c_int, [_vp, c_int, c_int, _vp, _vp]),
         "mio_hip_llm_set_kv_rows": (c_int, [_vp, c_int, c_int, c_int, _vp, _vp]),
         "mio_hip_llm_debug_attention": (c_int, [_vp, c_int, c_int, c_int, _vp, _vp]),
+        "mio_hip_llm_handoff_words": (c_int, [_vp, c_int, _vp]),
         "mio_hip_llm_set_sampling": (c_int, [_vp, ctypes.POINTER(Sampling)]),
         "mio_hip_llm_get_sampling": (c_int, [_vp, ctypes.POINTER(Sampling)]),
         "mio_hip_llm_debug_sample_chain": (c_int, [_vp, _vp, _vp, c_int, ctypes.POINTER(Sampling), ctypes.c_float,
@@ -656,6 +657,14 @@ class Llm:
         att = np.empty((self.n_head, self.head_dim), np.float32)
         check(lib().mio_hip_llm_debug_attention(self.h, il, pos, which, _ptr(qkv), _ptr(att)))
         return att
+
+    def handoff_words(self, reset: bool = False) -> np.ndarray:
+        """[n_kv, 3]: per kv head the q row counter, the q|k|v row counter and the chunk arrival word
+        of the fused attention launches, 0 between steps (test-support library); reset: after
+        the runner's counter reset."""
+        w = np.full((self.n_kv, 3), -1, np.int32)
+        check(lib().mio_hip_llm_handoff_words(self.h, int(reset), _ptr(w)))
+        return w
 
     def set_sampling(self, sampling=None, **knobs) -> None:
         """The sampler chain's knobs for later generate / generate_batch calls

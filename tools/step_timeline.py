@@ -93,7 +93,8 @@ if ia:
           f"{med(T[:, :, 1] - base, isO):.2f} end {med(T[:, :, 7] - base, isO):.2f} "
           f"(last {lastv(T[:, :, 7] - base, isO):.2f}) us after the launch's first start")
 # the whole attention block in one launch: producers (no mark 3), attention (mark 4 = K/V
-# staged, mark 3 = q|k|v ready), O workgroups (mark 3, no mark 4)
+# staged, mark 3 = the head rows the chunk loads are written: q, and k|v too in the chunks that
+# own the position, the last n_kv attention workgroups), O workgroups (mark 3, no mark 4)
 il = [i for i, n in enumerate(names) if n == "layer_att"]
 if il:
     T = t[il]
@@ -101,6 +102,10 @@ if il:
     m3, m4 = np.isfinite(T[:, :, 3]), np.isfinite(T[:, :, 4])
     isA, isO = m3 & m4, m3 & ~m4
     isP = np.isfinite(T[:, :, 2]) & ~m3
+    # the owning chunks: the n_kv attention workgroups with the highest indices
+    own = np.zeros_like(isA)
+    for i in range(isA.shape[0]):
+        own[i, np.flatnonzero(isA[i])[-llm.n_kv:]] = True
 
     def med(x, msk):
         return float(np.nanmedian(np.where(msk, x, np.nan)))
@@ -109,12 +114,13 @@ if il:
         return float(np.nanmedian(np.nanmax(np.where(msk, x, np.nan), axis=1)))
     print(f"  layer_att: {int(isP[0].sum())} producers end {med(T[:, :, 7] - base, isP):.2f} (last "
           f"{lastv(T[:, :, 7] - base, isP):.2f}); {int(isA[0].sum())} attention: K/V staged "
-          f"{med(T[:, :, 4] - base, isA):.2f}, q|k|v ready {med(T[:, :, 3] - base, isA):.2f}, end "
+          f"{med(T[:, :, 4] - base, isA):.2f}, q ready {med(T[:, :, 3] - base, isA & ~own):.2f}, q|k|v ready "
+          f"{med(T[:, :, 3] - base, own):.2f}, end "
           f"{med(T[:, :, 7] - base, isA):.2f} (last {lastv(T[:, :, 7] - base, isA):.2f}); {int(isO[0].sum())} O: "
           f"wait done {med(T[:, :, 3] - base, isO):.2f}, end {med(T[:, :, 7] - base, isO):.2f} (last "
           f"{lastv(T[:, :, 7] - base, isO):.2f}) us after the launch's first start")
     mg = np.isfinite(T[:, :, 5])
-    print(f"  layer_att mergers ({int(mg[0].sum())}): ticket {med(T[:, :, 5] - base, mg):.2f}, outputs written "
+    print(f"  layer_att mergers ({int(mg[0].sum())}): saw the records' count {med(T[:, :, 5] - base, mg):.2f}, outputs written "
           f"{med(T[:, :, 6] - base, mg):.2f}, end {med(T[:, :, 7] - base, mg):.2f}; chunk compute done (m2->end "
           f"of non-mergers) {med(T[:, :, 7] - base, isA & ~mg):.2f} (last {lastv(T[:, :, 7] - base, isA & ~mg):.2f})")
 # the FFN pair in one launch: gate|up producers (no mark 3), down workgroups (mark 3 = their
