@@ -190,6 +190,34 @@ int mio_hip_llm_generate_batch(mio_hip_llm *m, const int32_t *prompts, const int
                                int32_t allow_hi, int32_t eos0, int32_t eos1, int32_t check_interval,
                                int32_t *out_tokens, int32_t *n_out);
 
+/* An utterance queue on the batched decode: N >= 1 prompts (concatenated as for
+ * mio_hip_llm_generate_batch) decoded on min(slots, N) streams, 1 <= slots <= 16 under the
+ * rule B follows there. Utterances are admitted in index order; as soon as the host sees, between
+ * two step graphs, that a slot's utterance has stored its end token or spent its budget of
+ * min(max_tokens, n_ctx - len + 1) tokens, the next utterance is prefilled into that slot's
+ * cache and starts there while the other slots keep decoding ("Utterance queue").
+ * Utterance u uses seeds[u]; its tokens go to out_tokens[u * max_tokens ...], n_out[u] of them,
+ * stopping before an end token, and equal mio_hip_llm_generate of its prompt with its seed
+ * exactly, sampler chain included (mio_hip_llm_set_sampling; the penalty history is the
+ * utterance's own). Errors as mio_hip_llm_generate_batch: MIO_ERR_UNSUPPORTED for a slot count
+ * out of range and for BF16 matrices beside quantized ones, MIO_ERR_INVALID for a bad length or
+ * an out-of-vocabulary id in any of the N prompts (checked before anything is queued).
+ * stats may be NULL. Its scalars are written by the call; slot_of / start_step are the caller's
+ * arrays of N ints (each may be NULL). */
+typedef struct mio_llm_queue_stats {
+    int32_t steps;           /* batched decode steps issued */
+    int32_t live_slot_steps; /* sum over utterances of the steps each one sampled (end token
+                              * included): live_slot_steps / (steps * slots) is the occupancy */
+    int32_t refills;         /* admissions into a slot that had held an utterance: N - min(slots, N) */
+    int32_t prefill_chunks;  /* weight passes spent on prompt positions */
+    int32_t *slot_of;        /* [N] in: the array or NULL; out: the slot utterance u ran on */
+    int32_t *start_step;     /* [N] in: the array or NULL; out: `steps` when u was admitted */
+} mio_llm_queue_stats;
+int mio_hip_llm_generate_queue(mio_hip_llm *m, const int32_t *prompts, const int32_t *prompt_lens, int N,
+                               int slots, int max_tokens, float temperature, const uint64_t *seeds,
+                               int32_t allow_lo, int32_t allow_hi, int32_t eos0, int32_t eos1,
+                               int32_t *out_tokens, int32_t *n_out, mio_llm_queue_stats *stats);
+
 /* The sampler chain, on the device ("sampler chain"): per step and stream, over the
  * window [allow_lo, allow_hi),
  *   penalties  for every id among the last repeat_last_n SAMPLED tokens of this generate (prompt
@@ -263,6 +291,10 @@ int mio_hip_llm_conv_ring(mio_hip_llm *m, int il, float *ring, int set);
 /* Wall time (ms) of mio_hip_llm_load: GGUF mmap, re-layout into pinned staging buffers,
  * asynchronous copies into the HBM weight arena (double-buffered). */
 int mio_hip_llm_load_ms(const mio_hip_llm *m, double *ms);
+/* Decode steps per replayed step graph (8; MIO_GRAPH_STEPS in the environment of the process,
+ * read once): the grain at which mio_hip_llm_generate / _generate_batch stop issuing steps and at
+ * which mio_hip_llm_generate_queue refills slots. Returns the count itself, not an error code. */
+int mio_hip_llm_graph_steps(void);
 /* Decode steps (one sampled token each) issued since the last generate began, look-ahead
  * included: generate keeps up to 2 step graphs queued ahead of the GPU, so a run that stops at
  * an end token after n_out tokens issued *steps - n_out - 1 steps for nothing (the rest of the

@@ -134,8 +134,8 @@ public:
                              std::string & out_token_text);
 
     // (extension) several utterances on this device: their LLM decodes run together (one
-    // weight pass per step for all of them, mio_hip_llm_generate_batch, up to 16 at a time),
-    // then each is written as synthesize_to_file writes it (the same bytes: every utterance
+    // weight pass per step for all of them, up to 16 at a time; mio_hip_llm_generate_queue: a
+    // text starts as soon as an earlier one has ended), then each is written as synthesize_to_file writes it (the same bytes: every utterance
     // samples with the seed synthesize_to_file uses)
     bool synthesize_batch_to_files(const VoiceModel & voice,
                                    const std::vector<std::string> & texts,

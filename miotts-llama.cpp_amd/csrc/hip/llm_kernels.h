@@ -185,6 +185,36 @@ bool batch_supported(const LlmDims &d, int B, int lm_type);
 void launch_batch_embed(const LlmDims &d, const QMat &tok_embd, const PrefillBuffers &pb, const BatchBuffers &bb,
                         int B, hipStream_t s);
 
+// The utterance queue on the batched decode (mio_hip_llm_generate_queue): what an admission
+// reads on the device, uploaded once per call.
+struct QueueUtt {
+    int tok_off;  // its prompt in QueueBuffers.tokens
+    int P;        // prompt length - 1: positions [0, P) are prefilled, decoding starts at P
+    int budget;   // sampled tokens at most (max_steps = P + budget)
+    int out_off;  // its output region in QueueBuffers.out: step s goes to out[out_off + s - P]
+    uint32_t seed_lo, seed_hi;
+};
+struct QueueBuffers {
+    const int *tokens;    // every prompt of the queue, concatenated
+    const QueueUtt *utt;  // [N]
+    int *out;             // n_ctx ints of slack (out_off - P stays inside), then the output regions
+    int *host_done;       // [N] mapped host words, one per utterance (SampleCfg.host_done)
+    int *ptok, *ppos, *pseq;  // the flattened prefill lists the admission's chunks read
+};
+// The admissions of one graph boundary: utterance utt[j] into slot slot[j], its P prompt
+// positions at flat[j] of the flattened lists.
+struct QueueRefill {
+    int n;
+    int slot[kBatchMax], utt[kBatchMax], flat[kBatchMax];
+};
+// Before the prefill chunks: the list entries, and (lfm2) the slots' short-conv rings zeroed.
+void launch_queue_refill(const PrefillBuffers &pb, const QueueBuffers &q, const QueueRefill &r, hipStream_t s);
+// After them: the admitted slots' StepState and SampleCfg (base + the table), and the next input
+// of all B slots embedded into pb.x.
+void launch_queue_admit(const LlmDims &d, const QMat &tok_embd, const PrefillBuffers &pb, const BatchBuffers &bb,
+                        SampleCfg *cfg, const SampleCfg &base, const QueueBuffers &q, const QueueRefill &r, int B,
+                        hipStream_t s);
+
 // The launches of a decode step. The numbers are an interface and stay as they are: bench.py,
 // tools/, the tests and the callers of mio_hip_llm_step_kinds / _time_kernel / _trace_kernel
 // pass them as int (the C ABI keeps int). 5 was the final norm, now inside lm_head.

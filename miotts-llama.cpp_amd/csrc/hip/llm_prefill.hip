@@ -998,6 +998,64 @@ __global__ __launch_bounds__(ST) void k_bt_embed(LlmDims d, QMat emb, PrefillBuf
     embed_row<Q3>(emb, bb.st[t].token, d.n_embd, pb.x + (size_t)t * d.n_embd);
 }
 
+// ------------------------------------------------------------------ utterance queue (slot refill)
+// mio_hip_llm_generate_queue admits utterance r.utt[j] into slot r.slot[j] between two step
+// graphs: k_bt_refill, the prefill chunks of the admitted prompts, k_bt_admit, all in stream
+// order behind the steps already queued. Everything they read was uploaded once, at the start of
+// the call (QueueBuffers).
+// k_bt_refill, workgroups (j, 0 .. kRefillY): the (token, position, sequence) entries of the
+// pair's prompt positions [0, P) at r.flat[j] of the flattened prefill lists, and, in an lfm2
+// model, the slot's short-conv rings zeroed, which is what a slot holds before its first
+// utterance (no kernel reads a ring row of a position below 0, k_bt_conv, so this only keeps
+// the previous utterance's B*X rows out of sight altogether).
+constexpr int kRefillY = 8;
+__global__ __launch_bounds__(ST) void k_bt_refill(PrefillBuffers pb, QueueBuffers q, QueueRefill r) {
+    const int j = blockIdx.x, b = r.slot[j], f = r.flat[j];
+    const QueueUtt u = q.utt[r.utt[j]];
+    const int i0 = blockIdx.y * ST + threadIdx.x;
+    for (int p = i0; p < u.P; p += kRefillY * ST) {
+        q.ptok[f + p] = q.tokens[u.tok_off + p];
+        q.ppos[f + p] = p;
+        q.pseq[f + p] = b;
+    }
+    if (pb.ring) {
+        float *ring = pb.ring + (size_t)b * pb.seq_ring;
+        for (size_t e = i0; e < pb.seq_ring; e += kRefillY * ST) ring[e] = 0.0f;
+    }
+}
+
+// k_bt_admit, one workgroup per slot t of all B (after the prefill chunks): an admitted slot gets
+// its utterance's StepState {P, P, last prompt token} and SampleCfg (base = the call's shared
+// parameters; seed, output region, step budget, history start and end-token word from the table);
+// then the input of EVERY slot's next step is embedded, as k_bt_embed does: the prefill chunks
+// overwrote pb.x, where k_bt_sample had left the live slots' next inputs, and a live slot's
+// st.token is the token it sampled last, so its row comes back as it was.
+template <bool Q3>
+__global__ __launch_bounds__(ST) void k_bt_admit(LlmDims d, QMat emb, PrefillBuffers pb, BatchBuffers bb,
+                                                 SampleCfg *cfg, SampleCfg base, QueueBuffers q, QueueRefill r) {
+    const int t = blockIdx.x;
+    int j = 0;
+    while (j < r.n && r.slot[j] != t) ++j;  // block-uniform
+    int tok;
+    if (j < r.n) {
+        const QueueUtt u = q.utt[r.utt[j]];
+        tok = q.tokens[u.tok_off + u.P];
+        if (threadIdx.x == 0) {
+            bb.st[t] = StepState{u.P, u.P, tok, 0, 0};
+            SampleCfg c = base;
+            c.seed_lo = u.seed_lo, c.seed_hi = u.seed_hi;
+            c.out_tokens = q.out + u.out_off - u.P;  // out_tokens[step], step from P on
+            c.max_steps = u.P + u.budget;
+            c.first_step = u.P;
+            c.host_done = q.host_done + r.utt[j];
+            cfg[t] = c;
+        }
+    } else {
+        tok = bb.st[t].token;
+    }
+    embed_row<Q3>(emb, tok, d.n_embd, pb.x + (size_t)t * d.n_embd);
+}
+
 template <int HD>
 void launch_bt_attention(int G, dim3 grid, hipStream_t s, const LlmDims &d, const LayerW &L, _Float16 *kc,
                          _Float16 *vc, const PrefillBuffers &pb, int att_q) {
@@ -1455,6 +1513,18 @@ void launch_batch_embed(const LlmDims &d, const QMat &tok_embd, const PrefillBuf
                         int B, hipStream_t s) {
     hipLaunchKernelGGL(q3_table(tok_embd) ? k_bt_embed<true> : k_bt_embed<false>, dim3(B), dim3(ST), 0, s, d, tok_embd, pb,
                        bb);
+}
+
+void launch_queue_refill(const PrefillBuffers &pb, const QueueBuffers &q, const QueueRefill &r, hipStream_t s) {
+    if (r.n <= 0) return;
+    hipLaunchKernelGGL(k_bt_refill, dim3(r.n, kRefillY), dim3(ST), 0, s, pb, q, r);
+}
+
+void launch_queue_admit(const LlmDims &d, const QMat &tok_embd, const PrefillBuffers &pb, const BatchBuffers &bb,
+                        SampleCfg *cfg, const SampleCfg &base, const QueueBuffers &q, const QueueRefill &r, int B,
+                        hipStream_t s) {
+    hipLaunchKernelGGL(q3_table(tok_embd) ? k_bt_admit<true> : k_bt_admit<false>, dim3(B), dim3(ST), 0, s, d, tok_embd, pb,
+                       bb, cfg, base, q, r);
 }
 
 }  // namespace mio

@@ -525,6 +525,8 @@ extern "C" int mio_hip_llm_prompt_chunks(const mio_hip_llm *m, int *chunks) {
     return MIO_OK;
 }
 
+extern "C" int mio_hip_llm_graph_steps(void) { return graph_steps(); }
+
 extern "C" int mio_hip_llm_steps_issued(const mio_hip_llm *m, int *steps) {
     MIO_REQUIRE(m && steps, MIO_ERR_INVALID, "llm_steps_issued: null");
     *steps = std::max(0, m->steps_issued - (m->n_prompt - 1));

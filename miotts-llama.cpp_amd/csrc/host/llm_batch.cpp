@@ -2,6 +2,7 @@
 // decoded together on the multi-token layers (csrc/hip/llm_prefill.hip), one weight pass per
 // step for all of them.
 #include <algorithm>
+#include <climits>
 #include <cstring>
 #include <vector>
 
@@ -214,6 +215,196 @@ extern "C" int mio_hip_llm_generate_batch(mio_hip_llm *m, const int32_t *prompts
     if (qflag) {
         MIO_HIP_CHECK(hipMemsetAsync(m->pf.qcnt + mio::kQcntFlag, 0, sizeof(int), m->d->stream));
         mio::set_error("llm_generate_batch: the in-launch quantization hand-off wait timed out");
+        return MIO_ERR_HIP;
+    }
+    return MIO_OK;
+}
+
+namespace {
+
+// What one mio_hip_llm_generate_queue call owns on the device, and its per-utterance end-token
+// words. One word per utterance, not per slot: a slot whose budget the host counts as spent may
+// still have its last steps queued, and one of them can store an end-token word after the host
+// has admitted the next utterance there; that store must not land in the new utterance's word.
+// The buffers are sized by the call (N, its prompts, its budgets), so they are allocated and
+// released per call: four allocations and frees, each a device-wide synchronise, once per call
+// and never per refill.
+struct QueueCall {
+    mio::Scratch<int> tokens, out;
+    mio::Scratch<mio::QueueUtt> utt;
+    mio::Pinned<int> done;
+    int *done_dev = nullptr;
+};
+
+// The queue itself (arguments checked, device bound). Work it queued may still be running when
+// it returns an error: the caller drains the stream before the buffers go.
+int queue_run(mio_hip_llm *m, const int32_t *prompts, const int32_t *prompt_lens, const std::vector<int> &off, int N,
+              int S, int max_tokens, const mio::SamplingParams &sp, const uint64_t *seeds, QueueCall &qc,
+              int32_t *out_tokens, int32_t *n_out, mio_llm_queue_stats *stats) {
+    const mio::LlmDims &D = m->dims;
+    auto &bt = m->bt;
+    hipStream_t s = m->d->stream;
+    int rc;
+    // one upload: every prompt, and per utterance where its prompt lies, its seed, its budget
+    // (as llm_begin: a full context ends it after n_ctx - len + 1 tokens) and its output region
+    std::vector<mio::QueueUtt> utt(N);
+    size_t out_ints = (size_t)D.n_ctx;
+    for (int u = 0; u < N; ++u) {
+        const int budget = std::min(max_tokens, D.n_ctx - prompt_lens[u] + 1);
+        utt[u] = mio::QueueUtt{off[u], prompt_lens[u] - 1, budget, (int)out_ints, (uint32_t)seeds[u],
+                               (uint32_t)(seeds[u] >> 32)};
+        out_ints += (size_t)budget;
+    }
+    MIO_REQUIRE(out_ints < ((size_t)1 << 31), MIO_ERR_INVALID,
+                "llm_generate_queue: %d utterances x their budgets overflow", N);
+    MIO_HIP_CHECK(hipMalloc((void **)qc.tokens.put(), (size_t)off[N] * 4));
+    MIO_HIP_CHECK(hipMalloc((void **)qc.utt.put(), (size_t)N * sizeof(mio::QueueUtt)));
+    MIO_HIP_CHECK(hipMalloc((void **)qc.out.put(), out_ints * 4));
+    // coherent, as the handle's own end-token words: the sampler's system-scope store must be
+    // visible to the host while the graphs still run
+    MIO_HIP_CHECK(hipHostMalloc((void **)qc.done.put(), (size_t)N * sizeof(int),
+                                hipHostMallocMapped | hipHostMallocCoherent));
+    MIO_HIP_CHECK(hipHostGetDevicePointer((void **)&qc.done_dev, qc.done.get(), 0));
+    std::memset(qc.done.get(), 0, (size_t)N * sizeof(int));
+    MIO_HIP_CHECK(hipMemcpyAsync(qc.tokens.get(), prompts, (size_t)off[N] * 4, hipMemcpyHostToDevice, s));
+    MIO_HIP_CHECK(
+        hipMemcpyAsync(qc.utt.get(), utt.data(), (size_t)N * sizeof(mio::QueueUtt), hipMemcpyHostToDevice, s));
+    // -1 everywhere: what an utterance did not sample stays -1 (token ids are >= 0)
+    MIO_HIP_CHECK(hipMemsetAsync(qc.out.get(), 0xFF, out_ints * 4, s));
+    const mio::QueueBuffers qb{qc.tokens.get(), qc.utt.get(), qc.out.get(), qc.done_dev, bt.ptok, bt.ppos, bt.pseq};
+    const bool chain = chain_on(sp);
+    const mio::SampleCfg base = sample_cfg(m, sp, 0, nullptr, nullptr, 0);
+
+    // slot b decodes utterance cur[b] (-1: none yet), admitted when `steps` was start[b]
+    std::vector<int> cur(S, -1), start(S, 0);
+    int steps = 0, next = 0, refills = 0, chunks = 0;
+    bool fin[mio::kBatchMax];
+    // graph k's event is run_ev[k % kRunDepth]: the one graph k - kRunDepth recorded, which is the
+    // graph to wait for before k is issued (run_wait / run_mark keep one event per graph, which
+    // here would grow with N)
+    for (int k = 0;;) {
+        if (k >= kRunDepth) MIO_HIP_CHECK(hipEventSynchronize(m->run_ev[k % kRunDepth]));
+        // one look at every slot per boundary: the GPU is still running the graph queued last, so
+        // an end-token word can be stored at any moment, and everything below must decide from
+        // the same picture (a word read again later could end the loop with utterances waiting)
+        for (int b = 0; b < S; ++b)
+            fin[b] = cur[b] < 0 || steps - start[b] >= utt[cur[b]].budget ||
+                     __atomic_load_n(qc.done.get() + cur[b], __ATOMIC_ACQUIRE);
+        // admissions of this graph boundary, in slot order, on the runner's stream: behind every
+        // step already queued, so the slot's old utterance is frozen when they run
+        mio::QueueRefill r{};
+        std::vector<int> fpos;  // the position of every token of the flattened lists (host copy)
+        for (int b = 0; b < S && next < N; ++b) {
+            if (!fin[b]) continue;
+            if (cur[b] >= 0) ++refills;
+            const int u = next++;
+            r.slot[r.n] = b, r.utt[r.n] = u, r.flat[r.n] = (int)fpos.size(), ++r.n;
+            for (int p = 0; p < utt[u].P; ++p) fpos.push_back(p);
+            cur[b] = u, start[b] = steps, fin[b] = false;  // budget >= 1, its word is still 0
+            if (stats && stats->slot_of) stats->slot_of[u] = b;
+            if (stats && stats->start_step) stats->start_step[u] = steps;
+        }
+        if (r.n) {
+            mio::launch_queue_refill(step_pb(m), qb, r, s);
+            const int nf = (int)fpos.size();
+            for (int c0 = 0; c0 < nf; c0 += mio::kPrefillB, ++chunks) {
+                const int nt = std::min(nf - c0, mio::kPrefillB);
+                const int pmax = *std::max_element(fpos.begin() + c0, fpos.begin() + c0 + nt);
+                mio::PrefillBuffers pb = batch_pb(m, bt.ppos + c0, 1, bt.pseq + c0);
+                pb.tokens = bt.ptok;
+                mio::launch_prefill_chunk(D, m->layers.data(), m->n_layer, bt.kc, bt.vc, m->tok, pb, c0, nt,
+                                          pmax / mio::kAttChunk + 1, s);
+            }
+            mio::launch_queue_admit(D, m->tok, step_pb(m), batch_bb(m), bt.cfg, base, qb, r, S, s);
+            MIO_HIP_CHECK(hipGetLastError());
+        }
+        // steps to the next boundary: a graph's worth, or what the longest live budget still takes
+        int left = 0;
+        for (int b = 0; b < S; ++b)
+            if (!fin[b]) left = std::max(left, utt[cur[b]].budget - (steps - start[b]));
+        if (left == 0) {
+            // every slot is finished; with utterances waiting they were all admitted above and are
+            // live, so this is the end only when the queue is empty too
+            if (next >= N) break;
+            continue;
+        }
+        const int n = std::min(graph_steps(), left);
+        if ((rc = run_batch(m, n, chain))) return rc;
+        steps += n;
+        if ((rc = run_mark(m, k % kRunDepth))) return rc;
+        ++k;
+    }
+    std::vector<int32_t> out(out_ints);
+    MIO_HIP_CHECK(hipMemcpyAsync(out.data(), qc.out.get(), out_ints * 4, hipMemcpyDeviceToHost, s));
+    // every slot is frozen now, and its SampleCfg still points at this call's output region and
+    // end-token word, which go when the call returns. Whoever runs a batched step next writes
+    // every slot's cfg first (mio_hip_llm_generate_batch, an admission here); zeroed, the slots
+    // stay frozen (max_steps 0) and name no freed memory whoever comes
+    MIO_HIP_CHECK(hipMemsetAsync(bt.cfg, 0, (size_t)S * sizeof(mio::SampleCfg), s));
+    MIO_HIP_CHECK(hipStreamSynchronize(s));
+    long live = 0;
+    for (int u = 0; u < N; ++u) {
+        const int32_t *t = out.data() + utt[u].out_off;
+        int n = 0, k = 0;
+        while (n < utt[u].budget && t[n] >= 0) ++n;  // sampled, the end token included
+        while (k < n && t[k] != sp.eos0 && t[k] != sp.eos1) ++k;
+        std::memcpy(out_tokens + (size_t)u * max_tokens, t, (size_t)k * 4);
+        n_out[u] = k;
+        live += n;
+    }
+    if (stats) {
+        stats->steps = steps, stats->live_slot_steps = (int32_t)live;
+        stats->refills = refills, stats->prefill_chunks = chunks;
+    }
+    return MIO_OK;
+}
+
+}  // namespace
+
+// An utterance queue on the batched decode: N utterances on min(slots, N) streams, the next one
+// admitted into a slot at the first step-graph boundary after the slot's utterance has ended
+// ("Utterance queue"). Each utterance's tokens equal a single-stream generate with
+// its seed, as mio_hip_llm_generate_batch's streams do.
+extern "C" int mio_hip_llm_generate_queue(mio_hip_llm *m, const int32_t *prompts, const int32_t *prompt_lens, int N,
+                                          int slots, int max_tokens, float temperature, const uint64_t *seeds,
+                                          int32_t allow_lo, int32_t allow_hi, int32_t eos0, int32_t eos1,
+                                          int32_t *out_tokens, int32_t *n_out, mio_llm_queue_stats *stats) {
+    MIO_REQUIRE(m && prompts && prompt_lens && seeds && out_tokens && n_out && N >= 1 && max_tokens >= 1,
+                MIO_ERR_INVALID, "llm_generate_queue: bad args");
+    MIO_REQUIRE(mio::batch_supported(m->dims, slots, m->lm.type), MIO_ERR_UNSUPPORTED,
+                "llm_generate_queue: %d slots not supported (1..%d, lm_head LDS)", slots, mio::kBatchMax);
+    MIO_REQUIRE(m->bf16_mt(), MIO_ERR_UNSUPPORTED,
+                "llm_generate_queue: BF16 weights mixed with quantized ones run on the single-stream decode "
+                "only (mio_hip_llm_generate)");
+    const mio::LlmDims &D = m->dims;
+    std::vector<int> off(N + 1, 0);
+    for (int u = 0; u < N; ++u) {
+        MIO_REQUIRE(prompt_lens[u] >= 1 && prompt_lens[u] <= D.n_ctx, MIO_ERR_INVALID,
+                    "llm_generate_queue: utterance %d: %d prompt tokens exceed n_ctx %d", u, prompt_lens[u], D.n_ctx);
+        MIO_REQUIRE(off[u] <= INT32_MAX - prompt_lens[u], MIO_ERR_INVALID,
+                    "llm_generate_queue: too many prompt tokens");
+        off[u + 1] = off[u] + prompt_lens[u];
+    }
+    for (int i = 0; i < off[N]; ++i)
+        MIO_REQUIRE(prompts[i] >= 0 && prompts[i] < D.n_vocab, MIO_ERR_INVALID,
+                    "llm_generate_queue: token %d out of vocab", prompts[i]);
+    const int S = std::min(slots, N);
+    int rc = mio::bind(m->d);
+    if (rc || (rc = batch_ensure(m, S)) || (rc = reset_tickets(m))) return rc;
+    mio::SamplingParams sp = m->sampling;  // the chain knobs, shared by every utterance
+    sp.temperature = temperature, sp.allow_lo = allow_lo, sp.allow_hi = allow_hi, sp.eos0 = eos0, sp.eos1 = eos1;
+    QueueCall qc;
+    if ((rc = queue_run(m, prompts, prompt_lens, off, N, S, max_tokens, sp, seeds, qc, out_tokens, n_out, stats))) {
+        (void)hipStreamSynchronize(m->d->stream);  // nothing queued outlives the call's buffers
+        return rc;
+    }
+    // the in-launch quantization's bounded wait (launch_mmq_q) raises this flag if a producer's
+    // signal never came: an error instead of tokens computed from stale records
+    int qflag = 0;
+    MIO_HIP_CHECK(hipMemcpy(&qflag, m->pf.qcnt + mio::kQcntFlag, sizeof(int), hipMemcpyDeviceToHost));
+    if (qflag) {
+        MIO_HIP_CHECK(hipMemsetAsync(m->pf.qcnt + mio::kQcntFlag, 0, sizeof(int), m->d->stream));
+        mio::set_error("llm_generate_queue: the in-launch quantization hand-off wait timed out");
         return MIO_ERR_HIP;
     }
     return MIO_OK;

@@ -501,11 +501,16 @@ bool TestToSpeech::synthesize_to_file(const VoiceModel &voice, const std::string
     return synthesize_to_file(voice, text, output_path, Options{});
 }
 
-// Batched synthesis (extension): prompts in groups of up to 16 through the batched decode
-// engine, the group's codec + iSTFT decodes concurrently, then the PCM epilogue per utterance as
-// synthesize_to_file does it.
-// Every stream uses synthesize_to_file's seed, so each file has the bytes a single call writes
-// (mio_hip_llm_generate_batch's streams equal mio_hip_llm_generate of their prompts).
+// Batched synthesis (extension): every prompt through one utterance queue on the batched decode
+// engine (mio_hip_llm_generate_queue, 16 slots: a slot whose utterance has ended takes the next
+// text while the others keep decoding), then, in groups of up to 16, the codec + iSTFT decodes
+// concurrently and the PCM epilogue per utterance as synthesize_to_file does it.
+// Every utterance uses synthesize_to_file's seed, so each file has the bytes a single call writes
+// (the queue's utterances equal mio_hip_llm_generate of their prompts).
+// All texts are tokenized and decoded before the first file is written: a text that does not
+// tokenize fails the call with no file written, and a refusal of the queue call (a model the
+// batched engine does not take, a text longer than the context) sends every text, not only its
+// group of 16, through the one-at-a-time fallback.
 bool TestToSpeech::synthesize_batch_to_files(const VoiceModel &voice, const std::vector<std::string> &texts,
                                              const std::vector<std::string> &output_paths, const Options &options) {
     if (!is_ready() || !voice.is_ready() || texts.size() != output_paths.size()) {
@@ -519,44 +524,46 @@ bool TestToSpeech::synthesize_batch_to_files(const VoiceModel &voice, const std:
             if (!synthesize_to_file(voice, texts[i], output_paths[i], options)) return false;
         return true;
     }
+    if (texts.empty()) return true;
     const float temp = options.temperature >= 0.0f ? options.temperature : config_.temperature;
     const int max_tokens = options.max_tokens > 0 ? options.max_tokens : config_.max_tokens;
     mio::SamplingParams sp;
     sp.temperature = temp, sp.seed = 42, sp.eos0 = I.eos, sp.eos1 = I.im_end;
     if (!I.harness(options, sp)) return false;
     constexpr size_t kGroup = 16;
-    for (size_t g0 = 0; g0 < texts.size(); g0 += kGroup) {
-        const int B = (int)std::min(kGroup, texts.size() - g0);
-        std::vector<int32_t> prompts, lens;
-        for (int b = 0; b < B; ++b) {
-            const std::vector<int32_t> p = I.prompt_tokens(texts[g0 + b]);
-            if (p.empty()) {
-                fprintf(stderr, "TestToSpeech: tokenization failed\n");
-                return false;
-            }
-            prompts.insert(prompts.end(), p.begin(), p.end());
-            lens.push_back((int32_t)p.size());
+    const size_t N = texts.size();
+    std::vector<int32_t> prompts, lens;
+    for (size_t u = 0; u < N; ++u) {
+        const std::vector<int32_t> p = I.prompt_tokens(texts[u]);
+        if (p.empty()) {
+            fprintf(stderr, "TestToSpeech: tokenization failed\n");
+            return false;
         }
-        std::vector<uint64_t> seeds((size_t)B, sp.seed);
-        std::vector<int32_t> toks((size_t)B * max_tokens), n_out((size_t)B);
-        if (mio_hip_llm_generate_batch(I.llm, prompts.data(), lens.data(), B, max_tokens, temp, seeds.data(),
-                                       sp.allow_lo, sp.allow_hi, sp.eos0, sp.eos1, 32, toks.data(),
-                                       n_out.data()) != MIO_OK) {
-            // a model the batched engine does not take (or a failed hand-off): one utterance
-            // at a time, said on stderr so the fallback is visible
-            fprintf(stderr, "TestToSpeech: batched decode unavailable (%s); decoding one utterance at a time\n",
-                    mio_hip_last_error());
-            for (int b = 0; b < B; ++b)
-                if (!synthesize_to_file(voice, texts[g0 + b], output_paths[g0 + b], options)) return false;
-            continue;
-        }
-        // every stream's codes decoded concurrently (mio_hip_codec_decode_pcm_batch: the same
+        prompts.insert(prompts.end(), p.begin(), p.end());
+        lens.push_back((int32_t)p.size());
+    }
+    std::vector<uint64_t> seeds(N, sp.seed);
+    std::vector<int32_t> toks(N * max_tokens), n_out(N);
+    if (mio_hip_llm_generate_queue(I.llm, prompts.data(), lens.data(), (int)N, (int)kGroup, max_tokens, temp,
+                                   seeds.data(), sp.allow_lo, sp.allow_hi, sp.eos0, sp.eos1, toks.data(), n_out.data(),
+                                   nullptr) != MIO_OK) {
+        // a model the batched engine does not take (or a failed hand-off): one utterance
+        // at a time, said on stderr so the fallback is visible
+        fprintf(stderr, "TestToSpeech: batched decode unavailable (%s); decoding one utterance at a time\n",
+                mio_hip_last_error());
+        for (size_t u = 0; u < N; ++u)
+            if (!synthesize_to_file(voice, texts[u], output_paths[u], options)) return false;
+        return true;
+    }
+    for (size_t g0 = 0; g0 < N; g0 += kGroup) {
+        const int B = (int)std::min(kGroup, N - g0);
+        // every utterance's codes decoded concurrently (mio_hip_codec_decode_pcm_batch: the same
         // kernels per utterance, so the PCM is a single decode's), then synthesize_to_file's
         // epilogue (peak normalisation + PCM16 on the device, WAV) per utterance
         std::vector<std::vector<int32_t>> codes((size_t)B);
         for (int b = 0; b < B; ++b) {
             std::string text;
-            for (int i = 0; i < n_out[b]; ++i) text += I.tok.piece(toks[(size_t)b * max_tokens + i]);
+            for (int i = 0; i < n_out[g0 + b]; ++i) text += I.tok.piece(toks[(g0 + b) * max_tokens + i]);
             const std::vector<int> c = parse_speech_tokens(text);
             if (c.empty()) {
                 fprintf(stderr, "TestToSpeech: no speech codes parsed from text\n");

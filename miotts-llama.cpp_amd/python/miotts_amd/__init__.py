@@ -51,6 +51,12 @@ class Sampling(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class QueueStats(ctypes.Structure):
+    """mio_llm_queue_stats (include/mio_hip.h): what mio_hip_llm_generate_queue reports."""
+    _fields_ = [("steps", ctypes.c_int32), ("live_slot_steps", ctypes.c_int32), ("refills", ctypes.c_int32),
+                ("prefill_chunks", ctypes.c_int32), ("slot_of", ctypes.c_void_p), ("start_step", ctypes.c_void_p)]
+
+
 class _Libs:
     """The product library and, behind it, the test-support library: an entry point is looked
     up in libmiotts.so first, then in libmiotts_test.so."""
@@ -193,6 +199,10 @@ def _declare(L: ctypes.CDLL) -> None:
         "mio_hip_llm_generate_batch": (c_int, [_vp, _vp, _vp, c_int, c_int, ctypes.c_float, _vp,
                                                ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                                ctypes.c_int32, ctypes.c_int32, _vp, _vp]),
+        "mio_hip_llm_graph_steps": (c_int, []),
+        "mio_hip_llm_generate_queue": (c_int, [_vp, _vp, _vp, c_int, c_int, c_int, ctypes.c_float, _vp,
+                                               ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                               ctypes.c_int32, _vp, _vp, _vp]),
     }
     for name, (res, args) in sig.items():
         # a library built from an older tree (same-box A/B of MIO_BUILD_DIR builds) may lack
@@ -213,6 +223,11 @@ def check(rc: int) -> None:
 
 def _ptr(a: np.ndarray) -> int:
     return a.ctypes.data
+
+
+def llm_graph_steps() -> int:
+    """Decode steps per replayed step graph (mio_hip_llm_graph_steps)."""
+    return int(lib().mio_hip_llm_graph_steps())
 
 
 def device_count() -> int:
@@ -745,6 +760,29 @@ class Llm:
                                                _ptr(sd), allow[0], allow[1], eos[0], eos[1],
                                                check_interval, _ptr(out), _ptr(n)))
         return [out[b, : n[b]].copy() for b in range(B)]
+
+    def generate_queue(self, prompts, max_tokens: int, temperature: float = 0.8, seeds=None, slots: int = 16,
+                       allow=(-1, -1), eos=(-1, -1)):
+        """N utterances through min(slots, N) streams of the batched decode
+        (mio_hip_llm_generate_queue): a slot whose utterance has ended takes the next one while
+        the others keep decoding; utterance u's tokens equal generate(prompts[u], seed=seeds[u]).
+        Returns (the N token arrays, stats): stats has steps, live_slot_steps, refills,
+        prefill_chunks and, per utterance, slot_of and start_step (lists)."""
+        N = len(prompts)
+        seeds = [42 + u for u in range(N)] if seeds is None else list(seeds)
+        lens = np.array([len(p) for p in prompts], np.int32)
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(p, np.int32) for p in prompts]), np.int32)
+        sd = np.array(seeds, np.uint64)
+        out = np.empty((N, max_tokens), np.int32)
+        n = np.zeros(N, np.int32)
+        slot_of, start = np.full(N, -1, np.int32), np.full(N, -1, np.int32)
+        st = QueueStats(0, 0, 0, 0, _ptr(slot_of), _ptr(start))
+        check(lib().mio_hip_llm_generate_queue(self.h, _ptr(flat), _ptr(lens), N, slots, max_tokens, temperature,
+                                               _ptr(sd), allow[0], allow[1], eos[0], eos[1], _ptr(out), _ptr(n),
+                                               ctypes.byref(st)))
+        stats = {k: int(getattr(st, k)) for k in ("steps", "live_slot_steps", "refills", "prefill_chunks")}
+        stats["slot_of"], stats["start_step"] = [int(v) for v in slot_of], [int(v) for v in start]
+        return [out[u, : n[u]].copy() for u in range(N)], stats
 
 
 GGML_BLOCK = {2: (32, 18), 6: (32, 22), 8: (32, 34), 11: (256, 110), 12: (256, 144), 13: (256, 176), 14: (256, 210),
