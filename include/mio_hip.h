@@ -177,31 +177,21 @@ int mio_hip_llm_generate(mio_hip_llm *m, const int32_t *prompt, int n_prompt, in
                          float temperature, uint64_t seed, int32_t allow_lo, int32_t allow_hi,
                          int32_t eos0, int32_t eos1, int32_t check_interval,
                          int32_t *out_tokens, int *n_out);
-/* B independent run_llm calls (test-to-speech.cpp:94-199, one per utterance in the
- * reference) decoded together on this device: every step streams the weights once for all
- * B streams (1 <= B <= 16). prompts = the B prompts concatenated, prompt_lens[B]; stream b
- * uses seeds[b] and returns its tokens in out_tokens[b * max_tokens ...], n_out[b] of them
- * (stopping before an end token as mio_hip_llm_generate does). Each stream's tokens equal
- * mio_hip_llm_generate of its prompt with its seed. Uses its own KV caches (B x the model's),
- * allocated on first use. MIO_ERR_UNSUPPORTED for BF16 matrices beside quantized ones (all-BF16
- * files, lfm2 ones included, are taken). */
-int mio_hip_llm_generate_batch(mio_hip_llm *m, const int32_t *prompts, const int32_t *prompt_lens, int B,
-                               int max_tokens, float temperature, const uint64_t *seeds, int32_t allow_lo,
-                               int32_t allow_hi, int32_t eos0, int32_t eos1, int32_t check_interval,
-                               int32_t *out_tokens, int32_t *n_out);
-
-/* An utterance queue on the batched decode: N >= 1 prompts (concatenated as for
- * mio_hip_llm_generate_batch) decoded on min(slots, N) streams, 1 <= slots <= 16 under the
- * rule B follows there. Utterances are admitted in index order; as soon as the host sees, between
- * two step graphs, that a slot's utterance has stored its end token or spent its budget of
- * min(max_tokens, n_ctx - len + 1) tokens, the next utterance is prefilled into that slot's
- * cache and starts there while the other slots keep decoding ("Utterance queue").
- * Utterance u uses seeds[u]; its tokens go to out_tokens[u * max_tokens ...], n_out[u] of them,
- * stopping before an end token, and equal mio_hip_llm_generate of its prompt with its seed
- * exactly, sampler chain included (mio_hip_llm_set_sampling; the penalty history is the
- * utterance's own). Errors as mio_hip_llm_generate_batch: MIO_ERR_UNSUPPORTED for a slot count
- * out of range and for BF16 matrices beside quantized ones, MIO_ERR_INVALID for a bad length or
- * an out-of-vocabulary id in any of the N prompts (checked before anything is queued).
+/* The batched decode: N >= 1 independent run_llm calls (test-to-speech.cpp:94-199, one per
+ * utterance in the reference) decoded on min(slots, N) streams of this device, 1 <= slots <= 16
+ * (fewer where the lm_head's LDS holds fewer); every step streams the weights once for all
+ * streams. prompts = the N prompts concatenated, prompt_lens[N]. Utterances are admitted in index
+ * order; as soon as the host sees, between two step graphs, that a slot's utterance has stored
+ * its end token or spent its budget of min(max_tokens, n_ctx - len + 1) tokens, the next
+ * utterance is prefilled into that slot's cache and starts there while the other slots keep
+ * decoding ("Utterance queue"). Utterance u uses seeds[u]; its tokens go to
+ * out_tokens[u * max_tokens ...], n_out[u] of them, stopping before an end token, and equal
+ * mio_hip_llm_generate of its prompt with its seed exactly, sampler chain included
+ * (mio_hip_llm_set_sampling; the penalty history is the utterance's own). Uses its own KV caches
+ * (slots x the model's), allocated on first use. MIO_ERR_UNSUPPORTED for a slot count out of
+ * range and for BF16 matrices beside quantized ones (all-BF16 files, lfm2 ones included, are
+ * taken), MIO_ERR_INVALID for a bad length or an out-of-vocabulary id in any of the N prompts
+ * (checked before anything is queued).
  * stats may be NULL. Its scalars are written by the call; slot_of / start_step are the caller's
  * arrays of N ints (each may be NULL). */
 typedef struct mio_llm_queue_stats {
@@ -217,6 +207,15 @@ int mio_hip_llm_generate_queue(mio_hip_llm *m, const int32_t *prompts, const int
                                int slots, int max_tokens, float temperature, const uint64_t *seeds,
                                int32_t allow_lo, int32_t allow_hi, int32_t eos0, int32_t eos1,
                                int32_t *out_tokens, int32_t *n_out, mio_llm_queue_stats *stats);
+/* B utterances decoded together: mio_hip_llm_generate_queue with N = slots = B and no stats, so
+ * every utterance has a stream of its own from the first step and the call lasts as long as its
+ * longest one. B is the slot count and is refused as one (MIO_ERR_UNSUPPORTED for B = 0 or
+ * B > 16); everything else is as above. check_interval is accepted for ABI compatibility and
+ * unused, as in mio_hip_llm_generate. */
+int mio_hip_llm_generate_batch(mio_hip_llm *m, const int32_t *prompts, const int32_t *prompt_lens, int B,
+                               int max_tokens, float temperature, const uint64_t *seeds, int32_t allow_lo,
+                               int32_t allow_hi, int32_t eos0, int32_t eos1, int32_t check_interval,
+                               int32_t *out_tokens, int32_t *n_out);
 
 /* The sampler chain, on the device ("sampler chain"): per step and stream, over the
  * window [allow_lo, allow_hi),

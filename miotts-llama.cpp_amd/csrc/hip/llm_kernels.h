@@ -164,9 +164,10 @@ void launch_prefill_chunk(const LlmDims &d, const LayerW *layers, int n_layer, _
                           _Float16 *vcache, const QMat &tok_embd, const PrefillBuffers &pb, int p0, int nt,
                           int n_chunks, hipStream_t s);
 
-// Batched decode of B <= kBatchMax utterances (mio_hip_llm_generate_batch): per sequence b,
-// state st[b], sampling cfg[b] (cfg[b].out_tokens = its token ring), logits [B][n_vocab],
-// sampler partials smp [B][lm blocks][2]; the residual streams are pb.x[b].
+// Batched decode of B <= kBatchMax streams: per stream b, state st[b], sampling cfg[b]
+// (cfg[b].out_tokens[step] = where the token of that step goes: the output region of the utterance
+// the stream decodes, QueueBuffers.out), logits [B][n_vocab], sampler partials smp [B][lm blocks][2];
+// the residual streams are pb.x[b].
 struct BatchBuffers {
     StepState *st;
     const SampleCfg *cfg;
@@ -181,12 +182,9 @@ void launch_batch_step(const LlmDims &d, const LayerW *layers, int n_layer, _Flo
                        const BatchBuffers &bb, int B, bool chain, hipStream_t s);
 // B streams fit one batched step (B <= kBatchMax and the lm_head's LDS for its weight type)
 bool batch_supported(const LlmDims &d, int B, int lm_type);
-// Embedding of st[b].token into pb.x[b] for every sequence (decode start).
-void launch_batch_embed(const LlmDims &d, const QMat &tok_embd, const PrefillBuffers &pb, const BatchBuffers &bb,
-                        int B, hipStream_t s);
 
-// The utterance queue on the batched decode (mio_hip_llm_generate_queue): what an admission
-// reads on the device, uploaded once per call.
+// The utterance queue on the batched decode (mio_hip_llm_generate_queue, and _generate_batch with
+// a slot per utterance): what an admission reads on the device, uploaded once per call.
 struct QueueUtt {
     int tok_off;  // its prompt in QueueBuffers.tokens
     int P;        // prompt length - 1: positions [0, P) are prefilled, decoding starts at P

@@ -817,7 +817,7 @@ __global__ __launch_bounds__(MT) void k_pf_ffn_down_q(LlmDims d, QMat down, Pref
     });
 }
 
-// Q3 (here and in k_bt_sample, k_bt_embed): the embedding table is Q3_K (dequant_elem)
+// Q3 (here and in k_bt_sample, k_bt_admit): the embedding table is Q3_K (dequant_elem)
 template <bool Q3>
 __global__ __launch_bounds__(ST) void k_pf_embed(LlmDims d, QMat emb, PrefillBuffers pb, int p0) {
     const int t = blockIdx.x;
@@ -934,8 +934,8 @@ __global__ __launch_bounds__(MT) void k_bt_gumbel(int R, BatchBuffers bb, int nt
 }
 
 // One workgroup per stream b: the lm_head partials -> the sampled token (k_sample's
-// selection rule), the token ring, end-token flag, the next embedding into pb.x[b], and the
-// state advance. A stream whose step budget (cfg.max_steps) is spent, or that sampled an end
+// selection rule), its place in the utterance's output region, end-token flag, the next
+// embedding into pb.x[b], and the state advance. A stream whose step budget (cfg.max_steps) is spent, or that sampled an end
 // token, is frozen: nothing is recorded and its position no longer advances.
 template <bool Q3>
 __global__ __launch_bounds__(ST) void k_bt_sample(LlmDims d, QMat emb, int nblk, PrefillBuffers pb,
@@ -992,15 +992,9 @@ __global__ __launch_bounds__(ST) void k_bt_sample(LlmDims d, QMat emb, int nblk,
     }
 }
 
-template <bool Q3>
-__global__ __launch_bounds__(ST) void k_bt_embed(LlmDims d, QMat emb, PrefillBuffers pb, BatchBuffers bb) {
-    const int t = blockIdx.x;
-    embed_row<Q3>(emb, bb.st[t].token, d.n_embd, pb.x + (size_t)t * d.n_embd);
-}
-
 // ------------------------------------------------------------------ utterance queue (slot refill)
-// mio_hip_llm_generate_queue admits utterance r.utt[j] into slot r.slot[j] between two step
-// graphs: k_bt_refill, the prefill chunks of the admitted prompts, k_bt_admit, all in stream
+// The batched decode's calls (mio_hip_llm_generate_queue, mio_hip_llm_generate_batch) admit
+// utterance r.utt[j] into slot r.slot[j] at the start of a call and between two step graphs: k_bt_refill, the prefill chunks of the admitted prompts, k_bt_admit, all in stream
 // order behind the steps already queued. Everything they read was uploaded once, at the start of
 // the call (QueueBuffers).
 // k_bt_refill, workgroups (j, 0 .. kRefillY): the (token, position, sequence) entries of the
@@ -1027,9 +1021,9 @@ __global__ __launch_bounds__(ST) void k_bt_refill(PrefillBuffers pb, QueueBuffer
 // k_bt_admit, one workgroup per slot t of all B (after the prefill chunks): an admitted slot gets
 // its utterance's StepState {P, P, last prompt token} and SampleCfg (base = the call's shared
 // parameters; seed, output region, step budget, history start and end-token word from the table);
-// then the input of EVERY slot's next step is embedded, as k_bt_embed does: the prefill chunks
-// overwrote pb.x, where k_bt_sample had left the live slots' next inputs, and a live slot's
-// st.token is the token it sampled last, so its row comes back as it was.
+// then the input of EVERY slot's next step is embedded, the row of st.token into pb.x[t]: the
+// prefill chunks overwrote pb.x, where k_bt_sample had left the live slots' next inputs, and a
+// live slot's st.token is the token it sampled last, so its row comes back as it was.
 template <bool Q3>
 __global__ __launch_bounds__(ST) void k_bt_admit(LlmDims d, QMat emb, PrefillBuffers pb, BatchBuffers bb,
                                                  SampleCfg *cfg, SampleCfg base, QueueBuffers q, QueueRefill r) {
@@ -1507,12 +1501,6 @@ void launch_batch_step(const LlmDims &d, const LayerW *layers, int n_layer, _Flo
     if (chain) launch_sample_chain(ChainArgs{bb.logits, (size_t)lm.rows, bb.st, bb.cfg, bb.smp, nblk, nullptr, 0}, B, s);
     hipLaunchKernelGGL(q3_table(tok_embd) ? k_bt_sample<true> : k_bt_sample<false>, dim3(B), dim3(ST), 0, s, d, tok_embd,
                        nblk, pb, bb);
-}
-
-void launch_batch_embed(const LlmDims &d, const QMat &tok_embd, const PrefillBuffers &pb, const BatchBuffers &bb,
-                        int B, hipStream_t s) {
-    hipLaunchKernelGGL(q3_table(tok_embd) ? k_bt_embed<true> : k_bt_embed<false>, dim3(B), dim3(ST), 0, s, d, tok_embd, pb,
-                       bb);
 }
 
 void launch_queue_refill(const PrefillBuffers &pb, const QueueBuffers &q, const QueueRefill &r, hipStream_t s) {

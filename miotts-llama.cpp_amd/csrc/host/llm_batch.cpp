@@ -1,6 +1,7 @@
-// Batched decode engine of the LLM runner (see llm.h, llm_model.h): B independent utterances
+// Batched decode engine of the LLM runner (see llm.h, llm_model.h): independent utterances
 // decoded together on the multi-token layers (csrc/hip/llm_prefill.hip), one weight pass per
-// step for all of them.
+// step for all of them. One engine, the utterance queue (queue_run), behind both entries:
+// mio_hip_llm_generate_batch is the queue with a slot for every utterance.
 #include <algorithm>
 #include <climits>
 #include <cstring>
@@ -37,16 +38,15 @@ int batch_ensure(mio_hip_llm *m, int B) {
     bt.cfg = (mio::SampleCfg *)al((size_t)B * sizeof(mio::SampleCfg));
     bt.logits = (float *)al((size_t)B * D.n_vocab * 4);
     bt.smp = (float *)al((size_t)B * mio::lm_head_blocks(D) * 2 * 4);
-    bt.tokens = (int *)al((size_t)B * D.n_ctx * 4);
     bt.ppos = (int *)al((size_t)B * D.n_ctx * 4);
     bt.pseq = (int *)al((size_t)B * D.n_ctx * 4);
     bt.ptok = (int *)al((size_t)B * D.n_ctx * 4);
     bt.ring = m->buf.ring ? (float *)al(B * batch_seq_ring(m) * 4) : nullptr;
-    if (!bt.kc || !bt.vc || !bt.st || !bt.cfg || !bt.logits || !bt.smp || !bt.tokens || !bt.ppos || !bt.pseq ||
-        !bt.ptok || (m->buf.ring && !bt.ring)) {
+    if (!bt.kc || !bt.vc || !bt.st || !bt.cfg || !bt.logits || !bt.smp || !bt.ppos || !bt.pseq || !bt.ptok ||
+        (m->buf.ring && !bt.ring)) {
         for (void *p : bt.allocs) hipFree(p);
         bt.allocs.clear();
-        mio::set_error("llm_generate_batch: device allocation for %d streams failed", B);
+        mio::set_error("llm batched decode: device allocation for %d streams failed", B);
         return MIO_ERR_OOM;
     }
     bt.B = B;
@@ -101,129 +101,8 @@ int run_batch(mio_hip_llm *m, int n, bool chain) {
     return MIO_OK;
 }
 
-}  // namespace
-
-// B independent utterances decoded together (the reference runs them one after another, one
-// llama_context each: test-to-speech.cpp:94-199 per call). Prompts are concatenated;
-// stream b's sampled tokens go to out_tokens[b * max_tokens ...], n_out[b] of them (up to,
-// not including, an end token). Each stream's tokens equal a single-stream generate with
-// its seed (same kernels' arithmetic per token, same sampler noise).
-extern "C" int mio_hip_llm_generate_batch(mio_hip_llm *m, const int32_t *prompts, const int32_t *prompt_lens, int B,
-                                          int max_tokens, float temperature, const uint64_t *seeds,
-                                          int32_t allow_lo, int32_t allow_hi, int32_t eos0, int32_t eos1,
-                                          int32_t check_interval, int32_t *out_tokens, int32_t *n_out) {
-    MIO_REQUIRE(m && prompts && prompt_lens && seeds && out_tokens && n_out && max_tokens >= 1, MIO_ERR_INVALID,
-                "llm_generate_batch: bad args");
-    MIO_REQUIRE(mio::batch_supported(m->dims, B, m->lm.type), MIO_ERR_UNSUPPORTED,
-                "llm_generate_batch: %d streams not supported (1..%d, lm_head LDS)", B, mio::kBatchMax);
-    MIO_REQUIRE(m->bf16_mt(), MIO_ERR_UNSUPPORTED,
-                "llm_generate_batch: BF16 weights mixed with quantized ones run on the single-stream decode "
-                "only (mio_hip_llm_generate)");
-    const mio::LlmDims &D = m->dims;
-    std::vector<int> off(B + 1, 0);
-    for (int b = 0; b < B; ++b) {
-        MIO_REQUIRE(prompt_lens[b] >= 1 && prompt_lens[b] <= D.n_ctx, MIO_ERR_INVALID,
-                    "llm_generate_batch: stream %d: %d prompt tokens exceed n_ctx %d", b, prompt_lens[b], D.n_ctx);
-        off[b + 1] = off[b] + prompt_lens[b];
-    }
-    for (int i = 0; i < off[B]; ++i)
-        MIO_REQUIRE(prompts[i] >= 0 && prompts[i] < D.n_vocab, MIO_ERR_INVALID,
-                    "llm_generate_batch: token %d out of vocab", prompts[i]);
-    int rc = mio::bind(m->d);
-    if (rc || (rc = batch_ensure(m, B)) || (rc = reset_tickets(m))) return rc;
-    auto &bt = m->bt;
-    hipStream_t s = m->d->stream;
-    // prompt positions [0, P_b) of every stream: one flattened list, kPrefillB tokens per
-    // chunk whatever stream they belong to (one weight pass per chunk)
-    std::vector<int> ftok, fpos, fseq;
-    for (int b = 0; b < B; ++b)
-        for (int p = 0; p + 1 < prompt_lens[b]; ++p) {
-            ftok.push_back(prompts[off[b] + p]);
-            fpos.push_back(p);
-            fseq.push_back(b);
-        }
-    const int nf = (int)ftok.size();
-    if (nf) {
-        MIO_HIP_CHECK(hipMemcpyAsync(bt.ptok, ftok.data(), (size_t)nf * 4, hipMemcpyHostToDevice, s));
-        MIO_HIP_CHECK(hipMemcpyAsync(bt.ppos, fpos.data(), (size_t)nf * 4, hipMemcpyHostToDevice, s));
-        MIO_HIP_CHECK(hipMemcpyAsync(bt.pseq, fseq.data(), (size_t)nf * 4, hipMemcpyHostToDevice, s));
-    }
-    for (int c0 = 0; c0 < nf; c0 += mio::kPrefillB) {
-        const int nt = nf - c0 < mio::kPrefillB ? nf - c0 : mio::kPrefillB;
-        int pmax = 0;
-        for (int t = 0; t < nt; ++t) pmax = std::max(pmax, fpos[c0 + t]);
-        mio::PrefillBuffers pb = batch_pb(m, bt.ppos + c0, 1, bt.pseq + c0);
-        pb.tokens = bt.ptok;
-        mio::launch_prefill_chunk(D, m->layers.data(), m->n_layer, bt.kc, bt.vc, m->tok, pb, c0, nt,
-                                  pmax / mio::kAttChunk + 1, s);
-        MIO_HIP_CHECK(hipGetLastError());
-    }
-    // per-stream state: decoding starts at position P_b = len_b - 1 with the step counter at
-    // P_b (the single-stream generate's sampler stream)
-    mio::SamplingParams sp = m->sampling;  // the chain knobs, shared by every stream
-    sp.temperature = temperature, sp.allow_lo = allow_lo, sp.allow_hi = allow_hi, sp.eos0 = eos0, sp.eos1 = eos1;
-    const bool chain = chain_on(sp);
-    std::vector<mio::StepState> st(B);
-    std::vector<mio::SampleCfg> cf(B);
-    std::vector<int> budget(B);
-    for (int b = 0; b < B; ++b) {
-        const int P = prompt_lens[b] - 1;
-        st[b] = mio::StepState{P, P, prompts[off[b] + P], 0};
-        // as llm_begin: a full context ends the stream after n_ctx - len + 1 tokens
-        budget[b] = std::min(max_tokens, D.n_ctx - prompt_lens[b] + 1);
-        cf[b] = sample_cfg(m, sp, seeds[b], bt.tokens + (size_t)b * D.n_ctx, m->host_done_dev + 1 + b, P + budget[b]);
-        cf[b].first_step = P;  // each stream's own history: the tokens it sampled
-        __atomic_store_n(m->host_done + 1 + b, 0, __ATOMIC_SEQ_CST);
-    }
-    MIO_HIP_CHECK(hipMemcpyAsync(bt.st, st.data(), B * sizeof(mio::StepState), hipMemcpyHostToDevice, s));
-    MIO_HIP_CHECK(hipMemcpyAsync(bt.cfg, cf.data(), B * sizeof(mio::SampleCfg), hipMemcpyHostToDevice, s));
-    mio::launch_batch_embed(D, m->tok, step_pb(m), batch_bb(m), B, s);
-    MIO_HIP_CHECK(hipGetLastError());
-    // graphs of graph_steps() steps, at most kRunDepth queued ahead of the GPU; none issued once
-    // every stream has stored its end token's host word or spent its step budget
-    // (check_interval no longer paces this: r06)
-    (void)check_interval;
-    for (int issued = 0, k = 0; issued < max_tokens; ++k) {
-        if ((rc = run_wait(m, k))) return rc;
-        bool all = true;
-        for (int b = 0; b < B && all; ++b)
-            all = issued >= budget[b] || __atomic_load_n(m->host_done + 1 + b, __ATOMIC_ACQUIRE);
-        if (all) break;
-        const int n = std::min(graph_steps(), max_tokens - issued);
-        if ((rc = run_batch(m, n, chain))) return rc;
-        issued += n;
-        if ((rc = run_mark(m, k))) return rc;
-    }
-    std::vector<mio::StepState> hs(B);
-    MIO_HIP_CHECK(hipMemcpyAsync(hs.data(), bt.st, B * sizeof(mio::StepState), hipMemcpyDeviceToHost, s));
-    MIO_HIP_CHECK(hipStreamSynchronize(s));
-    std::vector<int32_t> ring(max_tokens);
-    for (int b = 0; b < B; ++b) {
-        const int P = prompt_lens[b] - 1;
-        const int n = std::max(0, std::min(hs[b].step - P, max_tokens));
-        if (n) MIO_HIP_CHECK(hipMemcpy(ring.data(), bt.tokens + (size_t)b * D.n_ctx + P, (size_t)n * 4,
-                                       hipMemcpyDeviceToHost));
-        int k = 0;
-        while (k < n && ring[k] != eos0 && ring[k] != eos1) ++k;
-        std::memcpy(out_tokens + (size_t)b * max_tokens, ring.data(), (size_t)k * 4);
-        n_out[b] = k;
-    }
-    // the in-launch quantization's bounded wait (launch_mmq_q) raises this flag if a producer's
-    // signal never came: an error instead of tokens computed from stale records
-    int qflag = 0;
-    MIO_HIP_CHECK(hipMemcpy(&qflag, m->pf.qcnt + mio::kQcntFlag, sizeof(int), hipMemcpyDeviceToHost));
-    if (qflag) {
-        MIO_HIP_CHECK(hipMemsetAsync(m->pf.qcnt + mio::kQcntFlag, 0, sizeof(int), m->d->stream));
-        mio::set_error("llm_generate_batch: the in-launch quantization hand-off wait timed out");
-        return MIO_ERR_HIP;
-    }
-    return MIO_OK;
-}
-
-namespace {
-
-// What one mio_hip_llm_generate_queue call owns on the device, and its per-utterance end-token
-// words. One word per utterance, not per slot: a slot whose budget the host counts as spent may
+// What one call (either entry) owns on the device, and its per-utterance end-token words. One
+// word per utterance, not per slot: a slot whose budget the host counts as spent may
 // still have its last steps queued, and one of them can store an end-token word after the host
 // has admitted the next utterance there; that store must not land in the new utterance's word.
 // The buffers are sized by the call (N, its prompts, its budgets), so they are allocated and
@@ -238,9 +117,9 @@ struct QueueCall {
 
 // The queue itself (arguments checked, device bound). Work it queued may still be running when
 // it returns an error: the caller drains the stream before the buffers go.
-int queue_run(mio_hip_llm *m, const int32_t *prompts, const int32_t *prompt_lens, const std::vector<int> &off, int N,
-              int S, int max_tokens, const mio::SamplingParams &sp, const uint64_t *seeds, QueueCall &qc,
-              int32_t *out_tokens, int32_t *n_out, mio_llm_queue_stats *stats) {
+int queue_run(const char *who, mio_hip_llm *m, const int32_t *prompts, const int32_t *prompt_lens,
+              const std::vector<int> &off, int N, int S, int max_tokens, const mio::SamplingParams &sp,
+              const uint64_t *seeds, QueueCall &qc, int32_t *out_tokens, int32_t *n_out, mio_llm_queue_stats *stats) {
     const mio::LlmDims &D = m->dims;
     auto &bt = m->bt;
     hipStream_t s = m->d->stream;
@@ -255,8 +134,7 @@ int queue_run(mio_hip_llm *m, const int32_t *prompts, const int32_t *prompt_lens
                                (uint32_t)(seeds[u] >> 32)};
         out_ints += (size_t)budget;
     }
-    MIO_REQUIRE(out_ints < ((size_t)1 << 31), MIO_ERR_INVALID,
-                "llm_generate_queue: %d utterances x their budgets overflow", N);
+    MIO_REQUIRE(out_ints < ((size_t)1 << 31), MIO_ERR_INVALID, "%s: %d utterances x their budgets overflow", who, N);
     MIO_HIP_CHECK(hipMalloc((void **)qc.tokens.put(), (size_t)off[N] * 4));
     MIO_HIP_CHECK(hipMalloc((void **)qc.utt.put(), (size_t)N * sizeof(mio::QueueUtt)));
     MIO_HIP_CHECK(hipMalloc((void **)qc.out.put(), out_ints * 4));
@@ -337,9 +215,9 @@ int queue_run(mio_hip_llm *m, const int32_t *prompts, const int32_t *prompt_lens
     std::vector<int32_t> out(out_ints);
     MIO_HIP_CHECK(hipMemcpyAsync(out.data(), qc.out.get(), out_ints * 4, hipMemcpyDeviceToHost, s));
     // every slot is frozen now, and its SampleCfg still points at this call's output region and
-    // end-token word, which go when the call returns. Whoever runs a batched step next writes
-    // every slot's cfg first (mio_hip_llm_generate_batch, an admission here); zeroed, the slots
-    // stay frozen (max_steps 0) and name no freed memory whoever comes
+    // end-token word, which go when the call returns. The next call admits into every slot it
+    // runs, which writes that slot's cfg first; zeroed, the slots stay frozen (max_steps 0) and
+    // name no freed memory whoever comes
     MIO_HIP_CHECK(hipMemsetAsync(bt.cfg, 0, (size_t)S * sizeof(mio::SampleCfg), s));
     MIO_HIP_CHECK(hipStreamSynchronize(s));
     long live = 0;
@@ -359,55 +237,101 @@ int queue_run(mio_hip_llm *m, const int32_t *prompts, const int32_t *prompt_lens
     return MIO_OK;
 }
 
-}  // namespace
-
-// An utterance queue on the batched decode: N utterances on min(slots, N) streams, the next one
-// admitted into a slot at the first step-graph boundary after the slot's utterance has ended
-// ("Utterance queue"). Each utterance's tokens equal a single-stream generate with
-// its seed, as mio_hip_llm_generate_batch's streams do.
-extern "C" int mio_hip_llm_generate_queue(mio_hip_llm *m, const int32_t *prompts, const int32_t *prompt_lens, int N,
-                                          int slots, int max_tokens, float temperature, const uint64_t *seeds,
-                                          int32_t allow_lo, int32_t allow_hi, int32_t eos0, int32_t eos1,
-                                          int32_t *out_tokens, int32_t *n_out, mio_llm_queue_stats *stats) {
-    MIO_REQUIRE(m && prompts && prompt_lens && seeds && out_tokens && n_out && N >= 1 && max_tokens >= 1,
-                MIO_ERR_INVALID, "llm_generate_queue: bad args");
+// What both entries check before anything touches the device (who: the entry's name, for the
+// messages; slots: the streams the batched step would run, checked as the caller gave them).
+// off[u] = where utterance u's prompt starts in `prompts`, off[N] = their total.
+int check_call(const char *who, const mio_hip_llm *m, const int32_t *prompts, const int32_t *prompt_lens, int N,
+               int slots, int max_tokens, const uint64_t *seeds, const int32_t *out_tokens, const int32_t *n_out,
+               std::vector<int> &off) {
+    MIO_REQUIRE(m && prompts && prompt_lens && seeds && out_tokens && n_out && max_tokens >= 1, MIO_ERR_INVALID,
+                "%s: bad args", who);
     MIO_REQUIRE(mio::batch_supported(m->dims, slots, m->lm.type), MIO_ERR_UNSUPPORTED,
-                "llm_generate_queue: %d slots not supported (1..%d, lm_head LDS)", slots, mio::kBatchMax);
+                "%s: %d streams not supported (1..%d, lm_head LDS)", who, slots, mio::kBatchMax);
     MIO_REQUIRE(m->bf16_mt(), MIO_ERR_UNSUPPORTED,
-                "llm_generate_queue: BF16 weights mixed with quantized ones run on the single-stream decode "
-                "only (mio_hip_llm_generate)");
+                "%s: BF16 weights mixed with quantized ones run on the single-stream decode only "
+                "(mio_hip_llm_generate)", who);
     const mio::LlmDims &D = m->dims;
-    std::vector<int> off(N + 1, 0);
+    off.assign(N + 1, 0);
     for (int u = 0; u < N; ++u) {
         MIO_REQUIRE(prompt_lens[u] >= 1 && prompt_lens[u] <= D.n_ctx, MIO_ERR_INVALID,
-                    "llm_generate_queue: utterance %d: %d prompt tokens exceed n_ctx %d", u, prompt_lens[u], D.n_ctx);
-        MIO_REQUIRE(off[u] <= INT32_MAX - prompt_lens[u], MIO_ERR_INVALID,
-                    "llm_generate_queue: too many prompt tokens");
+                    "%s: utterance %d: %d prompt tokens exceed n_ctx %d", who, u, prompt_lens[u], D.n_ctx);
+        MIO_REQUIRE(off[u] <= INT32_MAX - prompt_lens[u], MIO_ERR_INVALID, "%s: too many prompt tokens", who);
         off[u + 1] = off[u] + prompt_lens[u];
     }
     for (int i = 0; i < off[N]; ++i)
-        MIO_REQUIRE(prompts[i] >= 0 && prompts[i] < D.n_vocab, MIO_ERR_INVALID,
-                    "llm_generate_queue: token %d out of vocab", prompts[i]);
-    const int S = std::min(slots, N);
-    int rc = mio::bind(m->d);
-    if (rc || (rc = batch_ensure(m, S)) || (rc = reset_tickets(m))) return rc;
-    mio::SamplingParams sp = m->sampling;  // the chain knobs, shared by every utterance
+        MIO_REQUIRE(prompts[i] >= 0 && prompts[i] < D.n_vocab, MIO_ERR_INVALID, "%s: token %d out of vocab", who,
+                    prompts[i]);
+    return MIO_OK;
+}
+
+// A call's sampler: the handle's chain knobs (mio_hip_llm_set_sampling), shared by every utterance,
+// and the call's own temperature, allowed range and end tokens.
+mio::SamplingParams call_sampling(const mio_hip_llm *m, float temperature, int32_t allow_lo, int32_t allow_hi,
+                                  int32_t eos0, int32_t eos1) {
+    mio::SamplingParams sp = m->sampling;
     sp.temperature = temperature, sp.allow_lo = allow_lo, sp.allow_hi = allow_hi, sp.eos0 = eos0, sp.eos1 = eos1;
-    QueueCall qc;
-    if ((rc = queue_run(m, prompts, prompt_lens, off, N, S, max_tokens, sp, seeds, qc, out_tokens, n_out, stats))) {
-        (void)hipStreamSynchronize(m->d->stream);  // nothing queued outlives the call's buffers
-        return rc;
-    }
-    // the in-launch quantization's bounded wait (launch_mmq_q) raises this flag if a producer's
-    // signal never came: an error instead of tokens computed from stale records
+    return sp;
+}
+
+// End of a call: the in-launch quantization's bounded wait (launch_mmq_q) raises this flag if a
+// producer's signal never came: an error instead of tokens computed from stale records.
+int check_quant_wait(mio_hip_llm *m, const char *who) {
     int qflag = 0;
     MIO_HIP_CHECK(hipMemcpy(&qflag, m->pf.qcnt + mio::kQcntFlag, sizeof(int), hipMemcpyDeviceToHost));
     if (qflag) {
         MIO_HIP_CHECK(hipMemsetAsync(m->pf.qcnt + mio::kQcntFlag, 0, sizeof(int), m->d->stream));
-        mio::set_error("llm_generate_queue: the in-launch quantization hand-off wait timed out");
+        mio::set_error("%s: the in-launch quantization hand-off wait timed out", who);
         return MIO_ERR_HIP;
     }
     return MIO_OK;
+}
+
+// Both entries: N utterances on min(slots, N) streams of the batched decode.
+int generate_on_queue(const char *who, mio_hip_llm *m, const int32_t *prompts, const int32_t *prompt_lens, int N,
+                      int slots, int max_tokens, float temperature, const uint64_t *seeds, int32_t allow_lo,
+                      int32_t allow_hi, int32_t eos0, int32_t eos1, int32_t *out_tokens, int32_t *n_out,
+                      mio_llm_queue_stats *stats) {
+    std::vector<int> off;
+    int rc = check_call(who, m, prompts, prompt_lens, N, slots, max_tokens, seeds, out_tokens, n_out, off);
+    if (rc || (rc = mio::bind(m->d)) || (rc = batch_ensure(m, std::min(slots, N))) || (rc = reset_tickets(m)))
+        return rc;
+    const mio::SamplingParams sp = call_sampling(m, temperature, allow_lo, allow_hi, eos0, eos1);
+    QueueCall qc;
+    if ((rc = queue_run(who, m, prompts, prompt_lens, off, N, m->bt.B, max_tokens, sp, seeds, qc, out_tokens, n_out,
+                        stats))) {
+        (void)hipStreamSynchronize(m->d->stream);  // nothing queued outlives the call's buffers
+        return rc;
+    }
+    return check_quant_wait(m, who);
+}
+
+}  // namespace
+
+// An utterance queue on the batched decode: N utterances on min(slots, N) streams, the next one
+// admitted into a slot at the first step-graph boundary after the slot's utterance has ended
+// ("Utterance queue"). Each utterance's tokens equal a single-stream generate with its
+// seed: the same kernels' arithmetic per token, the same sampler noise. (The reference runs
+// utterances one after another, one llama_context each: test-to-speech.cpp:94-199 per call.)
+extern "C" int mio_hip_llm_generate_queue(mio_hip_llm *m, const int32_t *prompts, const int32_t *prompt_lens, int N,
+                                          int slots, int max_tokens, float temperature, const uint64_t *seeds,
+                                          int32_t allow_lo, int32_t allow_hi, int32_t eos0, int32_t eos1,
+                                          int32_t *out_tokens, int32_t *n_out, mio_llm_queue_stats *stats) {
+    MIO_REQUIRE(N >= 1, MIO_ERR_INVALID, "llm_generate_queue: bad args");
+    return generate_on_queue("llm_generate_queue", m, prompts, prompt_lens, N, slots, max_tokens, temperature, seeds,
+                             allow_lo, allow_hi, eos0, eos1, out_tokens, n_out, stats);
+}
+
+// B utterances decoded together: the queue with as many slots as utterances, so all of them are
+// admitted at its first boundary and nothing is refilled. B itself is what is checked as the
+// slot count: more than the batched step takes is refused, never run on fewer slots.
+// check_interval is unused (the end-token words pace the call).
+extern "C" int mio_hip_llm_generate_batch(mio_hip_llm *m, const int32_t *prompts, const int32_t *prompt_lens, int B,
+                                          int max_tokens, float temperature, const uint64_t *seeds,
+                                          int32_t allow_lo, int32_t allow_hi, int32_t eos0, int32_t eos1,
+                                          int32_t check_interval, int32_t *out_tokens, int32_t *n_out) {
+    (void)check_interval;
+    return generate_on_queue("llm_generate_batch", m, prompts, prompt_lens, B, B, max_tokens, temperature, seeds,
+                             allow_lo, allow_hi, eos0, eos1, out_tokens, n_out, nullptr);
 }
 
 // The launch structure of the batched step, observable: its kernel nodes as a captured graph.

@@ -379,11 +379,11 @@ int carve_buffers(const Load &ld, mio_hip_llm *m, float2 **rope) {
                             hipSuccess &&
                         hipEventCreate(sn.ev.put()) == hipSuccess,
                     MIO_ERR_OOM, "llm_load: pinned host buffers / events failed");
-    MIO_REQUIRE(hipHostMalloc((void **)m->host_done.put(), 64 * sizeof(int),
+    MIO_REQUIRE(hipHostMalloc((void **)m->host_done.put(), sizeof(int),
                               hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess &&
                     hipHostGetDevicePointer((void **)&m->host_done_dev, m->host_done, 0) == hipSuccess,
-                MIO_ERR_OOM, "llm_load: mapped host end-token words failed");
-    std::memset(m->host_done, 0, 64 * sizeof(int));
+                MIO_ERR_OOM, "llm_load: mapped host end-token word failed");
+    std::memset(m->host_done, 0, sizeof(int));
     want(m->d_tokens, m->max_steps);
     want(m->d_force, m->max_steps);
     want(m->d_prompt, n_ctx);

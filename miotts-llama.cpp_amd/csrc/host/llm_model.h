@@ -51,14 +51,13 @@ struct mio_hip_llm {
     int *d_tokens = nullptr, *d_force = nullptr, *d_prompt = nullptr;
     mio::PrefillBuffers pf{};  // batched prompt prefill (kPrefillB tokens per chunk)
     int *d_iota = nullptr;     // 0, 1, ..., n_ctx - 1 (prefill positions; batch stream ids)
-    // batched decode of B utterances (mio_hip_llm_generate_batch), allocated on first use
+    // batched decode on B streams (mio_hip_llm_generate_batch / _queue), allocated on first use
     struct Batch {
         int B = 0;
         _Float16 *kc = nullptr, *vc = nullptr;  // [B][layer][kv head][n_ctx][hd]
         mio::StepState *st = nullptr;
         mio::SampleCfg *cfg = nullptr;
         float *logits = nullptr, *smp = nullptr;
-        int *tokens = nullptr;                  // [B][n_ctx] token rings
         int *ppos = nullptr, *pseq = nullptr, *ptok = nullptr;  // flattened prompt prefill lists
         float *ring = nullptr;  // lfm2: [B][n_layer][kConvSlots][n_embd] short-conv rings
         mio::GraphExec graph, graph_n;
@@ -119,9 +118,9 @@ struct mio_hip_llm {
     // time of the whole intervals queued behind that snapshot
     int eos_snap = -1, tail_steps = 0, tail_timed_steps = 0;
     float tail_ms = 0.0f;
-    // end-token words the samplers store to host memory (pinned, mapped: [0] the single-stream
-    // decode, [1 + b] batched stream b), so the host stops enqueuing steps without a blocking
-    // poll; and one event per step graph of the running generate (flow control: at most
+    // the end-token word the single-stream decode's sampler stores to host memory (pinned, mapped;
+    // a batched call has words of its own, one per utterance), so the host stops enqueuing steps
+    // without a blocking poll; and one event per step graph of the running generate (flow control: at most
     // kRunDepth graphs queued ahead of the GPU; the tail timing)
     mio::Pinned<int> host_done;
     int *host_done_dev = nullptr;

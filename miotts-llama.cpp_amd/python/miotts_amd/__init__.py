@@ -745,17 +745,21 @@ class Llm:
                                          check_interval, _ptr(out), ctypes.byref(n)))
         return out[: n.value]
 
+    @staticmethod
+    def _utterances(prompts, max_tokens, seeds):
+        """What both batched entries take for N prompts: their lengths, the prompts concatenated,
+        the seeds (default 42 + u) and the output arrays [N][max_tokens] and [N]."""
+        N = len(prompts)
+        lens = np.array([len(p) for p in prompts], np.int32)
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(p, np.int32) for p in prompts]), np.int32)
+        sd = np.array([42 + u for u in range(N)] if seeds is None else list(seeds), np.uint64)
+        return N, lens, flat, sd, np.empty((N, max_tokens), np.int32), np.zeros(N, np.int32)
+
     def generate_batch(self, prompts, max_tokens: int, temperature: float = 0.8, seeds=None,
                        allow=(-1, -1), eos=(-1, -1), check_interval: int = 32):
         """B utterances decoded together (mio_hip_llm_generate_batch): one weight pass per
         step for all of them; stream b's tokens equal generate(prompts[b], seed=seeds[b])."""
-        B = len(prompts)
-        seeds = [42 + b for b in range(B)] if seeds is None else list(seeds)
-        lens = np.array([len(p) for p in prompts], np.int32)
-        flat = np.ascontiguousarray(np.concatenate([np.asarray(p, np.int32) for p in prompts]), np.int32)
-        sd = np.array(seeds, np.uint64)
-        out = np.empty((B, max_tokens), np.int32)
-        n = np.zeros(B, np.int32)
+        B, lens, flat, sd, out, n = self._utterances(prompts, max_tokens, seeds)
         check(lib().mio_hip_llm_generate_batch(self.h, _ptr(flat), _ptr(lens), B, max_tokens, temperature,
                                                _ptr(sd), allow[0], allow[1], eos[0], eos[1],
                                                check_interval, _ptr(out), _ptr(n)))
@@ -768,13 +772,7 @@ class Llm:
         the others keep decoding; utterance u's tokens equal generate(prompts[u], seed=seeds[u]).
         Returns (the N token arrays, stats): stats has steps, live_slot_steps, refills,
         prefill_chunks and, per utterance, slot_of and start_step (lists)."""
-        N = len(prompts)
-        seeds = [42 + u for u in range(N)] if seeds is None else list(seeds)
-        lens = np.array([len(p) for p in prompts], np.int32)
-        flat = np.ascontiguousarray(np.concatenate([np.asarray(p, np.int32) for p in prompts]), np.int32)
-        sd = np.array(seeds, np.uint64)
-        out = np.empty((N, max_tokens), np.int32)
-        n = np.zeros(N, np.int32)
+        N, lens, flat, sd, out, n = self._utterances(prompts, max_tokens, seeds)
         slot_of, start = np.full(N, -1, np.int32), np.full(N, -1, np.int32)
         st = QueueStats(0, 0, 0, 0, _ptr(slot_of), _ptr(start))
         check(lib().mio_hip_llm_generate_queue(self.h, _ptr(flat), _ptr(lens), N, slots, max_tokens, temperature,

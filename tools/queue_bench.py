@@ -14,13 +14,15 @@ pairs are timed alternately, queue first in even pairs and groups first in odd o
 around calls that end in a device synchronise. Reported: every pair's two times, the median of
 the per-pair ratios groups / queue (> 1: the queue is faster), the batched steps each way issued
 and the queue's occupancy live_slot_steps / (steps * slots) beside the groups' (the same sum of
-sampled steps over 16 x the steps the four calls issued, i.e. the sum of each group's longest budget
-rounded up to whole step graphs as generate_batch issues them).
+sampled steps over 16 x the steps the four calls issued, i.e. the sum of each group's longest
+budget: a call's last graph issues only what that budget still takes), and a SHA-256 over every
+utterance's tokens as the timed calls return them.
 
   python tools/queue_bench.py [--out profiles/utt_queue/runs.txt]
 
 Needs a GPU; prints the report and writes it to --out. bench.py is not involved."""
 import argparse
+import hashlib
 import os
 import sys
 import tempfile
@@ -34,7 +36,6 @@ import miotts_amd as m  # noqa: E402
 
 N, SLOTS, N_CTX, PAIRS = 64, 16, 512, 5
 BUDGET_LO, BUDGET_HI = 32, 448
-GRAPH_STEPS = m.llm_graph_steps()
 
 
 def main():
@@ -76,21 +77,24 @@ def main():
         assert [len(t) for t in tq] == budgets, "the queue's lengths are not the budgets"
         assert all(np.array_equal(x, y) for x, y in zip(tq, tg)), "queue and groups sampled different tokens"
         live = sum(budgets)
-        gsteps = sum(-(-max(budgets[g0:g0 + SLOTS]) // GRAPH_STEPS) * GRAPH_STEPS for g0 in range(0, N, SLOTS))
+        gsteps = sum(max(budgets[g0:g0 + SLOTS]) for g0 in range(0, N, SLOTS))
         say(f"model: synthetic 1.7B Q4_K_M (preset 3), n_ctx {N_CTX}; {N} utterances, {SLOTS} slots, "
             f"budgets {min(budgets)}..{max(budgets)} (sum {live}), prompt tokens {sum(len(p) for p in prompts)}")
         say(f"queue:  steps {stats['steps']}, refills {stats['refills']}, prefill chunks {stats['prefill_chunks']}, "
             f"occupancy {stats['live_slot_steps'] / (stats['steps'] * SLOTS):.3f}")
         say(f"groups: steps {gsteps}, occupancy {live / (gsteps * SLOTS):.3f}")
-        ratios = []
+        ratios, digest = [], hashlib.sha256()
         for i in range(PAIRS):
             if i % 2 == 0:
-                q, g = queue()[0], groups()[0]
+                (q, tq, _), (g, tg) = queue(), groups()
             else:
-                g, q = groups()[0], queue()[0]
+                (g, tg), (q, tq, _) = groups(), queue()
+            for t in tq + tg:
+                digest.update(np.asarray(t, np.int32).tobytes())
             ratios.append(g / q)
             say(f"pair {i}: queue {q * 1e3:.1f} ms, groups {g * 1e3:.1f} ms, groups / queue {g / q:.3f}")
         say(f"median groups / queue: {float(np.median(ratios)):.3f} (min {min(ratios):.3f}, max {max(ratios):.3f})")
+        say(f"tokens sha256: {digest.hexdigest()}")
         llm.close()
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w", encoding="utf-8") as f:
