@@ -87,6 +87,40 @@ int mio_hip_llm_debug_attention(mio_hip_llm *m, int il, int pos, int which, cons
  * decode steps. reset != 0: the runner's counter reset runs first. */
 int mio_hip_llm_handoff_words(mio_hip_llm *m, int reset, int32_t *words);
 
+/* ---------------- the batched decode's state, read back ----------------
+ * After mio_hip_llm_generate_batch / _generate_queue on the handle: stream-ordered copies on the
+ * runner's stream followed by a synchronise, no launch. Each is MIO_ERR_INVALID before the first
+ * batched call (the batch state is allocated by it). tests/test_llm_batch_logits_gpu.py holds the
+ * batched step's logits and caches to the single-stream decode's bit for bit with them.
+ * *B = the slot count of the batch state; pos / step / token / done [kBatchMax = 16 at most]: every
+ * slot's StepState after the call's last step (pos: where the slot's next token would be decoded,
+ * rows [0, pos) of its caches are written; step: its sampler counter; token: the id sampled last). */
+int mio_hip_llm_batch_state(mio_hip_llm *m, int *B, int32_t *pos, int32_t *step, int32_t *token, int32_t *done);
+/* The logits rows of the last step, logits[B][n_vocab] (mio_hip_llm_logits of the single stream). A
+ * frozen slot (budget spent, end token sampled) keeps being stepped at its last position: its row
+ * is that step's. */
+int mio_hip_llm_batch_logits(mio_hip_llm *m, float *logits);
+/* mio_hip_llm_kv_rows on slot `slot`: f16 bit patterns k, v [n_kv][n_pos][head_dim] of cache rows
+ * [0, n_pos) of layer il. A short-conv layer, or a slot or layer out of range: MIO_ERR_INVALID. */
+int mio_hip_llm_batch_kv_rows(mio_hip_llm *m, int slot, int il, int n_pos, uint16_t *k, uint16_t *v);
+/* mio_hip_llm_conv_ring (get) on slot `slot`: ring[4][n_embd] of the lfm2 short-conv layer il;
+ * an attention layer, or a slot or layer out of range: MIO_ERR_INVALID. */
+int mio_hip_llm_batch_conv_ring(mio_hip_llm *m, int slot, int il, float *ring);
+
+/* How a batched decode step of B streams would run on the loaded model, with nothing launched:
+ * plan[n_layer][*n_sites] (*n_sites = 4: q|k|v or conv-in, O or conv-out, gate|up, down) and
+ * *lm_head, each a code engine | shape << 8 | passes << 16.
+ * engine: 0 kDot4 (streaming rows over act records), 1 kDot4Xpre (the same, RMSNorm + quantize in
+ * the launch), 2 kDot4DownQ (the dot4 down with producer workgroups), 3 kMmq (int8 matrix cores
+ * over act records), 4 kMmqQ (matrix cores with producer workgroups).
+ * shape, for engine 4: the fused kernel the launcher has for the site: 1 q|k|v, 2 gate|up one
+ * workgroup per 16-row tile, 3 gate|up walking its tiles, 4 K-quant down, 5 Q8_0 multi-pass down;
+ * 0: none, the site runs its fall-back (a quantization launch + the engine-3 matmul).
+ * passes: 1, 3 or 6 for the site's reduction length (<= 2048, <= 6144, above).
+ * The decisions are the ones the launches themselves call (LayerRun::plan, mmq_q_shape), under
+ * the process's environment switches. MIO_ERR_UNSUPPORTED where B streams cannot run. */
+int mio_debug_batch_plan(mio_hip_llm *m, int B, int32_t *plan, int *n_sites, int32_t *lm_head);
+
 /* ---------------- the sampler chain on an injected logits row ----------------
  * One launch of the chain kernel (penalties -> top-k -> top-p -> min-p -> draw, mio_hip.h
  * mio_sampling) followed by the flush sampler that takes its token: logits[n_vocab] is the row,

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <vector>
 
 #include "weight_types.h"
 
@@ -182,6 +183,15 @@ void launch_batch_step(const LlmDims &d, const LayerW *layers, int n_layer, _Flo
                        const BatchBuffers &bb, int B, bool chain, hipStream_t s);
 // B streams fit one batched step (B <= kBatchMax and the lm_head's LDS for its weight type)
 bool batch_supported(const LlmDims &d, int B, int lm_type);
+// How a batched step of B streams would run, with nothing launched: per layer four codes (q|k|v or
+// conv-in, O or conv-out, gate|up, down), then one for the lm_head. A code is engine | shape << 8
+// | passes << 16: engine 0 dot4, 1 dot4 quantizing in the launch (xpre), 2 the dot4 down with
+// producers, 3 the matrix cores over act records, 4 the matrix cores with producers; shape = the
+// MmqQShape launch_mmq_q has for an engine-4 site (0: its fall-back, the quantization launch +
+// launch_mmq); passes = pick_np of the site's K. The same LayerRun::plan and mmq_q_shape that the
+// launches call decide it. Only pb.qcnt (whether producers exist) is read of pb.
+void batch_step_plan(const LlmDims &d, const LayerW *layers, int n_layer, const QMat &lm, const PrefillBuffers &pb,
+                     int B, std::vector<int> &plan);
 
 // The utterance queue on the batched decode (mio_hip_llm_generate_queue, and _generate_batch with
 // a slot per utterance): what an admission reads on the device, uploaded once per call.

@@ -44,6 +44,20 @@ struct MmqQuant {
     int early = 0;  // set by launch_mmq_q: K-quant tiles issue their weight loads before the wait
 };
 
+// The fused shapes of launch_mmq_q: which kernel with producer workgroups a launch has.
+enum MmqQShape {
+    kQNone = 0,    // none: the quantization launch + launch_mmq
+    kQQkv,         // q|k|v, RMSNorm input, one pass (K-quant pairs, Q8_0 over whole superblocks)
+    kQGateUp,      // gate|up, RMSNorm input, one pass, one workgroup per 16-row tile
+    kQGateUpWalk,  // the same with more tiles than CUs: the workgroups walk the tiles
+    kQDownKq,      // K-quant down, plain h rows of 3 passes
+    kQDownQ8,      // Q8_0 down, plain h rows of 3 or 6 passes (the multi-pass pair path)
+};
+// The shape launch_mmq_q launches for these segments (types as for launch_mmq), epilogue `mode`,
+// reduction length K, nt tokens and producer input qmode (MmqQuant::mode as the caller sets it: 0
+// RMSNorm, 1 plain rows). The launcher itself decides by this; nothing is launched here.
+MmqQShape mmq_q_shape(const MmqSeg *seg, const int *types, int nseg, int mode, int K, int nt, int qmode);
+
 int mmq_tiles(int rows);
 // Segments 0..nseg-1 (types: ggml ids 8 / 12 / 14; with 3 segments, 0 and 1 share a type).
 void launch_mmq(const MmqSeg *seg, const int *types, int nseg, int mode, const MmqArgs &a, hipStream_t s);

@@ -1654,18 +1654,53 @@ void launch_mmq(const MmqSeg *seg, const int *types, int nseg, int mode, const M
     else no_kernel("matmul", types[0], a.K);
 }
 
+// Does a K-quant q|k type QK with attn_v of type V have a fused q|k|v kernel: the pairs of
+// kQkvTypes, but for Q4_K v beside Q6_K q|k, which no file type mixes so
+static constexpr bool qkv_fused_pair(int QK, int V) { return is_kquant(QK) && !(QK == GGML_Q6_K && V == GGML_Q4_K); }
+
+static int tiles16(const MmqSeg *seg, int nseg) {
+    int tiles = 0;
+    for (int i = 0; i < nseg; ++i) tiles += (seg[i].w.rows + RT16 - 1) / RT16;
+    return tiles;
+}
+
 // The fused shapes of the batched decode (launch_layers), each with what routes to it by
-// default at <= 8 streams. Anything else: false.
+// default at <= 8 streams. Anything else: kQNone.
+MmqQShape mmq_q_shape(const MmqSeg *seg, const int *types, int nseg, int mode, int K, int nt, int qmode) {
+    if (nt > TT16) return kQNone;
+    const int np = pick_np(K), T = types[0];
+    const bool q8_one_pass = T == GGML_Q8_0 && K % 256 == 0 && K <= 2048;
+    if (mode == MMQ_STORE && nseg == 3 && qmode == 0 && np == 1 && types[1] == T) {
+        // q|k|v (RMSNorm input, one pass): the K-quant pairs, and Q8_0 models whose n_embd is a
+        // multiple of 256 up to 2048 (the others keep q|k|v on the dot4 engine, quantizing in
+        // that launch)
+        const bool kq = for_qkv_types([&]<int QK, int V>() { return qkv_fused_pair(QK, V) && T == QK && types[2] == V; });
+        if (kq || (q8_one_pass && types[2] == GGML_Q8_0)) return kQQkv;
+    }
+    if (mode == MMQ_SWIGLU && nseg == 1 && qmode == 0 && np == 1 && (is_kquant(T) || q8_one_pass)) {
+        // gate|up (RMSNorm input, one pass): every K-quant model, and Q8_0 where both of the
+        // model's one-pass pair conditions hold (launch_layers' use_mmq). More tiles than the CUs
+        // the producers leave (they keep CUs of their own): the walk
+        return walks(T, K, tiles16(seg, nseg), n_cu() - nt, 2) ? kQGateUpWalk : kQGateUp;
+    }
+    if (mode == MMQ_RESID && nseg == 1 && qmode == 1) {
+        // down (plain h rows): every K-quant model of 3 passes; Q8_0 (multi-pass pair path) at 9 to
+        // 16 streams, or with MIO_MMQ=1 (up to 8 it stays on the dot4 engine: 2.010 vs 1.984 ms and
+        // 171.2 vs 179.4x with it here)
+        if (np == 3 && is_kquant(T)) return kQDownKq;
+        if (T == GGML_Q8_0 && K % 256 == 0 && K > 2048 && (np == 3 || np == 6)) return kQDownQ8;
+    }
+    return kQNone;
+}
+
 bool launch_mmq_q(const MmqSeg *seg, const int *types, int nseg, int mode, const MmqArgs &a, const MmqQuant &q,
                   hipStream_t s) {
-    if (a.nt > TT16) return false;
+    const MmqQShape shape = mmq_q_shape(seg, types, nseg, mode, a.K, a.nt, q.mode);
+    if (shape == kQNone) return false;
     MmqSeg sg[3] = {seg[0], nseg > 1 ? seg[1] : MmqSeg{}, nseg > 2 ? seg[2] : MmqSeg{}};
-    int tiles = 0;
+    const int tiles = tiles16(seg, nseg);
     size_t lds = act_bytes(a.K) + smem_bytes(a.K);  // the producers' record + scratch
-    for (int i = 0; i < nseg; ++i) {
-        tiles += (sg[i].w.rows + RT16 - 1) / RT16;
-        lds = std::max(lds, mmq16_lds(types[i], a.K, mode));
-    }
+    for (int i = 0; i < nseg; ++i) lds = std::max(lds, mmq16_lds(types[i], a.K, mode));
     const MmqSwitches &sw = switches();
     // k_mmq16's producer count: per (token, 2048-element chunk) for plain rows (q.mode 1)
     MmqQuant qq = q;
@@ -1676,53 +1711,37 @@ bool launch_mmq_q(const MmqSeg *seg, const int *types, int nseg, int mode, const
         launch_tiles(kern, dim3(nq + tiles), lds, s, sg[0], sg[1], sg[2], a, qq);
         return true;
     };
-    const int np = pick_np(a.K), T = types[0];
-    const bool q8_one_pass = T == GGML_Q8_0 && a.K % 256 == 0 && a.K <= 2048;
-    if (mode == MMQ_STORE && nseg == 3 && q.mode == 0 && np == 1 && types[1] == T) {
-        // q|k|v (RMSNorm input, one pass): the K-quant pairs of kQkvTypes, but for Q4_K v beside
-        // Q6_K q|k, which no file type mixes so and which has no fused shape
+    const int T = types[0];
+    if (shape == kQQkv) {
         const bool hit = for_qkv_types([&]<int QK, int V>() {
-            if constexpr (is_kquant(QK) && !(QK == GGML_Q6_K && V == GGML_Q4_K)) {
+            if constexpr (qkv_fused_pair(QK, V)) {
                 if (T == QK && types[2] == V) return go(k_mmq16<QK, QK, V, MMQ_STORE, 0, 1, 0>);
             }
             return false;
         });
-        if (hit) return true;
-        // Q8_0 models whose n_embd is a multiple of 256 up to 2048 (the others keep q|k|v on the
-        // dot4 engine, quantizing in that launch)
-        if (q8_one_pass && types[2] == GGML_Q8_0) return go(k_mmq16<GGML_Q8_0, GGML_Q8_0, GGML_Q8_0, MMQ_STORE, 1, 1, 0>);
+        return hit || go(k_mmq16<GGML_Q8_0, GGML_Q8_0, GGML_Q8_0, MMQ_STORE, 1, 1, 0>);
     }
-    if (mode == MMQ_SWIGLU && nseg == 1 && q.mode == 0 && np == 1) {
-        // gate|up (RMSNorm input, one pass): every K-quant model, and Q8_0 where both of the
-        // model's one-pass pair conditions hold (launch_layers' use_mmq). More tiles than the CUs
-        // the producers leave: the walk. The tokens are quantized behind producer workgroups: the
-        // walk quantizing its <= 8 tokens in its own prologue measured 8 streams 1.7B 1.366 vs
-        // 1.252 ms per step (profiles/r06/bt_iq_ab.txt): one wave per token quantizing 8
-        // superblocks in a row is a longer chain than the producers' hop
-        const int nl = n_cu() - a.nt;  // the producers keep CUs of their own
+    if (shape == kQGateUp || shape == kQGateUpWalk) {
+        // The tokens are quantized behind producer workgroups: the walk quantizing its <= 8
+        // tokens in its own prologue measured 8 streams 1.7B 1.366 vs 1.252 ms per step
+        // (profiles/r06/bt_iq_ab.txt): one wave per token quantizing 8 superblocks in a row is a
+        // longer chain than the producers' hop
+        const bool w = shape == kQGateUpWalk;
         auto walk = [&](auto kern) {
-            launch_walk(kern, a.nt + nl, lds, s, sg[0], a, q, tiles);
+            launch_walk(kern, n_cu(), lds, s, sg[0], a, q, tiles);  // nt producers + the CUs they leave
             return true;
         };
-        const bool w = walks(T, a.K, tiles, nl, 2);
         auto kq_up = [&]<int TK>() {
             if (w) walk(k_mmq16_loop_kq<TK, MMQ_SWIGLU, 1, 0>);
             else go(k_mmq16<TK, -1, -1, MMQ_SWIGLU, 0, 1, 0>);
         };
         if (dispatch_kquant(T, kq_up)) return true;
-        if (q8_one_pass) return w ? walk(k_mmq16_loop<MMQ_SWIGLU, 1, 0>) : go(k_mmq16<GGML_Q8_0, -1, -1, MMQ_SWIGLU, 1, 1, 0>);
+        return w ? walk(k_mmq16_loop<MMQ_SWIGLU, 1, 0>) : go(k_mmq16<GGML_Q8_0, -1, -1, MMQ_SWIGLU, 1, 1, 0>);
     }
-    if (mode == MMQ_RESID && nseg == 1 && q.mode == 1 && np == 3) {
-        // down (plain h rows of 3 passes): every K-quant model
-        if (dispatch_kquant(T, [&]<int TK>() { go(k_mmq16<TK, -1, -1, MMQ_RESID, 0, 3, 1>); })) return true;
-    }
-    // Q8_0 down (multi-pass pair path): at 9 to 16 streams, or with MIO_MMQ=1 (up to 8 it stays on
-    // the dot4 engine: 2.010 vs 1.984 ms and 171.2 vs 179.4x with it here)
-    if (mode == MMQ_RESID && nseg == 1 && q.mode == 1 && T == GGML_Q8_0 && a.K % 256 == 0 && a.K > 2048) {
-        if (np == 3) return go(k_mmq16<GGML_Q8_0, -1, -1, MMQ_RESID, 2, 3, 1>);
-        if (np == 6) return go(k_mmq16<GGML_Q8_0, -1, -1, MMQ_RESID, 2, 6, 1>);
-    }
-    return false;
+    if (shape == kQDownKq) return dispatch_kquant(T, [&]<int TK>() { go(k_mmq16<TK, -1, -1, MMQ_RESID, 0, 3, 1>); });
+    // kQDownQ8
+    if (pick_np(a.K) == 3) return go(k_mmq16<GGML_Q8_0, -1, -1, MMQ_RESID, 2, 3, 1>);
+    return go(k_mmq16<GGML_Q8_0, -1, -1, MMQ_RESID, 2, 6, 1>);
 }
 
 }  // namespace mio

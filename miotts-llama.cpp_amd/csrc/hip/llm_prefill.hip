@@ -942,7 +942,7 @@ __global__ __launch_bounds__(ST) void k_bt_sample(LlmDims d, QMat emb, int nblk,
                                                   BatchBuffers bb) {
     __shared__ float bs_[ST / 64];
     __shared__ int bi_[ST / 64];
-    __shared__ int tok_s;
+    __shared__ int tok_s, live_s;
     const int t = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // the step's last launch: both sets of the in-launch quantization counters start the next
     // step at zero (launch_layers alternates them within a step)
@@ -974,14 +974,20 @@ __global__ __launch_bounds__(ST) void k_bt_sample(LlmDims d, QMat emb, int nblk,
         int tok = bi;
         if (tok == INT_MAX) tok = sc.lo;
         if (sc.force && step < sc.n_force && sc.force[step] >= 0) tok = sc.force[step];
-        tok_s = tok;
+        // a stream whose step budget is spent or that sampled its end token stays frozen
+        // (test-to-speech.cpp:168-170: the reference decodes nothing after the end token); decided
+        // here, by the thread that writes the state below, for the whole workgroup
+        live_s = step < sc.max_steps && !st->done;
+        tok_s = live_s ? tok : st->token;
     }
     lds_barrier();
     const int tok = tok_s;
-    // a stream whose step budget is spent or that sampled its end token stays frozen
-    // (test-to-speech.cpp:168-170: the reference decodes nothing after the end token)
-    const bool live = step < sc.max_steps && !st->done;
-    if (live) embed_row<Q3>(emb, tok, d.n_embd, pb.x + (size_t)t * d.n_embd);
+    const bool live = live_s;
+    // live: the sampled token's row is the next step's input. Frozen: the row of the token it
+    // sampled last, again: the layers left their output in pb.x[t], and the next step repeats
+    // (token, pos) on the same input instead of on that residual, so a slot whose budget is spent
+    // holds the logits of its last token however many steps follow
+    embed_row<Q3>(emb, tok, d.n_embd, pb.x + (size_t)t * d.n_embd);
     if (tid == 0 && live) {
         sc.out_tokens[step] = tok;
         if (tok == sc.eos0 || tok == sc.eos1) st->done = 1, signal_host_done(sc);
@@ -1199,6 +1205,8 @@ enum Engine {
     kMmqQ,       // int8 matrix cores with producer workgroups (launch_mmq_q); a shape without a
                  // fused kernel falls back to kMmq
 };
+// What batch_step_plan reports per site (llm_kernels.h): engine | fused shape << 8 | passes << 16
+constexpr int plan_code(Engine e, int shape, int np) { return (int)e | shape << 8 | np << 16; }
 struct Plan {
     Engine engine;
     bool quant_launch;  // a k_bt_quant launch writes the act records first (kMmqQ: on its fall-back)
@@ -1226,6 +1234,8 @@ struct LayerRun {
     hipStream_t s;
     const LayerSwitches &sw = switches();
     int set = 0;  // the producer counter set of the next fused launch
+    // not null: nothing is launched; run() appends the site's plan_code instead (batch_step_plan)
+    std::vector<int> *report = nullptr;
 
     bool mmq_all() const { return sw.mmq >= 0 ? sw.mmq != 0 : nt > 8; }
     // producer workgroups exist in the batched decode only (the counters are the step's)
@@ -1288,11 +1298,14 @@ struct LayerRun {
         launch_quant(d, st.in == kInNorm ? 0 : 1, st.src, st.K, st.norm_w, akind(st.w[0].type), pb, nt, s);
     }
 
+    // the producers' input mode of the site (MmqQuant::mode): 0 RMSNorm, 1 plain rows
+    static int qmode(const Site &st) { return st.in == kInNorm ? 0 : 1; }
+
     // f(MmqQuant of the current counter set) launches a kernel with producer workgroups for the
     // site's input, or returns false; the sets alternate per such launch.
     template <class F>
     bool with_producers(const Site &st, F &&f) {
-        const MmqQuant q{st.src, st.norm_w, st.in == kInNorm ? 0 : 1, d.eps, pb.qcnt + 512 * set,
+        const MmqQuant q{st.src, st.norm_w, qmode(st), d.eps, pb.qcnt + 512 * set,
                          pb.qcnt + 512 * (1 - set), pb.qcnt + kQcntFlag};
         if (!f(q)) return false;
         set ^= 1;
@@ -1381,6 +1394,11 @@ struct LayerRun {
             sg[i] = {st.w[i], mmq_tiles(st.w[i].rows), off};
             ty[i] = st.w[i].type;
         }
+        if (report) {
+            const int shape = p.engine == kMmqQ ? mmq_q_shape(sg, ty, st.nseg, st.epi, st.K, nt, qmode(st)) : kQNone;
+            report->push_back(plan_code(p.engine, shape, pick_np(st.K)));
+            return;
+        }
         const MmqArgs a{pb.act, act_bytes(st.K), st.K, nt, st.out, st.ld, st.up};
         if (p.engine == kMmqQ &&
             with_producers(st, [&](const MmqQuant &q) { return launch_mmq_q(sg, ty, st.nseg, st.epi, a, q, s); }))
@@ -1398,6 +1416,7 @@ struct LayerRun {
     // RoPE + K/V rows + attention of nt tokens; the merger writes pb.att and, with att_q >= 0,
     // the O matvec's act records. decode: all inside k_bt_attention, per token.
     void attention(const LayerW &L, _Float16 *kc, _Float16 *vc, int n_chunks, int att_q) const {
+        if (report) return;
         const int G = d.n_head / d.n_kv;
         const dim3 grid(d.n_kv * nt, n_chunks);
         dispatch_hd(d.hd, [&]<int HD>() {
@@ -1411,6 +1430,7 @@ struct LayerRun {
     // lfm2: the gated short conv between in_proj and out_proj, writing out_proj's act records,
     // then the ring update
     void conv(const LayerW &L, float *ring) const {
+        if (report) return;
         const int ak = akind(L.out_proj.type);
         dispatch_np(d.n_embd, [&]<int NP>() {
             hipLaunchKernelGGL((k_bt_conv<NP>), dim3(nt), dim3(MT), smem_bytes(d.n_embd), s, d, L.conv_w, ring, ak, pb);
@@ -1422,8 +1442,10 @@ struct LayerRun {
 // Every layer for nt tokens of pb (residual streams pb.x in, out): one weight pass per matvec
 // site (sub-launches only where a token range does not fit LDS).
 void launch_layers(const LlmDims &d, const LayerW *layers, int n_layer, _Float16 *kcache, _Float16 *vcache,
-                   const PrefillBuffers &pb, int nt, int n_chunks, bool decode, hipStream_t s) {
+                   const PrefillBuffers &pb, int nt, int n_chunks, bool decode, hipStream_t s,
+                   std::vector<int> *report = nullptr) {
     LayerRun r{d, pb, nt, decode, s};
+    r.report = report;
     const size_t layer_kv = (size_t)d.n_kv * d.n_ctx * d.hd;
     const int n = d.n_embd, QD = (d.n_head + 2 * d.n_kv) * d.hd;
     for (int il = 0; il < n_layer; ++il) {
@@ -1481,12 +1503,27 @@ bool batch_supported(const LlmDims &d, int B, int lm_type) {
     return B >= 1 && B <= kBatchMax && batch_lm_head_lds(d, B, lm_type) <= (size_t)LDS_DYN_MAX;
 }
 
+namespace {
+// the batched lm_head as a site: RMSNorm(x) * out_norm through lm into the logits rows
+Site lm_head_site(const LlmDims &d, const QMat &lm, const float *out_norm, const PrefillBuffers &pb, float *logits) {
+    return {kSiteLmHead, {lm}, 1, {}, d.n_embd, kInNorm, pb.x, out_norm, MMQ_STORE, logits, lm.rows, 0};
+}
+}  // namespace
+
+void batch_step_plan(const LlmDims &d, const LayerW *layers, int n_layer, const QMat &lm, const PrefillBuffers &pb,
+                     int B, std::vector<int> &plan) {
+    plan.clear();
+    launch_layers(d, layers, n_layer, nullptr, nullptr, pb, B, d.max_splits, true, nullptr, &plan);
+    const LayerRun r{d, pb, B, true, nullptr};
+    plan.push_back(plan_code(r.plan(lm_head_site(d, lm, nullptr, pb, nullptr)).engine, kQNone, pick_np(d.n_embd)));
+}
+
 void launch_batch_step(const LlmDims &d, const LayerW *layers, int n_layer, _Float16 *kcache, _Float16 *vcache,
                        const float *out_norm, const QMat &lm, const QMat &tok_embd, const PrefillBuffers &pb,
                        const BatchBuffers &bb, int B, bool chain, hipStream_t s) {
     launch_layers(d, layers, n_layer, kcache, vcache, pb, B, d.max_splits, true, s);
     LayerRun r{d, pb, B, true, s};
-    const Site head{kSiteLmHead, {lm}, 1, {}, d.n_embd, kInNorm, pb.x, out_norm, MMQ_STORE, bb.logits, lm.rows, 0};
+    const Site head = lm_head_site(d, lm, out_norm, pb, bb.logits);
     const int nblk = matvec_grid(d, d.n_vocab);  // the batched lm_head keeps one workgroup per CU
     if (r.plan(head).engine == kMmq) {
         // the logits on the matrix cores, then the sampling partials from them

@@ -61,4 +61,16 @@ int llm_debug_sample_chain(mio_hip_llm *m, const float *logits, const int32_t *h
                            const SamplingParams &sp, int step, int32_t *token, int32_t *kept, int32_t *cut_id,
                            float *penalised);
 
+// Read-back of the batched decode's state after the last batched call on the handle (stream-ordered
+// copies and a synchronise, no launch; MIO_ERR_INVALID before any batched call): the slot count and
+// every slot's StepState fields; the logits rows [B][n_vocab]; slot `slot`'s cache rows [0, n_pos)
+// of layer il as [n_kv][n_pos][head_dim] (llm_kv_rows of a slot); its short-conv ring of layer il.
+int llm_batch_state(mio_hip_llm *m, int *B, int32_t *pos, int32_t *step, int32_t *token, int32_t *done);
+int llm_batch_logits(mio_hip_llm *m, float *logits);
+int llm_batch_kv_rows(mio_hip_llm *m, int slot, int il, int n_pos, uint16_t *k, uint16_t *v);
+int llm_batch_conv_ring(mio_hip_llm *m, int slot, int il, float *ring);
+// The engines a batched step of B streams would run per layer and site, plan[n_layer][*n_sites],
+// and the lm_head's (batch_step_plan's codes, llm_kernels.h). Launches nothing.
+int llm_batch_plan(mio_hip_llm *m, int B, int32_t *plan, int *n_sites, int32_t *lm_head);
+
 }  // namespace mio

@@ -2,6 +2,7 @@
 // llm_model.h; include/mio_hip.h, include/mio_hip_test.h). No product path calls these.
 #include <algorithm>
 #include <cstring>
+#include <vector>
 
 #include "gguf.h"
 #include "llm_model.h"
@@ -212,6 +213,91 @@ int mio::llm_debug_sample_chain(mio_hip_llm *m, const float *logits, const int32
     rc = run();
     hipFree(dbg);
     return rc;
+}
+
+// ---- read-back of the batched decode's state (parity tests): stream-ordered copies on the
+// runner's stream and a synchronise, no launch ----
+
+// The slot count of the batch state and every slot's StepState fields after the last batched call.
+int mio::llm_batch_state(mio_hip_llm *m, int *B, int32_t *pos, int32_t *step, int32_t *token, int32_t *done) {
+    MIO_REQUIRE(m && B && pos && step && token && done, MIO_ERR_INVALID, "llm_batch_state: null argument");
+    MIO_REQUIRE(m->bt.B > 0, MIO_ERR_INVALID, "llm_batch_state: no batched call has run on this handle");
+    int rc = mio::bind(m->d);
+    if (rc) return rc;
+    std::vector<mio::StepState> st(m->bt.B);
+    MIO_HIP_CHECK(hipMemcpyAsync(st.data(), m->bt.st, st.size() * sizeof(mio::StepState), hipMemcpyDeviceToHost,
+                                 m->d->stream));
+    MIO_HIP_CHECK(hipStreamSynchronize(m->d->stream));
+    *B = m->bt.B;
+    for (int b = 0; b < m->bt.B; ++b) pos[b] = st[b].pos, step[b] = st[b].step, token[b] = st[b].token, done[b] = st[b].done;
+    return MIO_OK;
+}
+
+// The batched step's logits rows [B][n_vocab] (mio_hip_llm_logits of the single stream).
+int mio::llm_batch_logits(mio_hip_llm *m, float *logits) {
+    MIO_REQUIRE(m && logits, MIO_ERR_INVALID, "llm_batch_logits: null argument");
+    MIO_REQUIRE(m->bt.B > 0, MIO_ERR_INVALID, "llm_batch_logits: no batched call has run on this handle");
+    int rc = mio::bind(m->d);
+    if (rc) return rc;
+    MIO_HIP_CHECK(hipMemcpyAsync(logits, m->bt.logits, (size_t)m->bt.B * m->dims.n_vocab * 4, hipMemcpyDeviceToHost,
+                                 m->d->stream));
+    MIO_HIP_CHECK(hipStreamSynchronize(m->d->stream));
+    return MIO_OK;
+}
+
+// mio_hip_llm_kv_rows on slot `slot` of the batch caches: rows [0, n_pos) of layer il as
+// [n_kv][n_pos][head_dim].
+int mio::llm_batch_kv_rows(mio_hip_llm *m, int slot, int il, int n_pos, uint16_t *k, uint16_t *v) {
+    MIO_REQUIRE(m && k && v, MIO_ERR_INVALID, "llm_batch_kv_rows: null argument");
+    MIO_REQUIRE(m->bt.B > 0, MIO_ERR_INVALID, "llm_batch_kv_rows: no batched call has run on this handle");
+    MIO_REQUIRE(slot >= 0 && slot < m->bt.B && il >= 0 && il < m->n_layer && n_pos >= 0 && n_pos <= m->dims.n_ctx,
+                MIO_ERR_INVALID, "llm_batch_kv_rows: slot %d / layer %d / %d rows out of range", slot, il, n_pos);
+    MIO_REQUIRE(!m->layers[il].conv, MIO_ERR_INVALID, "llm_batch_kv_rows: layer %d is a short-conv layer", il);
+    int rc = mio::bind(m->d);
+    if (rc) return rc;
+    const mio::LlmDims &D = m->dims;
+    hipStream_t s = m->d->stream;
+    const size_t seq_kv = (size_t)m->n_layer * D.n_kv * D.n_ctx * D.hd;  // batch_pb's seq_kv
+    for (int h = 0; h < D.n_kv && n_pos > 0; ++h) {
+        const size_t src = (size_t)slot * seq_kv + (((size_t)il * D.n_kv + h) * D.n_ctx) * D.hd,
+                     dst = (size_t)h * n_pos * D.hd;
+        MIO_HIP_CHECK(hipMemcpyAsync(k + dst, m->bt.kc + src, (size_t)n_pos * D.hd * 2, hipMemcpyDeviceToHost, s));
+        MIO_HIP_CHECK(hipMemcpyAsync(v + dst, m->bt.vc + src, (size_t)n_pos * D.hd * 2, hipMemcpyDeviceToHost, s));
+    }
+    MIO_HIP_CHECK(hipStreamSynchronize(s));
+    return MIO_OK;
+}
+
+// mio_hip_llm_conv_ring (get) on slot `slot` of the batch rings: [kConvSlots][n_embd] of layer il.
+int mio::llm_batch_conv_ring(mio_hip_llm *m, int slot, int il, float *ring) {
+    MIO_REQUIRE(m && ring, MIO_ERR_INVALID, "llm_batch_conv_ring: null argument");
+    MIO_REQUIRE(m->bt.B > 0, MIO_ERR_INVALID, "llm_batch_conv_ring: no batched call has run on this handle");
+    MIO_REQUIRE(slot >= 0 && slot < m->bt.B && il >= 0 && il < m->n_layer && m->layers[il].conv && m->bt.ring,
+                MIO_ERR_INVALID, "llm_batch_conv_ring: slot %d / layer %d is not a short-conv layer of a slot", slot, il);
+    int rc = mio::bind(m->d);
+    if (rc) return rc;
+    const size_t n = (size_t)mio::kConvSlots * m->dims.n_embd;
+    const float *dr = m->bt.ring + ((size_t)slot * m->n_layer + il) * n;  // [B][n_layer][kConvSlots][n_embd]
+    MIO_HIP_CHECK(hipMemcpyAsync(ring, dr, n * 4, hipMemcpyDeviceToHost, m->d->stream));
+    MIO_HIP_CHECK(hipStreamSynchronize(m->d->stream));
+    return MIO_OK;
+}
+
+// How a batched step of B streams would run on this model (batch_step_plan, llm_kernels.h): host
+// code over the loaded model, nothing launched. plan[n_layer][4], *lm_head the lm_head's code.
+int mio::llm_batch_plan(mio_hip_llm *m, int B, int32_t *plan, int *n_sites, int32_t *lm_head) {
+    MIO_REQUIRE(m && plan && n_sites && lm_head, MIO_ERR_INVALID, "llm_batch_plan: null argument");
+    MIO_REQUIRE(mio::batch_supported(m->dims, B, m->lm.type) && m->bf16_mt(), MIO_ERR_UNSUPPORTED,
+                "llm_batch_plan: %d streams not supported", B);
+    int rc = mio::bind(m->d);  // the tile walks are sized by the current device's CU count
+    if (rc) return rc;
+    std::vector<int> p;
+    mio::batch_step_plan(m->dims, m->layers.data(), m->n_layer, m->lm, m->pf, B, p);
+    MIO_REQUIRE((int)p.size() == 4 * m->n_layer + 1, MIO_ERR_INVALID, "llm_batch_plan: %d codes for %d layers",
+                (int)p.size(), m->n_layer);
+    std::copy(p.begin(), p.end() - 1, plan);
+    *n_sites = 4, *lm_head = p.back();
+    return MIO_OK;
 }
 
 namespace {

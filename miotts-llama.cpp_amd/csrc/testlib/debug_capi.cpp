@@ -204,6 +204,27 @@ extern "C" int mio_hip_llm_handoff_words(mio_hip_llm *m, int reset, int32_t *wor
     return mio::llm_handoff_words(m, reset, words);
 }
 
+// The batched decode's state read back, and its plan: next to the runner's state too
+// (csrc/host/llm_diag.cpp).
+extern "C" int mio_hip_llm_batch_state(mio_hip_llm *m, int *B, int32_t *pos, int32_t *step, int32_t *token,
+                                       int32_t *done) {
+    return mio::llm_batch_state(m, B, pos, step, token, done);
+}
+
+extern "C" int mio_hip_llm_batch_logits(mio_hip_llm *m, float *logits) { return mio::llm_batch_logits(m, logits); }
+
+extern "C" int mio_hip_llm_batch_kv_rows(mio_hip_llm *m, int slot, int il, int n_pos, uint16_t *k, uint16_t *v) {
+    return mio::llm_batch_kv_rows(m, slot, il, n_pos, k, v);
+}
+
+extern "C" int mio_hip_llm_batch_conv_ring(mio_hip_llm *m, int slot, int il, float *ring) {
+    return mio::llm_batch_conv_ring(m, slot, il, ring);
+}
+
+extern "C" int mio_debug_batch_plan(mio_hip_llm *m, int B, int32_t *plan, int *n_sites, int32_t *lm_head) {
+    return mio::llm_batch_plan(m, B, plan, n_sites, lm_head);
+}
+
 extern "C" int mio_hip_llm_debug_sample_chain(mio_hip_llm *m, const float *logits, const int32_t *history,
                                               int n_history, const mio_sampling *s, float temperature, uint64_t seed,
                                               int step, int32_t lo, int32_t hi, int32_t *token, int32_t *kept,

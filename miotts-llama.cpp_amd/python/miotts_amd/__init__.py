@@ -159,6 +159,11 @@ def _declare(L: ctypes.CDLL) -> None:
         "mio_hip_llm_set_kv_rows": (c_int, [_vp, c_int, c_int, c_int, _vp, _vp]),
         "mio_hip_llm_debug_attention": (c_int, [_vp, c_int, c_int, c_int, _vp, _vp]),
         "mio_hip_llm_handoff_words": (c_int, [_vp, c_int, _vp]),
+        "mio_hip_llm_batch_state": (c_int, [_vp, ctypes.POINTER(c_int), _vp, _vp, _vp, _vp]),
+        "mio_hip_llm_batch_logits": (c_int, [_vp, _vp]),
+        "mio_hip_llm_batch_kv_rows": (c_int, [_vp, c_int, c_int, c_int, _vp, _vp]),
+        "mio_hip_llm_batch_conv_ring": (c_int, [_vp, c_int, c_int, _vp]),
+        "mio_debug_batch_plan": (c_int, [_vp, c_int, _vp, ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_int32)]),
         "mio_hip_llm_set_sampling": (c_int, [_vp, ctypes.POINTER(Sampling)]),
         "mio_hip_llm_get_sampling": (c_int, [_vp, ctypes.POINTER(Sampling)]),
         "mio_hip_llm_debug_sample_chain": (c_int, [_vp, _vp, _vp, c_int, ctypes.POINTER(Sampling), ctypes.c_float,
@@ -522,6 +527,11 @@ STEP_KIND_NAMES = {0: "attn_in", 1: "attention", 2: "attn_out", 3: "ffn_in", 4: 
                    14: "sample_chain"}
 
 
+# mio_debug_batch_plan's codes (include/mio_hip_test.h)
+PLAN_ENGINES = {0: "dot4", 1: "dot4_xpre", 2: "dot4_down_q", 3: "mmq", 4: "mmq_q"}
+PLAN_SHAPES = {0: "none", 1: "qkv", 2: "gate_up", 3: "gate_up_walk", 4: "down_kq", 5: "down_q8"}
+
+
 def synth_llm(path: str, preset: int = 0, seed: int = 1) -> str:
     check(lib().mio_synth_llm_gguf(path.encode(), preset, seed))
     return path
@@ -724,6 +734,45 @@ class Llm:
         n = ctypes.c_int(0)
         check(lib().mio_hip_llm_batch_step_launches(self.h, B, ctypes.byref(n)))
         return n.value
+
+    def batch_state(self) -> dict:
+        """Every slot's StepState after the last batched call (test-support library): int32 arrays
+        pos, step, token, done of the batch state's slot count."""
+        B = ctypes.c_int(0)
+        f = {k: np.full(16, -1, np.int32) for k in ("pos", "step", "token", "done")}
+        check(lib().mio_hip_llm_batch_state(self.h, ctypes.byref(B), _ptr(f["pos"]), _ptr(f["step"]),
+                                            _ptr(f["token"]), _ptr(f["done"])))
+        return {k: v[: B.value].copy() for k, v in f.items()}
+
+    def batch_logits(self) -> np.ndarray:
+        """The logits rows [B, n_vocab] of the last batched step (B = the batch state's slot count)."""
+        out = np.empty((len(self.batch_state()["pos"]), self.n_vocab), np.float32)
+        check(lib().mio_hip_llm_batch_logits(self.h, _ptr(out)))
+        return out
+
+    def batch_kv_rows(self, slot: int, il: int, n_pos: int):
+        """kv_rows of slot `slot` of the batched decode's caches: two [n_kv, n_pos, head_dim]."""
+        k = np.empty((self.n_kv, n_pos, self.head_dim), np.float16)
+        v = np.empty_like(k)
+        check(lib().mio_hip_llm_batch_kv_rows(self.h, slot, il, n_pos, _ptr(k), _ptr(v)))
+        return k, v
+
+    def batch_conv_ring(self, slot: int, il: int) -> np.ndarray:
+        """conv_ring of slot `slot` of the batched decode: [4, n_embd] of short-conv layer il."""
+        r = np.empty((4, self.n_embd), np.float32)
+        check(lib().mio_hip_llm_batch_conv_ring(self.h, slot, il, _ptr(r)))
+        return r
+
+    def batch_plan(self, B: int):
+        """How a batched step of B streams would run (mio_debug_batch_plan; nothing is launched):
+        (sites, lm_head), sites[il][j] and lm_head = (engine, fused shape, passes), j = 0 q|k|v or
+        conv-in, 1 O or conv-out, 2 gate|up, 3 down; the numbers are PLAN_ENGINES / PLAN_SHAPES."""
+        plan = np.zeros((self.n_layer, 4), np.int32)
+        ns, lm = ctypes.c_int(0), ctypes.c_int32(0)
+        check(lib().mio_debug_batch_plan(self.h, B, _ptr(plan), ctypes.byref(ns), ctypes.byref(lm)))
+        assert ns.value == 4, ns.value
+        code = lambda c: (int(c) & 0xFF, (int(c) >> 8) & 0xFF, int(c) >> 16)
+        return [[code(c) for c in row] for row in plan], code(lm.value)
 
     def conv_ring(self, il: int, ring=None):
         """lfm2 short-conv state of layer il, [4, n_embd] (slot p & 3 = B*X of position p);
