@@ -441,7 +441,7 @@ __device__ __forceinline__ void x_after_weights_plain(XRegs<XV> &xr) {
 }
 
 // Activation kind of a weight type (ggml's vec_dot_type): 0 Q8_0 (Q8_0 weights), 1 Q8_K
-// (Q3_K / Q4_K / Q5_K / Q6_K), 2 BF16 (BF16 weights: the activation rounded to bf16, ggml_fp32_to_bf16).
+// (Q3_K / Q4_K / Q5_K / Q6_K / IQ4_XS), 2 BF16 (BF16 weights: the activation rounded to bf16, ggml_fp32_to_bf16).
 __host__ __device__ constexpr int akind(int T) { return T == GGML_BF16 ? 2 : (T == GGML_Q8_0 ? 0 : 1); }
 
 // ggml_compute_fp32_to_bf16: round to nearest even, NaN kept quiet
@@ -670,6 +670,8 @@ constexpr uint32_t M4 = 0x0F0F0F0Fu, M2 = 0x03030303u;
 //   Q6_K: a = 16 B of ql, b = 16 B of qh, c = the lane's two int8 sub-block scales, e = d
 //   Q3_K: a.x, a.y = the piece's two runs of 16 2-bit codes, b.x = their 32 high bits, c = the two
 //         int8 sub-block scales, e = d (quant.h: piece pc = lane & 7 at position 4 (pc & 1) + (pc >> 1))
+//   IQ4_XS: a = 16 B of nibbles in Q4_K's pattern, c = the lane's two int8 sub-block scales
+//         (ls - 32), e = d
 //   Q8_0: a, b = the lane's 32 codes, e = d
 //   BF16: a, b, a2, b2 = the lane's 32 weights (bf16 pairs), one contiguous KB per register
 //         over the wave (weights pass*2048 + 512 i + 8 l .. +8 for register i = a, b, a2, b2)
@@ -733,6 +735,22 @@ __device__ __forceinline__ uint2 bld8(const uint8_t *base, uint32_t bytes, uint3
     return make_uint2(v[0], v[1]);
 }
 
+// IQ4_XS's table lookup: the 8 nibbles of q -> kv[low nibbles] in lo, kv[high nibbles] in hi, four
+// signed bytes each, as the dot4 and MFMA instructions take them. The 16-entry table is four
+// constant dwords (entries 0-3, 4-7, 8-11, 12-15). v_perm_b32 selects among 8 bytes, so a code's low
+// three bits select in the low and in the high half of the table (two perms on the same selector)
+// and a third perm picks per byte between the two results by the code's bit 3: its selector is
+// byte i's own index i, + 4 where bit 3 is set (selector bytes 4-7 take the first operand). The
+// selectors come straight off the packed nibbles: q & 0x07070707 are the low nibbles' low bits,
+// (q >> 1) & 0x04040404 their bit 3 moved to the + 4. No LDS, no memory.
+__device__ __forceinline__ void iq4_lookup(uint32_t q, int &lo, int &hi) {
+    constexpr uint32_t T0 = iq4_table_dword(0), T1 = iq4_table_dword(1), T2 = iq4_table_dword(2), T3 = iq4_table_dword(3);
+    const uint32_t sl = q & 0x07070707u, sh = (q >> 4) & 0x07070707u;
+    const uint32_t pl = ((q >> 1) & 0x04040404u) | 0x03020100u, ph = ((q >> 5) & 0x04040404u) | 0x03020100u;
+    lo = (int)__builtin_amdgcn_perm(__builtin_amdgcn_perm(T3, T2, sl), __builtin_amdgcn_perm(T1, T0, sl), pl);
+    hi = (int)__builtin_amdgcn_perm(__builtin_amdgcn_perm(T3, T2, sh), __builtin_amdgcn_perm(T1, T0, sh), ph);
+}
+
 template <int T, int AUX = MIO_WEIGHT_AUX>
 __device__ __forceinline__ Frag load_frag(const QMat W, int row, int pass) {
     const int lane = MIO_TIDX & 63;
@@ -781,6 +799,14 @@ __device__ __forceinline__ Frag load_frag(const QMat W, int row, int pass) {
         f.b = make_uint4(bld4<AUX>(W.p1, R * hb, sb * 32 + P * 4, r * hb), 0, 0, 0);
         f.c = bld2<AUX>(W.p2, R * sbb, sb * 16 + 2 * P, r * sbb);
         f.e = bld2<AUX>(W.p3, R * db, sb * 2, r * db);
+    } else if constexpr (T == GGML_IQ4_XS) {
+        const int nsb = W.k >> 8, sb = min(pass * 8 + (lane >> 3), nsb - 1), pc = lane & 7;
+        const uint32_t qb = (uint32_t)(W.k / 2), sbb = (uint32_t)nsb * 8, db = (uint32_t)nsb * 2;
+        static_assert(stride_is(T, 0, 1, 2) && stride_is(T, 1, 8, 256) && stride_is(T, 2, 2, 256), "IQ4_XS row strides");
+        f.a = bld16<AUX>(W.p0, R * qb, sb * 128 + pc * 16, r * qb);
+        f.b = make_uint4(0, 0, 0, 0);
+        f.c = bld2<AUX>(W.p1, R * sbb, sb * 8 + 2 * (pc >> 1), r * sbb);
+        f.e = bld2<AUX>(W.p2, R * db, sb * 2, r * db);
     } else if constexpr (T == GGML_BF16) {
         // element offsets clamped into the row (past K: another valid piece, zeroed in dot_frag)
         const uint32_t rb = (uint32_t)W.k * 2;
@@ -812,7 +838,7 @@ __device__ __forceinline__ ALane load_alane(const ActL &a, int K, int pass) {
         const int nsb = K >> 8, sb = pass * 8 + (lane >> 3), pc = lane & 7;
         const int sbc = sb < nsb ? sb : 0;
         int e, e2;
-        if constexpr (T == GGML_Q3_K || has_mins(T)) {
+        if constexpr (T == GGML_Q3_K || has_mins(T) || table_codes(T)) {
             e = sbc * 256 + 64 * (pc >> 1) + 16 * (pc & 1);
             e2 = e + 32;
         } else {
@@ -845,7 +871,8 @@ __device__ __forceinline__ ALane load_alane(const ActL &a, int K, int pass) {
 
 // The per-lane part of a K-quant unit's row dot: the scaled integer terms of the lane's 32
 // weights (isum; Q4_K / Q5_K also imin, the mins against the activation's bsums) and the
-// superblock's raw float factors hd (Q4_K / Q5_K: the header's d | dmin f16 pair, Q6_K / Q3_K: d).
+// superblock's raw float factors hd (Q4_K / Q5_K: the header's d | dmin f16 pair, Q6_K / Q3_K /
+// IQ4_XS: d).
 // No cross-lane sum: dot_frag reduces one unit's terms, pair_term two units' together.
 struct LaneTerms {
     int isum, imin;
@@ -876,6 +903,29 @@ __device__ __forceinline__ LaneTerms lane_terms(const Frag &f, const ALane &al) 
         dhi = sdot4(code(f.a.y, f.b.x, 3, 7), al.hi.w, dhi);
         const int sa = (int)(int8_t)(f.c & 0xFF), sb = (int)(int8_t)(f.c >> 8);
         t.isum = __mul24(sa, dlo - 4 * al.b0) + __mul24(sb, dhi - 4 * al.b1);
+        t.imin = 0;
+        t.hd = f.e;
+    } else if constexpr (T == GGML_IQ4_XS) {
+        // the lane's bytes hold half of sub-block 2 jj in their low nibbles and half of sub-block
+        // 2 jj + 1 in their high ones (Q4_K's pattern); the codes go through the table and enter the
+        // dot as the signed values they stand for, so nothing comes off through the bsums.
+        // |dlo|, |dhi| <= 16 * 127 * 127 = 258 064 < 2^23 and |scale| <= 32: mul24 is exact
+        int l0, l1, l2, l3, h0, h1, h2, h3;
+        iq4_lookup(f.a.x, l0, h0);
+        iq4_lookup(f.a.y, l1, h1);
+        iq4_lookup(f.a.z, l2, h2);
+        iq4_lookup(f.a.w, l3, h3);
+        int dlo = 0, dhi = 0;
+        dlo = sdot4(l0, al.lo.x, dlo);
+        dlo = sdot4(l1, al.lo.y, dlo);
+        dlo = sdot4(l2, al.lo.z, dlo);
+        dlo = sdot4(l3, al.lo.w, dlo);
+        dhi = sdot4(h0, al.hi.x, dhi);
+        dhi = sdot4(h1, al.hi.y, dhi);
+        dhi = sdot4(h2, al.hi.z, dhi);
+        dhi = sdot4(h3, al.hi.w, dhi);
+        const int sa = (int)(int8_t)(f.c & 0xFF), sb = (int)(int8_t)(f.c >> 8);
+        t.isum = __mul24(sa, dlo) + __mul24(sb, dhi);
         t.imin = 0;
         t.hd = f.e;
     } else if constexpr (has_mins(T)) {
@@ -945,6 +995,8 @@ __device__ __forceinline__ LaneTerms lane_terms(const Frag &f, const ALane &al) 
 template <int T>
 __device__ __forceinline__ float sb_term(int isum, int imin, uint32_t hd, float ad) {
     if constexpr (scale_only(T)) {
+        // (IQ4_XS: |isum| can reach 32 * 127 * 127 * 32 * 8 = 132 128 768, which fits int32 but lies
+        // above 2^24, so this conversion rounds to nearest even; every path converts the same integer)
         const float d = h2f(hd) * ad;
         return d * (float)isum;
     } else {
@@ -1061,7 +1113,7 @@ __device__ __forceinline__ float swapadd32(float a, float b) {
 // whose instantiations would lose an occupancy step to the joint form's registers (k_ffn<1, 13,
 // 6, 3, 13, 3> 80 -> 81 VGPRs, k_attn_in<1, 12, 12, 6> 64 -> 65, k_attn_out<1, 14, 6> 79 -> 84)
 template <int T, int NP, int NM, int SU>
-constexpr bool joint_rows = (T == GGML_Q3_K || T == GGML_Q4_K || T == GGML_Q6_K) && NP == 1 && SU >= 2 && (NM == 2 || SU <= 4);
+constexpr bool joint_rows = (T == GGML_Q3_K || T == GGML_Q4_K || T == GGML_Q6_K || T == GGML_IQ4_XS) && NP == 1 && SU >= 2 && (NM == 2 || SU <= 4);
 
 // The rows of one group F (SU one-pass units: unit u = row lo + u / NM, matrix u % NM; units
 // past the share are clamped duplicates, computed and dropped) reduced pairwise, fin(row, dot0,
@@ -1293,13 +1345,43 @@ __device__ inline void wave_range(const LlmDims &d, int R, int &lo, int &hi) {
 
 
 // ------------------------------------------------------------------ embedding rows
-// Q3: the table may be Q3_K too (an untied token_embd of a Q3_K_S / _M / _L file). Only the kernels
-// of such a model are built with it, so the others' embedding lookups stay the code they were.
-// The launches of the embedding kernels pick the Q3 form by this and nothing else.
-inline bool q3_table(const QMat &tok_embd) { return tok_embd.type == GGML_Q3_K; }
-template <bool Q3 = false>
+// TE: the table may be of type TE too, GGML_Q3_K (an untied token_embd of a Q3_K_S / _M / _L file)
+// or GGML_IQ4_XS (of an IQ4_XS file); 0: neither. Only the kernels of such a model are built with
+// it, so the others' embedding lookups stay the code they were. The launches of the embedding
+// kernels pick the form by table_te and nothing else (for_table_te: f.template operator()<TE>()).
+inline int table_te(const QMat &tok_embd) {
+    return tok_embd.type == GGML_Q3_K || tok_embd.type == GGML_IQ4_XS ? tok_embd.type : 0;
+}
+// the TE of the kernels of a model whose layer-0 q|k (or in_proj) type is TQ (llm_load: such a
+// table loads beside such a layer 0 only)
+constexpr int te_of(int TQ) { return TQ == GGML_Q3_K || TQ == GGML_IQ4_XS ? TQ : 0; }
+template <class F>
+auto for_table_te(const QMat &tok_embd, F &&f) {
+    const int te = table_te(tok_embd);
+    if (te == GGML_Q3_K) return f.template operator()<GGML_Q3_K>();
+    if (te != GGML_IQ4_XS) return f.template operator()<0>();
+    return f.template operator()<GGML_IQ4_XS>();  // last: the earlier kernels keep their places
+}
+template <int TE = 0>
 __device__ float dequant_elem(const QMat &W, int row, int e) {
-    if constexpr (Q3) {
+    if constexpr (TE == GGML_IQ4_XS) {
+        if (W.type == GGML_IQ4_XS) {
+            // quant.h: element c of the superblock is byte 32 (c / 64) + c % 32, nibble (c / 32) % 2
+            const int nsb = W.k >> 8, sb = e >> 8, c = e & 255;
+            static_assert(stride_is(GGML_IQ4_XS, 0, 1, 2) && stride_is(GGML_IQ4_XS, 1, 8, 256) &&
+                          stride_is(GGML_IQ4_XS, 2, 2, 256), "IQ4_XS row strides (p2 in f16 units)");
+            const uint8_t qb = W.p0[(size_t)row * (W.k / 2) + sb * 128 + 32 * (c >> 6) + (c & 31)];
+            const int code = (qb >> (4 * ((c >> 5) & 1))) & 0xF;
+            // the table from its four dwords (no constant array in memory)
+            const uint32_t tw = code < 8 ? (code < 4 ? iq4_table_dword(0) : iq4_table_dword(1))
+                                         : (code < 12 ? iq4_table_dword(2) : iq4_table_dword(3));
+            const int kv = (int)(int8_t)(tw >> (8 * (code & 3)));
+            const int sc = ((const int8_t *)W.p1)[((size_t)row * nsb + sb) * 8 + (c >> 5)];
+            const float dd = h2f(((const uint16_t *)W.p2)[(size_t)row * nsb + sb]);
+            return dd * (float)sc * (float)kv;  // dequantize_row_iq4_xs: dl = d * (ls - 32), y = dl * kv
+        }
+    }
+    if constexpr (TE == GGML_Q3_K) {
         if (W.type == GGML_Q3_K) {
             // quant.h: element c of the superblock lies in piece pc's run t at index i
             const int nsb = W.k >> 8, sb = e >> 8, c = e & 255, pc = 2 * (c >> 6) + ((c >> 4) & 1), t = (c >> 5) & 1,
@@ -1353,13 +1435,13 @@ __device__ float dequant_elem(const QMat &W, int row, int e) {
 
 constexpr int ST = 1024;  // sampler / embedding threads (n_embd <= 4 * ST)
 
-template <bool Q3 = false>
+template <int TE = 0>
 __device__ inline void embed_row(const QMat &emb, int tok, int n, float *x) {
     float v[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int e = MIO_TIDX + i * ST;
-        v[i] = e < n ? dequant_elem<Q3>(emb, tok, e) : 0.0f;
+        v[i] = e < n ? dequant_elem<TE>(emb, tok, e) : 0.0f;
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -1527,7 +1609,7 @@ __device__ int sample_token(const float *smp, int nblk, const SampleCfg &sc, int
 
 // Embedding row of tok in the matvec prologue's register layout (thread t: elements
 // 4(t + i*MT) .. +3), the same dequantization as embed_row.
-template <int XV, bool Q3 = false>
+template <int XV, int TE = 0>
 __device__ inline void embed_regs(const QMat &emb, int tok, int K, XRegs<XV> &xr) {
 #pragma unroll
     for (int i = 0; i < XV; ++i) {
@@ -1535,7 +1617,7 @@ __device__ inline void embed_regs(const QMat &emb, int tok, int K, XRegs<XV> &xr
         float v[4] = {0.f, 0.f, 0.f, 0.f};
         if (e < K)
 #pragma unroll
-            for (int q = 0; q < 4; ++q) v[q] = dequant_elem<Q3>(emb, tok, e + q);
+            for (int q = 0; q < 4; ++q) v[q] = dequant_elem<TE>(emb, tok, e + q);
         xr.v[i] = make_float4(v[0], v[1], v[2], v[3]);
     }
 }
@@ -1550,7 +1632,7 @@ __device__ inline void embed_regs(const QMat &emb, int tok, int K, XRegs<XV> &xr
 
 // Calls f.template operator()<NP, T>() for the matrix's pass count and weight type. BF = false:
 // the int8 types only (the multi-token engine: BF16 models prefill token by token). Q3 = false:
-// without Q3_K (the lm_head launches: the loader refuses a Q3_K output matrix).
+// without Q3_K and IQ4_XS (the lm_head launches: the loader refuses such an output matrix).
 // The helpers below return true when a case matched and f ran. The cases of a list run in the
 // list's order, which is the order the kernels are first used in and so their place in the code
 // object: append to a list, do not sort it. For the same reason they return `auto`: a function
@@ -1574,6 +1656,7 @@ void dispatch_nt(int K, int type, F &&f) {
     }
     if constexpr (Q3) {
         if (nt_cases<GGML_Q3_K>(np, type, f)) return;
+        if (nt_cases<GGML_IQ4_XS>(np, type, f)) return;  // last: the earlier types' kernels keep their places
     }
     no_kernel("matvec", type, K);
 }
@@ -1607,6 +1690,7 @@ auto dispatch_kquant(int type, F &&f) {
     if (type == GGML_Q5_K) return f.template operator()<GGML_Q5_K>(), true;
     if (type == GGML_Q6_K) return f.template operator()<GGML_Q6_K>(), true;
     if (type == GGML_Q3_K) return f.template operator()<GGML_Q3_K>(), true;
+    if (type == GGML_IQ4_XS) return f.template operator()<GGML_IQ4_XS>(), true;
     return false;
 }
 

@@ -305,7 +305,8 @@ __global__ __launch_bounds__(MT) void k_ffn(float *x, const float *norm_w, StepS
 // the instantiated (np, gate|up type, su, down np, down type, down su): 1.7B Q4_K_M (down Q4_K
 // or Q6_K), Q5_K_M / Q5_K_S (gate|up Q5_K, down Q5_K or Q6_K), Q6_K and BF16, 0.1B Q8_0 (down Q8_0,
 // or Q6_K: its Q6_K file), 2.6B Q8_0 (and LFM2-2.6B) and Q6_K, the tiny test presets' shapes; last,
-// the 1.7B shape as Q3_K_S / Q3_K_M / Q3_K_L (gate|up Q3_K, down Q3_K, Q4_K or Q5_K)
+// the 1.7B shape as Q3_K_S / Q3_K_M / Q3_K_L (gate|up Q3_K, down Q3_K, Q4_K or Q5_K) and then as
+// IQ4_XS (gate|up IQ4_XS, down IQ4_XS, or Q5_K on the first n_layer / 8 layers)
 #define MIO_FFN_SHAPES(X) \
     X(1, GGML_Q4_K, 6, 3, GGML_Q4_K, 3)            \
     X(1, GGML_Q4_K, 6, 3, GGML_Q6_K, 3)            \
@@ -319,7 +320,9 @@ __global__ __launch_bounds__(MT) void k_ffn(float *x, const float *norm_w, StepS
     X(1, GGML_Q6_K, 0, 6, GGML_Q6_K, 0)            \
     X(1, GGML_Q3_K, 6, 3, GGML_Q3_K, 3)            \
     X(1, GGML_Q3_K, 6, 3, GGML_Q4_K, 3)            \
-    X(1, GGML_Q3_K, 6, 3, GGML_Q5_K, 3)
+    X(1, GGML_Q3_K, 6, 3, GGML_Q5_K, 3)            \
+    X(1, GGML_IQ4_XS, 6, 3, GGML_IQ4_XS, 3)        \
+    X(1, GGML_IQ4_XS, 6, 3, GGML_Q5_K, 3)
 
 struct FfnShape {
     int np, t, su, npd, td, sud, GI, GD;
@@ -526,8 +529,8 @@ void launch_att_o(int G, int grid, size_t lds, hipStream_t s, const LlmDims &d, 
 // ------------------------------------------------------------------ sampler / embedding
 // The flush sampler (after the last step of a run; the step graph samples inside the next
 // step's layer-0 attn_in): the pending token, its embedding into b.x, the state advance.
-// Q3: the embedding table is Q3_K (dequant_elem)
-template <bool DG, bool Q3>
+// TE: the embedding table's type where it is Q3_K or IQ4_XS, else 0 (dequant_elem)
+template <bool DG, int TE>
 __global__ __launch_bounds__(ST) void k_sample(LlmDims d, QMat emb, int nblk, LlmBuffers b) {
     constexpr bool kDiag = DG;
     __shared__ float rs_[ST / 64];
@@ -541,7 +544,7 @@ __global__ __launch_bounds__(ST) void k_sample(LlmDims d, QMat emb, int nblk, Ll
     const int tok = sample_token<ST>(b.smp, nblk, sc, step, rs_, ri_);
     MIO_TRACE(b, 1);
     MIO_TL_MARK1(b);
-    embed_row<Q3>(emb, tok, d.n_embd, b.x);
+    embed_row<TE>(emb, tok, d.n_embd, b.x);
     MIO_TL_END(b);
     MIO_TRACE(b, 15);
     if (MIO_TIDX == 0) {
@@ -556,9 +559,9 @@ __global__ __launch_bounds__(ST) void k_sample(LlmDims d, QMat emb, int nblk, Ll
     }
 }
 
-template <bool Q3>
+template <int TE>
 __global__ __launch_bounds__(ST) void k_embed(LlmDims d, QMat emb, LlmBuffers b) {
-    embed_row<Q3>(emb, b.st->token, d.n_embd, b.x);
+    embed_row<TE>(emb, b.st->token, d.n_embd, b.x);
 }
 
 }  // namespace
@@ -595,7 +598,7 @@ int lm_head_blocks(const LlmDims &d) { const LlmDims l = lm_dims(d); return matv
 size_t matvec_lds(int K) { return smem_bytes(K); }
 
 void launch_embed_token(const LlmDims &d, const QMat &tok_embd, const LlmBuffers &b, hipStream_t s) {
-    hipLaunchKernelGGL(q3_table(tok_embd) ? k_embed<true> : k_embed<false>, dim3(1), dim3(ST), 0, s, d, tok_embd, b);
+    hipLaunchKernelGGL(for_table_te(tok_embd, []<int TE>() { return k_embed<TE>; }), dim3(1), dim3(ST), 0, s, d, tok_embd, b);
 }
 
 inline size_t mv_lds(int K) { return smem_bytes(K); }
@@ -723,7 +726,7 @@ void launch_step_kernel(StepKind which, const StepCtx &c, int il, const LlmBuffe
             launch_sample_chain(ChainArgs{b.logits, 0, b.st, b.cfg, b.smp, lm_head_blocks(d), nullptr, 0}, 1, s);
             break;
         case kSample:
-            hipLaunchKernelGGL((q3_table(tok_embd) ? k_sample<DG, true> : k_sample<DG, false>), dim3(1), dim3(ST), 0, s, d,
+            hipLaunchKernelGGL(for_table_te(tok_embd, []<int TE>() { return k_sample<DG, TE>; }), dim3(1), dim3(ST), 0, s, d,
                                tok_embd, lm_head_blocks(d), b);
             break;
         default: break;

@@ -142,7 +142,8 @@ __global__ __launch_bounds__(MT) void k_layer_att(const float *x, const float *n
 // the instantiated (np, q|k type, v type, su, hd, G, o type, o su): 1.7B Q4_K_M (v Q4_K or
 // Q6_K), Q5_K_M / Q5_K_S (q|k, o Q5_K, v Q5_K or Q6_K), Q6_K (every matrix) and BF16, 0.1B Q8_0,
 // 2.6B Q8_0 (and the LFM2-2.6B attention layers) and Q6_K; last, the 1.7B shape as Q3_K_S (every
-// matrix Q3_K), Q3_K_M (v Q4_K or Q5_K, o Q4_K) and Q3_K_L (v, o Q5_K)
+// matrix Q3_K), Q3_K_M (v Q4_K or Q5_K, o Q4_K) and Q3_K_L (v, o Q5_K), then as IQ4_XS (G 2: v is
+// IQ4_XS too)
 #define MIO_LAYER_ATT_SHAPES(X)   \
     X(1, GGML_Q4_K, GGML_Q4_K, 2, 128, 2, GGML_Q4_K, 1)              \
     X(1, GGML_Q4_K, GGML_Q6_K, 2, 128, 2, GGML_Q4_K, 1)              \
@@ -156,7 +157,8 @@ __global__ __launch_bounds__(MT) void k_layer_att(const float *x, const float *n
     X(1, GGML_Q3_K, GGML_Q3_K, 2, 128, 2, GGML_Q3_K, 1)              \
     X(1, GGML_Q3_K, GGML_Q4_K, 2, 128, 2, GGML_Q4_K, 1)              \
     X(1, GGML_Q3_K, GGML_Q5_K, 2, 128, 2, GGML_Q4_K, 1)              \
-    X(1, GGML_Q3_K, GGML_Q5_K, 2, 128, 2, GGML_Q5_K, 1)
+    X(1, GGML_Q3_K, GGML_Q5_K, 2, 128, 2, GGML_Q5_K, 1)              \
+    X(1, GGML_IQ4_XS, GGML_IQ4_XS, 2, 128, 2, GGML_IQ4_XS, 1)
 
 struct Shape {
     int np, tq, tv, su, hd, g, to, suo;

@@ -275,6 +275,54 @@ __device__ __forceinline__ v16f sb_q3k(const QMat &W, int row, int s, const int8
     return v;
 }
 
+// IQ4_XS superblock s: 8 sub-blocks of 32, v = d * sum_ib (ls_ib - 32) * C_ib (ggml
+// vec_dot_iq4_xs_q8_K). The nibbles lie in Q4_K's pattern (quant.h), so the loads and the MFMA
+// shape are sb_q4k's: chunk c's low nibbles are sub-block 2 c, its high ones sub-block 2 c + 1,
+// one 32x32x32 MFMA each; the B operand is the table values of the codes (iq4_lookup), signed
+// int8 as they stand, so there is no min term and no second accumulator.
+__device__ __forceinline__ v16f sb_iq4xs(const QMat &W, int row, int s, const int8_t *aq, const float *da_lds) {
+    const int lane = threadIdx.x & 63, h = lane >> 5;
+    const int nsb = W.k >> 8;
+    static_assert(stride_is(GGML_IQ4_XS, 0, 1, 2) && stride_is(GGML_IQ4_XS, 1, 8, 256) && stride_is(GGML_IQ4_XS, 2, 2, 256),
+                  "IQ4_XS row strides (drow in f16 units)");
+    const uint8_t *qrow = W.p0 + (size_t)row * (W.k / 2);
+    const uint2 scr = *reinterpret_cast<const uint2 *>(W.p1 + ((size_t)row * nsb + s) * 8);
+    const uint16_t *drow = (const uint16_t *)W.p2 + (size_t)row * nsb;
+    int8_t sc[8];
+    __builtin_memcpy(sc, &scr, 8);
+    uint4 nb[4];
+    v4i al[4], ah[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        nb[c] = *reinterpret_cast<const uint4 *>(qrow + (size_t)s * 128 + 32 * c + 16 * h);
+        al[c] = act16(aq, s * 256 + 64 * c + 16 * h);
+        ah[c] = act16(aq, s * 256 + 64 * c + 32 + 16 * h);
+    }
+    v16i isum = {};
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        int l[4], hh[4];
+        iq4_lookup(nb[c].x, l[0], hh[0]);
+        iq4_lookup(nb[c].y, l[1], hh[1]);
+        iq4_lookup(nb[c].z, l[2], hh[2]);
+        iq4_lookup(nb[c].w, l[3], hh[3]);
+        const v4i blo = {l[0], l[1], l[2], l[3]}, bhi = {hh[0], hh[1], hh[2], hh[3]};
+        const v16i clo = __builtin_amdgcn_mfma_i32_32x32x32_i8(al[c], blo, v16i{}, 0, 0, 0);
+        const v16i chi = __builtin_amdgcn_mfma_i32_32x32x32_i8(ah[c], bhi, v16i{}, 0, 0, 0);
+        const int sc0 = sc[2 * c], sc1 = sc[2 * c + 1];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) isum[r] += __mul24(sc0, clo[r]) + __mul24(sc1, chi[r]);
+    }
+    const float dw = h2f(drow[s]);
+    v16f v;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const float d = dw * da_lds[s * TT + tok_of(lane, r)];
+        v[r] = d * (float)isum[r];  // |isum| may pass 2^24: rounds, as the decode's conversion does
+    }
+    return v;
+}
+
 // slot k's pass accumulation (K-quants)
 template <int T>
 __device__ v16f slot_kq(const QMat &W, int row, int k, const int8_t *aq, const float *da_lds) {
@@ -287,7 +335,9 @@ __device__ v16f slot_kq(const QMat &W, int row, int k, const int8_t *aq, const f
             static_assert(is_kquant(T), "slot_kq: K-quant types");
             static_assert(stride_is(GGML_Q4_K, 0, 1, 2) && stride_is(GGML_Q4_K, 1, 16, 256) && stride_is(GGML_Q5_K, 0, 1, 2) &&
                           stride_is(GGML_Q5_K, 1, 1, 8) && stride_is(GGML_Q5_K, 2, 16, 256), "Q4_K / Q5_K row strides");
-            if constexpr (T == GGML_Q3_K)
+            if constexpr (T == GGML_IQ4_XS)
+                v = sb_iq4xs(W, row, s, aq, da_lds);
+            else if constexpr (T == GGML_Q3_K)
                 v = sb_q3k(W, row, s, aq, da_lds);
             else if constexpr (T == GGML_Q4_K)
                 v = sb_q4k(W.p0 + (size_t)row * (W.k / 2), W.p1 + (size_t)row * nsb * 16, s, aq, da_lds);
@@ -858,15 +908,70 @@ __device__ __forceinline__ v4f q3p_val(const Q3Pass &p, const v4i (&x)[4], int s
     return v;
 }
 
+// IQ4_XS superblock s on the 16x16 tiles: the nibble loads, the swaps and the MFMAs of Q4_K's pass
+// (q4p_val: run c's low nibbles are sub-block 2 c against the low halves of x[c], its high ones
+// sub-block 2 c + 1 against the high halves) with the codes sent through the table first. One
+// MFMA per sub-block: the table values are signed, so no masked second product and no min term.
+struct IqPass {
+    uint2 scr;
+    v4i w[2];
+    uint16_t d;
+};
+__device__ __forceinline__ void iqp_load(const QMat &W, int row, int s, IqPass &p) {
+    const int g = (threadIdx.x & 63) >> 4, nsb = W.k >> 8;
+    static_assert(stride_is(GGML_IQ4_XS, 0, 1, 2) && stride_is(GGML_IQ4_XS, 1, 8, 256) && stride_is(GGML_IQ4_XS, 2, 2, 256),
+                  "IQ4_XS row strides (p2 in f16 units)");
+    const uint8_t *qrow = W.p0 + (size_t)row * (W.k / 2);
+    p.scr = *reinterpret_cast<const uint2 *>(W.p1 + ((size_t)row * nsb + s) * 8);
+#pragma unroll
+    for (int i = 0; i < 2; ++i) p.w[i] = *reinterpret_cast<const v4i *>(qrow + (size_t)s * 128 + 64 * i + 16 * g);
+    p.d = ((const uint16_t *)W.p2)[(size_t)row * nsb + s];
+}
+// x: the superblock's activation codes of this lane, already swap_halves'd
+__device__ __forceinline__ v4f iqp_val(IqPass p, const v4i (&x)[4], int s, const float *da_lds) {
+    const int lane = threadIdx.x & 63;
+    int8_t sc[8];
+    __builtin_memcpy(sc, &p.scr, 8);
+    v4i (&w)[2] = p.w;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) swap_halves(w[i]);
+    v4i isum = {};
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const uint32_t q0 = (uint32_t)((c & 1) ? w[c >> 1].z : w[c >> 1].x), q1 = (uint32_t)((c & 1) ? w[c >> 1].w : w[c >> 1].y);
+        int l0, l1, h0, h1;
+        iq4_lookup(q0, l0, h0);
+        iq4_lookup(q1, l1, h1);
+        const long qlo = (long)(uint32_t)l0 | ((long)(uint32_t)l1 << 32), qhi = (long)(uint32_t)h0 | ((long)(uint32_t)h1 << 32);
+        const v4i clo = mfma16(lo8(x[c]), qlo, v4i{});
+        const v4i chi = mfma16(hi8(x[c]), qhi, v4i{});
+        const int sc0 = sc[2 * c], sc1 = sc[2 * c + 1];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) isum[i] += __mul24(sc0, clo[i]) + __mul24(sc1, chi[i]);
+    }
+    const float dw = h2f(p.d);
+    v4f v;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const float d = dw * da_lds[s * TT16 + tok16(lane, i)];
+        v[i] = d * (float)isum[i];  // |isum| may pass 2^24: rounds, as the decode's conversion does
+    }
+    return v;
+}
+
 template <int T>
-using KqPass = std::conditional_t<T == GGML_Q3_K, Q3Pass,
-                                  std::conditional_t<T == GGML_Q4_K, Q4Pass, std::conditional_t<T == GGML_Q5_K, Q5Pass, Q6Pass>>>;
+using KqPass = std::conditional_t<
+    T == GGML_IQ4_XS, IqPass,
+    std::conditional_t<T == GGML_Q3_K, Q3Pass,
+                       std::conditional_t<T == GGML_Q4_K, Q4Pass, std::conditional_t<T == GGML_Q5_K, Q5Pass, Q6Pass>>>>;
 template <int T>
 __device__ __forceinline__ void kqp_load(const QMat &W, int row, int s, KqPass<T> &p) {
     static_assert(is_kquant(T), "kqp_load: K-quant types");
     static_assert(stride_is(GGML_Q4_K, 0, 1, 2) && stride_is(GGML_Q4_K, 1, 16, 256) && stride_is(GGML_Q5_K, 0, 1, 2) &&
                   stride_is(GGML_Q5_K, 1, 1, 8) && stride_is(GGML_Q5_K, 2, 16, 256), "Q4_K / Q5_K row strides");
-    if constexpr (T == GGML_Q3_K)
+    if constexpr (T == GGML_IQ4_XS)
+        iqp_load(W, row, s, p);
+    else if constexpr (T == GGML_Q3_K)
         q3p_load(W, row, s, p);
     else if constexpr (T == GGML_Q4_K)
         q4p_load(W.p0 + (size_t)row * (W.k / 2), W.p1 + (size_t)row * (W.k >> 8) * 16, s, p);
@@ -878,7 +983,9 @@ __device__ __forceinline__ void kqp_load(const QMat &W, int row, int s, KqPass<T
 }
 template <int T>
 __device__ __forceinline__ v4f kqp_val(const KqPass<T> &p, const v4i (&x)[4], int s, const float *da) {
-    if constexpr (T == GGML_Q3_K)
+    if constexpr (T == GGML_IQ4_XS)
+        return iqp_val(p, x, s, da);
+    else if constexpr (T == GGML_Q3_K)
         return q3p_val(p, x, s, da);
     else if constexpr (T == GGML_Q6_K)
         return q6p_val(p, x, s, da);
@@ -895,7 +1002,13 @@ __device__ v4f slot16_kq(const QMat &W, int row, int k, const AP &aq, const floa
         v4f v = {};
         if (s < nsb) {
             static_assert(is_kquant(T), "slot16_kq: K-quant types");
-            if constexpr (T == GGML_Q3_K) {
+            if constexpr (T == GGML_IQ4_XS) {
+                IqPass ps;
+                iqp_load(W, row, s, ps);
+                v4i x[4];
+                kq_act(aq, s, x);
+                v = iqp_val(ps, x, s, da_lds);
+            } else if constexpr (T == GGML_Q3_K) {
                 Q3Pass ps;
                 q3p_load(W, row, s, ps);
                 v4i x[4];
@@ -1651,6 +1764,7 @@ void launch_mmq(const MmqSeg *seg, const int *types, int nseg, int mode, const M
     else if (types[0] == GGML_Q6_K) one.template operator()<GGML_Q6_K>();
     else if (types[0] == GGML_Q8_0) one.template operator()<GGML_Q8_0>();
     else if (types[0] == GGML_Q3_K) one.template operator()<GGML_Q3_K>();
+    else if (types[0] == GGML_IQ4_XS) one.template operator()<GGML_IQ4_XS>();  // last, as every new type
     else no_kernel("matmul", types[0], a.K);
 }
 

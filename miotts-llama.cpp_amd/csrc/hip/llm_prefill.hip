@@ -817,11 +817,12 @@ __global__ __launch_bounds__(MT) void k_pf_ffn_down_q(LlmDims d, QMat down, Pref
     });
 }
 
-// Q3 (here and in k_bt_sample, k_bt_admit): the embedding table is Q3_K (dequant_elem)
-template <bool Q3>
+// TE (here and in k_bt_sample, k_bt_admit): the embedding table's type where it is Q3_K or IQ4_XS,
+// else 0 (dequant_elem)
+template <int TE>
 __global__ __launch_bounds__(ST) void k_pf_embed(LlmDims d, QMat emb, PrefillBuffers pb, int p0) {
     const int t = blockIdx.x;
-    embed_row<Q3>(emb, pb.tokens[p0 + t], d.n_embd, pb.x + (size_t)t * d.n_embd);
+    embed_row<TE>(emb, pb.tokens[p0 + t], d.n_embd, pb.x + (size_t)t * d.n_embd);
 }
 
 // ------------------------------------------------------------------ batched decode (B utterances)
@@ -937,7 +938,7 @@ __global__ __launch_bounds__(MT) void k_bt_gumbel(int R, BatchBuffers bb, int nt
 // selection rule), its place in the utterance's output region, end-token flag, the next
 // embedding into pb.x[b], and the state advance. A stream whose step budget (cfg.max_steps) is spent, or that sampled an end
 // token, is frozen: nothing is recorded and its position no longer advances.
-template <bool Q3>
+template <int TE>
 __global__ __launch_bounds__(ST) void k_bt_sample(LlmDims d, QMat emb, int nblk, PrefillBuffers pb,
                                                   BatchBuffers bb) {
     __shared__ float bs_[ST / 64];
@@ -987,7 +988,7 @@ __global__ __launch_bounds__(ST) void k_bt_sample(LlmDims d, QMat emb, int nblk,
     // sampled last, again: the layers left their output in pb.x[t], and the next step repeats
     // (token, pos) on the same input instead of on that residual, so a slot whose budget is spent
     // holds the logits of its last token however many steps follow
-    embed_row<Q3>(emb, tok, d.n_embd, pb.x + (size_t)t * d.n_embd);
+    embed_row<TE>(emb, tok, d.n_embd, pb.x + (size_t)t * d.n_embd);
     if (tid == 0 && live) {
         sc.out_tokens[step] = tok;
         if (tok == sc.eos0 || tok == sc.eos1) st->done = 1, signal_host_done(sc);
@@ -1030,7 +1031,7 @@ __global__ __launch_bounds__(ST) void k_bt_refill(PrefillBuffers pb, QueueBuffer
 // then the input of EVERY slot's next step is embedded, the row of st.token into pb.x[t]: the
 // prefill chunks overwrote pb.x, where k_bt_sample had left the live slots' next inputs, and a
 // live slot's st.token is the token it sampled last, so its row comes back as it was.
-template <bool Q3>
+template <int TE>
 __global__ __launch_bounds__(ST) void k_bt_admit(LlmDims d, QMat emb, PrefillBuffers pb, BatchBuffers bb,
                                                  SampleCfg *cfg, SampleCfg base, QueueBuffers q, QueueRefill r) {
     const int t = blockIdx.x;
@@ -1053,7 +1054,7 @@ __global__ __launch_bounds__(ST) void k_bt_admit(LlmDims d, QMat emb, PrefillBuf
     } else {
         tok = bb.st[t].token;
     }
-    embed_row<Q3>(emb, tok, d.n_embd, pb.x + (size_t)t * d.n_embd);
+    embed_row<TE>(emb, tok, d.n_embd, pb.x + (size_t)t * d.n_embd);
 }
 
 template <int HD>
@@ -1474,7 +1475,7 @@ void launch_prefill_chunk(const LlmDims &d, const LayerW *layers, int n_layer, _
                           _Float16 *vcache, const QMat &tok_embd, const PrefillBuffers &pb, int p0, int nt,
                           int n_chunks, hipStream_t s) {
     if (nt <= 0) return;
-    hipLaunchKernelGGL(q3_table(tok_embd) ? k_pf_embed<true> : k_pf_embed<false>, dim3(nt), dim3(ST), 0, s, d, tok_embd,
+    hipLaunchKernelGGL(for_table_te(tok_embd, []<int TE>() { return k_pf_embed<TE>; }), dim3(nt), dim3(ST), 0, s, d, tok_embd,
                        pb, p0);
     launch_layers(d, layers, n_layer, kcache, vcache, pb, nt, n_chunks, false, s);
 }
@@ -1536,7 +1537,7 @@ void launch_batch_step(const LlmDims &d, const LayerW *layers, int n_layer, _Flo
         });
     }
     if (chain) launch_sample_chain(ChainArgs{bb.logits, (size_t)lm.rows, bb.st, bb.cfg, bb.smp, nblk, nullptr, 0}, B, s);
-    hipLaunchKernelGGL(q3_table(tok_embd) ? k_bt_sample<true> : k_bt_sample<false>, dim3(B), dim3(ST), 0, s, d, tok_embd,
+    hipLaunchKernelGGL(for_table_te(tok_embd, []<int TE>() { return k_bt_sample<TE>; }), dim3(B), dim3(ST), 0, s, d, tok_embd,
                        nblk, pb, bb);
 }
 
@@ -1548,7 +1549,7 @@ void launch_queue_refill(const PrefillBuffers &pb, const QueueBuffers &q, const 
 void launch_queue_admit(const LlmDims &d, const QMat &tok_embd, const PrefillBuffers &pb, const BatchBuffers &bb,
                         SampleCfg *cfg, const SampleCfg &base, const QueueBuffers &q, const QueueRefill &r, int B,
                         hipStream_t s) {
-    hipLaunchKernelGGL(q3_table(tok_embd) ? k_bt_admit<true> : k_bt_admit<false>, dim3(B), dim3(ST), 0, s, d, tok_embd, pb,
+    hipLaunchKernelGGL(for_table_te(tok_embd, []<int TE>() { return k_bt_admit<TE>; }), dim3(B), dim3(ST), 0, s, d, tok_embd, pb,
                        bb, cfg, base, q, r);
 }
 

@@ -22,6 +22,7 @@ size_t ggml_type_block_elems(uint32_t t) {
         case GGML_Q4_K:
         case GGML_Q5_K:
         case GGML_Q6_K:
+        case GGML_IQ4_XS:
         case GGML_Q8_K: return 256;
         default: return 1;
     }
@@ -42,6 +43,7 @@ size_t ggml_type_block_bytes(uint32_t t) {
         case GGML_Q4_K: return 144;
         case GGML_Q5_K: return 176;
         case GGML_Q6_K: return 210;
+        case GGML_IQ4_XS: return 136;
         case GGML_Q8_K: return 292;
         default: return 0;
     }
@@ -68,6 +70,7 @@ const char *ggml_type_name(uint32_t t) {
         case GGML_Q4_K: return "q4_K";
         case GGML_Q5_K: return "q5_K";
         case GGML_Q6_K: return "q6_K";
+        case GGML_IQ4_XS: return "iq4_xs";
         case GGML_Q8_K: return "q8_K";
         default: return "?";
     }

@@ -128,7 +128,7 @@ bool upload_qmat(mio_hip_llm *m, const mio::GgufTensor *t, mio::QMat &q) {
     q.p1 = dp + L.off[1];
     q.p2 = dp + L.off[2];
     q.p3 = dp + L.off[3];
-    // the bytes the split layout streams (Q3_K: 114 B per superblock, not the GGUF's 110). Q4_0 /
+    // the bytes the split layout streams (Q3_K: 114 B per superblock, not the GGUF's 110; IQ4_XS: 138, not 136). Q4_0 /
     // Q5_0 files keep counting their GGUF bytes although they stream as Q8_0
     m->weight_bytes += repack ? t->nbytes : (uint64_t)t->ne[1] * mio::row_bytes((int)type, t->ne[0]);
     return true;
@@ -233,20 +233,21 @@ int upload_globals(const Load &ld, mio_hip_llm *m) {
     D.n_vocab = (int)te->ne[1];
     MIO_REQUIRE(D.n_vocab <= 128 * 8 * D.n_wg, MIO_ERR_UNSUPPORTED, "llm_load: vocab %d > %d", D.n_vocab,
                 128 * 8 * D.n_wg);
-    // the output matrix (or the tied table) as Q3_K does not occur in llama-quantize's files (they
-    // carry Q6_K there): no lm_head kernel is instantiated for it
+    // the output matrix (or the tied table) as Q3_K or IQ4_XS does not occur in llama-quantize's
+    // files (they carry Q6_K there): no lm_head kernel is instantiated for either
     const mio::GgufTensor *tl = ld.g.tensor("output.weight") ? ld.g.tensor("output.weight") : te;
-    MIO_REQUIRE(tl->type != mio::GGML_Q3_K, MIO_ERR_UNSUPPORTED,
+    MIO_REQUIRE(tl->type != mio::GGML_Q3_K && tl->type != mio::GGML_IQ4_XS, MIO_ERR_UNSUPPORTED,
                 "llm: tensor %s has type %s as the output matrix; supported there: bf16, q8_0, q4_K, q5_K, q6_K",
                 tl->name.c_str(), mio::ggml_type_name(tl->type));
     // a Q3_K table's row lookup is built into the launches of a Q3_K model only (layer 0's first
-    // matrix Q3_K: llm_device.h dequant_elem), which is where llama-quantize's files have one
-    if (te->type == mio::GGML_Q3_K) {
+    // matrix Q3_K: llm_device.h dequant_elem), which is where llama-quantize's files have one; an
+    // IQ4_XS table's likewise
+    if (te->type == mio::GGML_Q3_K || te->type == mio::GGML_IQ4_XS) {
         const mio::GgufTensor *t0 = ld.g.tensor("blk.0.attn_q.weight");
         if (!t0) t0 = ld.g.tensor("blk.0.shortconv.in_proj.weight");
-        MIO_REQUIRE(t0 && t0->type == mio::GGML_Q3_K, MIO_ERR_UNSUPPORTED,
-                    "llm: tensor %s has type %s beside a layer 0 that is not q3_K: not supported", te->name.c_str(),
-                    mio::ggml_type_name(te->type));
+        MIO_REQUIRE(t0 && t0->type == te->type, MIO_ERR_UNSUPPORTED,
+                    "llm: tensor %s has type %s beside a layer 0 that is not %s: not supported", te->name.c_str(),
+                    mio::ggml_type_name(te->type), mio::ggml_type_name(te->type));
     }
     const uint64_t before = m->weight_bytes;
     if (!upload_qmat(m, te, m->tok)) return MIO_ERR_FORMAT;

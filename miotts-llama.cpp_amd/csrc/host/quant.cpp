@@ -278,6 +278,49 @@ static int q3k_scale6(const uint8_t *sc, int j) {
     return ((sc[j % 8] >> (4 * (j / 8))) & 0xF) | (((sc[8 + j % 4] >> (2 * (j / 4))) & 3) << 4);
 }
 
+// IQ4_XS: per sub-block of 32 the scale vmax / -127 that sends the signed largest element to code 0
+// (kv[0] = -127, the table's largest magnitude), d = the scale of largest magnitude / -32 (so that
+// one has ls - 32 = -32 exactly, the asymmetric end of the range), ls = round(scale / d) + 32 clamped
+// to 0 .. 63, every code the nearest table entry of x / (d * (ls - 32)). Not ggml's
+// search (no weighted refinement of the scale).
+void quantize_row_iq4_xs(const float *x, void *vy, int64_t k) {
+    BlockIQ4_XS *y = (BlockIQ4_XS *)vy;
+    for (int64_t i = 0; i < k / 256; ++i) {
+        const float *xb = x + i * 256;
+        float scales[8], max_scale = 0.0f;
+        for (int ib = 0; ib < 8; ++ib) {
+            float amax = 0.0f, vmax = 0.0f;
+            for (int l = 0; l < 32; ++l)
+                if (std::fabs(xb[32 * ib + l]) > amax) amax = std::fabs(xb[32 * ib + l]), vmax = xb[32 * ib + l];
+            scales[ib] = vmax / (float)kIq4Values[0];
+            if (std::fabs(scales[ib]) > std::fabs(max_scale)) max_scale = scales[ib];
+        }
+        y[i].d = f32_to_fp16(max_scale / -32.0f);
+        const float dh = fp16_to_f32(y[i].d);
+        y[i].scales_h = 0;
+        std::memset(y[i].scales_l, 0, 4);
+        std::memset(y[i].qs, 0, 128);
+        for (int ib = 0; ib < 8; ++ib) {
+            const int ls = dh != 0 ? std::min(63, std::max(0, nearest_int(scales[ib] / dh) + 32)) : 32;
+            y[i].scales_l[ib / 2] |= (uint8_t)((ls & 0xF) << (4 * (ib % 2)));
+            y[i].scales_h |= (uint16_t)((ls >> 4) << (2 * ib));
+            const float dl = dh * (float)(ls - 32);
+            for (int l = 0; l < 32; ++l) {
+                const float v = dl != 0 ? xb[32 * ib + l] / dl : 0.0f;
+                int best = 8;  // kv[8] = 1: the entry nearest 0
+                for (int c = 0; c < 16; ++c)
+                    if (std::fabs(v - (float)kIq4Values[c]) < std::fabs(v - (float)kIq4Values[best])) best = c;
+                y[i].qs[16 * ib + l % 16] |= (uint8_t)(best << (4 * (l / 16)));
+            }
+        }
+    }
+}
+
+// sub-block ib's 6-bit scale of an IQ4_XS block
+static int iq4xs_scale6(const BlockIQ4_XS &b, int ib) {
+    return ((b.scales_l[ib / 2] >> (4 * (ib % 2))) & 0xF) | (((b.scales_h >> (2 * ib)) & 3) << 4);
+}
+
 bool quantize_row(uint32_t type, const float *x, void *y, int64_t k) {
     switch (type) {
         case GGML_F32: std::memcpy(y, x, k * 4); return true;
@@ -294,6 +337,7 @@ bool quantize_row(uint32_t type, const float *x, void *y, int64_t k) {
         case GGML_Q4_K: quantize_row_q4_K(x, y, k); return true;
         case GGML_Q5_K: quantize_row_q5_K(x, y, k); return true;
         case GGML_Q6_K: quantize_row_q6_K(x, y, k); return true;
+        case GGML_IQ4_XS: quantize_row_iq4_xs(x, y, k); return true;
         default: return false;
     }
 }
@@ -418,6 +462,20 @@ bool dequantize_row(uint32_t type, const void *vx, float *y, int64_t k) {
             }
             return true;
         }
+        case GGML_IQ4_XS: {  // dequantize_row_iq4_xs: dl = d * (ls - 32), y = dl * kvalues[code]
+            const BlockIQ4_XS *x = (const BlockIQ4_XS *)vx;
+            for (int64_t i = 0; i < k / 256; ++i) {
+                const float d = fp16_to_f32(x[i].d);
+                for (int ib = 0; ib < 8; ++ib) {
+                    const float dl = d * (float)(iq4xs_scale6(x[i], ib) - 32);
+                    for (int j = 0; j < 16; ++j) {
+                        y[i * 256 + 32 * ib + j] = dl * (float)kIq4Values[x[i].qs[16 * ib + j] & 0xF];
+                        y[i * 256 + 32 * ib + j + 16] = dl * (float)kIq4Values[x[i].qs[16 * ib + j] >> 4];
+                    }
+                }
+            }
+            return true;
+        }
         default: return false;
     }
 }
@@ -528,6 +586,21 @@ bool to_split(uint32_t type, const void *src, int64_t R, int64_t K, uint8_t *dst
                         }
                     }
                 }
+                d[i] = b[i].d;
+            }
+        } else if (type == GGML_IQ4_XS) {
+            // quant.h: the code of element e goes to byte 32 (e / 64) + e % 32, nibble (e / 32) % 2
+            const BlockIQ4_XS *b = (const BlockIQ4_XS *)row;
+            uint8_t *qs = plane(0);
+            int8_t *sc = (int8_t *)plane(1);
+            uint16_t *d = (uint16_t *)plane(2);
+            for (int64_t i = 0; i < K / 256; ++i) {
+                std::memset(qs + 128 * i, 0, 128);
+                for (int e = 0; e < 256; ++e) {
+                    const int code = (b[i].qs[16 * (e / 32) + e % 16] >> (4 * ((e / 16) % 2))) & 0xF;
+                    qs[128 * i + 32 * (e / 64) + e % 32] |= (uint8_t)(code << (4 * ((e / 32) % 2)));
+                }
+                for (int ib = 0; ib < 8; ++ib) sc[8 * i + ib] = (int8_t)(iq4xs_scale6(b[i], ib) - 32);
                 d[i] = b[i].d;
             }
         } else {  // Q6_K

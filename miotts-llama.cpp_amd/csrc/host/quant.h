@@ -6,7 +6,7 @@
 // a plane is to_split's, restated by the dequantizers of the kernels (llm_device.h dequant_elem).
 //
 // Same bytes per weight as GGUF (algorithmic bytes unchanged; Q3_K: 114 B per superblock for
-// the GGUF's 110, below); each row's quant payload becomes one contiguous, 16-B aligned run, so
+// the GGUF's 110, IQ4_XS: 138 B for the GGUF's 136, both below); each row's quant payload becomes one contiguous, 16-B aligned run, so
 // one wave reads a row with 16 B per lane (Q3_K: 8 B).
 //
 // Q3_K regroups the bits inside a superblock (the same 256 codes and 16 scales, permuted), so a
@@ -26,6 +26,20 @@
 // 114 B, not the 112 B of the packed 12 scale bytes + d rounded up to a header: with int8
 // scales no lane runs ggml's kmask shuffle per unit, as Q6_K's lanes do not; 3.6 % more bytes
 // than the GGUF, which mio_hip_llm_weight_bytes counts.
+//
+// IQ4_XS (ggml type 23; restated from the public ggml block spec and not pinned against ggml's
+// own code, as Q3_K / Q5_K / Q6_K are not): 256 weights in 136 B, f16 d | u16 scales_h |
+// u8 scales_l[4] | u8 qs[128]; 8 sub-blocks of 32. Sub-block ib has the 6-bit scale
+//   ls = ((scales_l[ib / 2] >> 4 (ib % 2)) & 0xF) | (((scales_h >> 2 ib) & 3) << 4),  dl = d * (ls - 32),
+// its element j < 16 is dl * kv[qs[16 ib + j] & 0xF] and element j + 16 is dl * kv[qs[16 ib + j] >> 4]
+// with kv = kIq4Values (weight_types.h): the codes index a table, they are not an affine range.
+// The split layout regroups the nibbles into Q4_K's pattern, so a matvec lane's 16 bytes are half
+// of each of two sub-blocks against the activations Q4_K's lanes load:
+//   qs : 128 B, byte i of the 32-byte chunk jj: low nibble = the code of element 64 jj + i, high
+//        nibble = the code of element 64 jj + 32 + i
+//   sc : 8 B, ls - 32 of sub-blocks 0 .. 7 as int8 in [-32, 31] (no lane unpacks bit fields)
+//   d  : the superblock's f16 d
+// 138 B, 1.5 % more than the GGUF, which mio_hip_llm_weight_bytes counts.
 #pragma once
 
 #include <cstddef>
@@ -80,7 +94,14 @@ struct BlockQ6_K {
     int8_t scales[16];
     uint16_t d;
 };
+struct BlockIQ4_XS {
+    uint16_t d;
+    uint16_t scales_h;
+    uint8_t scales_l[4];
+    uint8_t qs[128];
+};
 #pragma pack(pop)
+static_assert(sizeof(BlockIQ4_XS) == 136, "iq4_xs");
 static_assert(sizeof(BlockQ8_0) == 34, "q8_0");
 static_assert(sizeof(BlockQ4_0) == 18, "q4_0");
 static_assert(sizeof(BlockQ5_0) == 22, "q5_0");
@@ -100,6 +121,7 @@ void quantize_row_q3_K(const float *x, void *y, int64_t k);
 void quantize_row_q4_K(const float *x, void *y, int64_t k);
 void quantize_row_q5_K(const float *x, void *y, int64_t k);
 void quantize_row_q6_K(const float *x, void *y, int64_t k);
+void quantize_row_iq4_xs(const float *x, void *y, int64_t k);
 bool quantize_row(uint32_t type, const float *x, void *y, int64_t k);
 bool dequantize_row(uint32_t type, const void *x, float *y, int64_t k);
 

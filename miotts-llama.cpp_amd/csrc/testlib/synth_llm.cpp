@@ -111,15 +111,16 @@ SynthLlmCfg synth_llm_preset(int p) {
 }
 
 bool synth_llm_qtype_known(int q) {
-    return q == 8 || q == 15 || q == 16 || q == 17 || q == 18 || q == 2 || q == 30 || q == 11 || q == 12 || q == 13;
+    return q == 8 || q == 15 || q == 16 || q == 17 || q == 18 || q == 2 || q == 30 || q == 11 || q == 12 || q == 13 || q == 23;
 }
 
 const char *synth_llm_check(const SynthLlmCfg &c) {
     // llama-quantize turns Q5_K rows that are not whole 256-element superblocks into Q5_1, which
     // the loader refuses: such a file would be of no use
     // (Q3_K rows likewise become IQ4_NL, refused too: the same message for Q3_K_S / _M / _L)
-    const bool q3 = c.qtype == 11 || c.qtype == 12 || c.qtype == 13;
-    if ((c.qtype == 16 || c.qtype == 17 || q3) && (c.n_embd % 256 || c.n_ff % 256 || (c.n_head * c.head_dim) % 256))
+    // (IQ4_XS rows too: recipe 23)
+    const bool whole_sb_only = c.qtype == 16 || c.qtype == 17 || c.qtype == 11 || c.qtype == 12 || c.qtype == 13 || c.qtype == 23;
+    if (whole_sb_only && (c.n_embd % 256 || c.n_ff % 256 || (c.n_head * c.head_dim) % 256))
         return "Q5_K_S / Q5_K_M need n_embd, n_ff and n_head * head_dim to be multiples of 256";
     return nullptr;
 }
@@ -160,10 +161,12 @@ bool synth_write_llm(const std::string &path, const SynthLlmCfg &c) {
     w.kv_str("general.architecture", a);
     w.kv_str("general.name", c.name);
     // llama_ftype: 7 MOSTLY_Q8_0, 15 MOSTLY_Q4_K_M, 16 MOSTLY_Q5_K_S, 17 MOSTLY_Q5_K_M, 18 MOSTLY_Q6_K,
-    // 2 MOSTLY_Q4_0, 32 MOSTLY_BF16, 11 MOSTLY_Q3_K_S, 12 MOSTLY_Q3_K_M, 13 MOSTLY_Q3_K_L
+    // 2 MOSTLY_Q4_0, 32 MOSTLY_BF16, 11 MOSTLY_Q3_K_S, 12 MOSTLY_Q3_K_M, 13 MOSTLY_Q3_K_L, 30
+    // MOSTLY_IQ4_XS (recipe 23: the ggml type's id, since 30 is BF16 here)
     const bool q3mix = c.qtype == 11 || c.qtype == 12 || c.qtype == 13;
-    const bool kmix = c.qtype == 15 || c.qtype == 16 || c.qtype == 17 || c.qtype == 18 || q3mix;
-    w.kv_u32("general.file_type", kmix ? c.qtype : (c.qtype == 2 ? 2 : (c.qtype == 30 ? 32 : 7)));
+    const bool iq4 = c.qtype == 23;
+    const bool kmix = c.qtype == 15 || c.qtype == 16 || c.qtype == 17 || c.qtype == 18 || q3mix || iq4;
+    w.kv_u32("general.file_type", iq4 ? 30 : (kmix ? c.qtype : (c.qtype == 2 ? 2 : (c.qtype == 30 ? 32 : 7))));
     w.kv_u32(a + ".context_length", c.n_ctx);
     w.kv_u32(a + ".embedding_length", c.n_embd);
     w.kv_u32(a + ".block_count", c.n_layer);
@@ -218,8 +221,14 @@ bool synth_write_llm(const std::string &path, const SynthLlmCfg &c) {
     // first two attention layers, Q4_K after; _L Q5_K), attn_output (Q3_K / Q4_K / Q5_K) and ffn_down
     // (_S Q3_K; _M Q5_K on layers i < n_layer / 16, Q4_K after; _L Q5_K); the untied embedding is
     // Q3_K, the output matrix Q6_K.
-    const uint32_t kbase = q3mix ? GGML_Q3_K : (c.qtype == 15 ? GGML_Q4_K : (c.qtype == 18 ? GGML_Q6_K : GGML_Q5_K));
+    // IQ4_XS (llama_tensor_get_type as far as it is known here, the no-imatrix case): IQ4_XS
+    // everywhere but attn_v (Q5_K when n_head / n_head_kv >= 4), ffn_down (Q5_K on layers i <
+    // n_layer / 8) and the output matrix (Q6_K; the tied embedding is one); the untied embedding is
+    // IQ4_XS.
+    const bool iq4_v5 = c.n_head_kv > 0 && c.n_head / c.n_head_kv >= 4;
+    const uint32_t kbase = iq4 ? GGML_IQ4_XS : q3mix ? GGML_Q3_K : (c.qtype == 15 ? GGML_Q4_K : (c.qtype == 18 ? GGML_Q6_K : GGML_Q5_K));
     const uint32_t base = pick(kbase, GGML_Q4_0), more = pick(c.qtype == 16 ? kbase : GGML_Q6_K, GGML_Q4_0);
+    auto iq4_down = [&](int i) -> uint32_t { return i < c.n_layer / 8 ? GGML_Q5_K : GGML_IQ4_XS; };
     int i_attn = 0;  // attention layers so far (llama-quant's i_attention_wv)
     auto q3_v = [&](int ia) -> uint32_t {
         return c.qtype == 11 ? GGML_Q3_K : (c.qtype == 13 ? GGML_Q5_K : (ia < 2 ? GGML_Q5_K : GGML_Q4_K));
@@ -244,7 +253,8 @@ bool synth_write_llm(const std::string &path, const SynthLlmCfg &c) {
         } else {
         ts.push_back({p + "attn_q.weight", base, c.n_embd, q_dim, false});
         ts.push_back({p + "attn_k.weight", base, c.n_embd, kv_dim, false});
-        ts.push_back({p + "attn_v.weight", q3mix ? q3_v(i_attn++) : (mb ? more : base), c.n_embd, kv_dim, false});
+        ts.push_back({p + "attn_v.weight", iq4 ? (iq4_v5 ? (uint32_t)GGML_Q5_K : base) : q3mix ? q3_v(i_attn++) : (mb ? more : base), c.n_embd,
+                      kv_dim, false});
         ts.push_back({p + "attn_output.weight", q3mix ? q3_o : base, q_dim, c.n_embd, false});
         if (c.qkv_bias) {
             ts.push_back({p + "attn_q.bias", GGML_F32, q_dim, 1, 2});
@@ -259,7 +269,8 @@ bool synth_write_llm(const std::string &path, const SynthLlmCfg &c) {
         ts.push_back({p + "ffn_norm.weight", GGML_F32, c.n_embd, 1, true});
         ts.push_back({p + "ffn_gate.weight", base, c.n_embd, c.n_ff, false});
         ts.push_back({p + "ffn_up.weight", base, c.n_embd, c.n_ff, false});
-        ts.push_back({p + "ffn_down.weight", q3mix ? q3_down(i) : (mb ? more : base), c.n_ff, c.n_embd, false});
+        ts.push_back({p + "ffn_down.weight", iq4 ? iq4_down(i) : q3mix ? q3_down(i) : (mb ? more : base), c.n_ff, c.n_embd,
+                      false});
     }
     // lfm2's final norm is token_embd_norm (llama.cpp model.tok_norm)
     ts.push_back({lfm2 ? "token_embd_norm.weight" : "output_norm.weight", GGML_F32, c.n_embd, 1, true});

@@ -12,8 +12,10 @@
 //   Q5_K : qs 128 u8 nibbles | qh 32 u8 fifth-bit plane | hd 16 as Q4_K's
 //   Q6_K : ql 128 u8         | qh 64 u8                | sc 16 i8 (lane-pair order) | d 2 f16
 //   BF16 : 2
+//   IQ4_XS: qs 128 u8 nibbles (Q4_K's pattern) | sc 8 i8 (ls - 32) | d 2 f16
 //
-// Same bytes per weight as GGUF, except Q3_K: 114 B per superblock for the GGUF's 110 (quant.h).
+// Same bytes per weight as GGUF, except Q3_K: 114 B per superblock for the GGUF's 110, and IQ4_XS:
+// 138 B for the GGUF's 136 (quant.h).
 #pragma once
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
@@ -36,6 +38,7 @@ enum GgmlType : unsigned {
     GGML_Q5_K = 13,
     GGML_Q6_K = 14,
     GGML_Q8_K = 15,
+    GGML_IQ4_XS = 23,
     GGML_I8 = 24,
     GGML_I16 = 25,
     GGML_I32 = 26,
@@ -43,15 +46,26 @@ enum GgmlType : unsigned {
 };
 
 // The types a weight matrix may have on the device (Q4_0 / Q5_0 files are repacked to Q8_0).
-constexpr int kWeightTypes[] = {GGML_Q8_0, GGML_Q3_K, GGML_Q4_K, GGML_Q5_K, GGML_Q6_K, GGML_BF16};
+constexpr int kWeightTypes[] = {GGML_Q8_0, GGML_Q3_K, GGML_Q4_K, GGML_Q5_K, GGML_Q6_K, GGML_BF16, GGML_IQ4_XS};
 constexpr int kNumWeightTypes = sizeof(kWeightTypes) / sizeof(kWeightTypes[0]);
 
-// 256-weight superblocks
-MIO_WT_FN bool is_kquant(int t) { return t == GGML_Q3_K || t == GGML_Q4_K || t == GGML_Q5_K || t == GGML_Q6_K; }
+// 256-weight superblocks against the Q8_K activation (IQ4_XS is one: its vec_dot_type is Q8_K)
+MIO_WT_FN bool is_kquant(int t) {
+    return t == GGML_Q3_K || t == GGML_Q4_K || t == GGML_Q5_K || t == GGML_Q6_K || t == GGML_IQ4_XS;
+}
 // superblock header {d, dmin, scales | mins}: the mins go against the activation's bsums
 MIO_WT_FN bool has_mins(int t) { return t == GGML_Q4_K || t == GGML_Q5_K; }
-// superblock of int8 scales and one d: no mins
-MIO_WT_FN bool scale_only(int t) { return t == GGML_Q6_K || t == GGML_Q3_K; }
+// superblock of int8 scales and one d: no mins (IQ4_XS: and no bsums term either, its table
+// values are signed as they stand)
+MIO_WT_FN bool scale_only(int t) { return t == GGML_Q6_K || t == GGML_Q3_K || t == GGML_IQ4_XS; }
+// codes are indices into a 16-entry table of signed bytes, not an affine range
+MIO_WT_FN bool table_codes(int t) { return t == GGML_IQ4_XS; }
+// IQ4_XS's table (ggml's kvalues_iq4nl), four entries per little-endian dword as v_perm_b32 takes them
+constexpr int kIq4Values[16] = {-127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113};
+MIO_WT_FN unsigned iq4_table_dword(int i) {
+    return (unsigned)(kIq4Values[4 * i] & 0xFF) | (unsigned)(kIq4Values[4 * i + 1] & 0xFF) << 8 |
+           (unsigned)(kIq4Values[4 * i + 2] & 0xFF) << 16 | (unsigned)(kIq4Values[4 * i + 3] & 0xFF) << 24;
+}
 // one block (Q8_0) or one piece (BF16) per lane: float terms, summed over 8 lanes by sum8_f
 MIO_WT_FN bool lane_blocks(int t) { return t == GGML_Q8_0 || t == GGML_BF16; }
 // activations are streamed as bf16 records (2 bytes per element)
@@ -74,6 +88,7 @@ MIO_WT_FN int plane_block_bytes(int t, int p) {
         case GGML_Q5_K: { const int b[kMaxPlanes] = {128, 32, 16, 0}; return b[p]; }
         case GGML_Q6_K: { const int b[kMaxPlanes] = {128, 64, 16, 2}; return b[p]; }
         case GGML_BF16: { const int b[kMaxPlanes] = {2, 0, 0, 0}; return b[p]; }
+        case GGML_IQ4_XS: { const int b[kMaxPlanes] = {128, 8, 2, 0}; return b[p]; }
         default: return 0;
     }
 }
@@ -107,13 +122,15 @@ static_assert(block_bytes(GGML_Q5_K) == 176 && block_elems(GGML_Q5_K) == 256 && 
 static_assert(block_bytes(GGML_Q6_K) == 210 && block_elems(GGML_Q6_K) == 256 && num_planes(GGML_Q6_K) == 4, "Q6_K");
 static_assert(block_bytes(GGML_Q8_0) == 34 && block_elems(GGML_Q8_0) == 32 && num_planes(GGML_Q8_0) == 2, "Q8_0");
 static_assert(block_bytes(GGML_BF16) == 2 && block_elems(GGML_BF16) == 1 && num_planes(GGML_BF16) == 1, "BF16");
+static_assert(block_bytes(GGML_IQ4_XS) == 138 && block_elems(GGML_IQ4_XS) == 256 && num_planes(GGML_IQ4_XS) == 3, "IQ4_XS");
+static_assert(iq4_table_dword(0) == 0xBFAD9881u && iq4_table_dword(3) == 0x71594535u, "IQ4_XS table dwords");
 static_assert(row_bytes(GGML_Q6_K, 2304) == 9 * 210 && plane_row_bytes(GGML_Q6_K, 2304, 1) == 2304 / 4, "rows");
 static_assert(!is_weight_type(GGML_F16) && !is_weight_type(GGML_Q4_0) && num_planes(GGML_F32) == 0, "others");
 
 // ------------------------------------------------------------------ q|k beside attn_v
 // The (q|k type, attn_v type) pairs the q|k|v launches are instantiated for: v of q|k's own type,
 // Q6_K beside Q4_K / Q5_K (the *_K_M mixes' use_more_bits layers), Q4_K beside Q6_K, Q4_K / Q5_K
-// beside Q3_K (Q3_K_M / Q3_K_L). In the order the launches first use them, which fixes each
+// beside Q3_K (Q3_K_M / Q3_K_L), Q5_K beside IQ4_XS (n_head / n_head_kv >= 4). In the order the launches first use them, which fixes each
 // kernel's place in its code object: append, do not sort.
 struct QkvTypes {
     int qk, v;
@@ -122,6 +139,7 @@ constexpr QkvTypes kQkvTypes[] = {
     {GGML_Q4_K, GGML_Q4_K}, {GGML_Q4_K, GGML_Q6_K}, {GGML_Q5_K, GGML_Q5_K}, {GGML_Q5_K, GGML_Q6_K},
     {GGML_Q6_K, GGML_Q6_K}, {GGML_Q6_K, GGML_Q4_K}, {GGML_Q8_0, GGML_Q8_0}, {GGML_Q3_K, GGML_Q3_K},
     {GGML_Q3_K, GGML_Q4_K}, {GGML_Q3_K, GGML_Q5_K}, {GGML_BF16, GGML_BF16},
+    {GGML_IQ4_XS, GGML_IQ4_XS}, {GGML_IQ4_XS, GGML_Q5_K},
 };
 constexpr int kNumQkvTypes = sizeof(kQkvTypes) / sizeof(kQkvTypes[0]);
 constexpr bool attn_v_supported(int tq, int tv) {

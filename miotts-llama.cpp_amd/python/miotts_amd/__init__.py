@@ -539,7 +539,7 @@ def synth_llm(path: str, preset: int = 0, seed: int = 1) -> str:
 
 def synth_llm_as(path: str, preset: int, qtype: int, seed: int = 1) -> str:
     """Preset `preset`'s shape, arch and seed rule written with the recipe `qtype` (SynthLlmCfg's
-    numbering: 8, 15, 16, 17, 18 = MOSTLY_Q6_K, 11 / 12 / 13 = Q3_K_S / _M / _L, 2, 30)."""
+    numbering: 8, 15, 16, 17, 18 = MOSTLY_Q6_K, 11 / 12 / 13 = Q3_K_S / _M / _L, 23 = IQ4_XS, 2, 30)."""
     check(lib().mio_synth_llm_gguf_as(path.encode(), preset, qtype, seed))
     return path
 
@@ -833,7 +833,7 @@ class Llm:
 
 
 GGML_BLOCK = {2: (32, 18), 6: (32, 22), 8: (32, 34), 11: (256, 110), 12: (256, 144), 13: (256, 176), 14: (256, 210),
-              30: (1, 2)}
+              23: (256, 136), 30: (1, 2)}
 
 
 def quantize_rows(qtype: int, x: np.ndarray) -> np.ndarray:
