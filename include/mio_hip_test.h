@@ -81,6 +81,38 @@ int mio_hip_llm_set_kv_rows(mio_hip_llm *m, int il, int p0, int n_pos, const uin
  * Cache row pos of the layer is written, the decode state is left at pos (eval / generate set
  * their own). A short-conv layer is refused with MIO_ERR_INVALID. */
 int mio_hip_llm_debug_attention(mio_hip_llm *m, int il, int pos, int which, const float *qkv, float *att);
+/* One call of the multi-token engine's attention (LayerRun::attention, csrc/hip/llm_prefill.hip) of
+ * layer il for nt tokens (1 <= nt <= kPrefillB = 128) on raw q|k|v rows qkv[nt][(H + 2 Hkv) * hd],
+ * which replace the engine's q|k|v buffer; nothing else of a layer runs.
+ * mode 0: the prefill pair (k_pf_rope, then k_pf_attention), as the chunked prefill and the queue's
+ * admissions launch it; 1: the batched decode step's k_bt_attention.
+ * slots 0: the handle's own cache, seen as the prefill sees it (one sequence: every seq[t] is 0).
+ * 1..16 (kBatchMax): the batch caches, seen as the batched engine sees them, seq[t] < slots naming
+ * the slot; a handle whose batch state has fewer slots gets one of `slots` slots first, all caches
+ * zero (the allocation of mio_hip_llm_generate_batch), which drops the rows of the state it had.
+ * pos[nt], seq[nt], frozen[nt] (NULL: none): per token its position (< n_ctx), its sequence, and
+ * whether its stream is frozen. Mode 1 passes them as the batched step does (a StepState per token,
+ * the frozen word its `done`), takes one token per sequence at most, and skips a frozen token: no
+ * cache row, no output, no ticket. Mode 0 refuses a frozen token and two tokens on one cache row.
+ * att_q: -1, or which activation record of the O matvec the merging workgroup also writes: 0 Q8_0
+ * blocks (G * hd a multiple of 32), 1 Q8_K superblocks (a multiple of 256).
+ * n_chunks: the chunk count of the grid; 0 = what production passes: mode 0 (prefill_issue, the
+ * queue's admissions) max pos / 64 + 1, mode 1 (launch_batch_step) ceil(n_ctx / 64) whatever the
+ * positions. A value below max pos / 64 + 1 or above ceil(n_ctx / 64) is refused.
+ * reset != 0: the chunk tickets are zeroed before the launch; 0: they are what the previous launch
+ * left (every launch leaves 0).
+ * Out: att[nt][H * hd], the merged outputs; rec[nt][K + (K / 32 + 8) * 4 + (K / 16 + 8) * 2 rounded
+ * up to 16] with K = H * hd (may be NULL; meaningful with att_q >= 0), the records' bytes: qs int8
+ * [K], d f32 [K / 32 + 8] (att_q 0: one per block, an f16 value; 1: one per superblock), bs int16
+ * [K / 16 + 8] (att_q 1: the bsums); tickets[nt * Hkv], the ticket words after the launch.
+ * Rows [0, nt] of the device's output buffer are filled with MIO_DEBUG_SENTINEL_F32 before the
+ * launch (row nt where nt < 128): a row no workgroup merged comes back as the sentinel, and a
+ * changed row nt is MIO_ERR_HIP. Every token's cache row pos[t] of the layer is written.
+ * Arguments outside the above and a short-conv layer are MIO_ERR_INVALID; a slot count the batched
+ * engine does not take is MIO_ERR_UNSUPPORTED. tests/test_attention_multi_gpu.py. */
+int mio_hip_llm_debug_attention_multi(mio_hip_llm *m, int il, int mode, int slots, int nt, const int32_t *pos,
+                                      const int32_t *seq, const int32_t *frozen, const float *qkv, int att_q,
+                                      int n_chunks, int reset, float *att, uint8_t *rec, int32_t *tickets);
 
 /* The polled words of the fused attention launches' hand-offs: words[3 * n_kv] receives, per kv
  * head, the q row counter, the q|k|v row counter and the chunk arrival word. Every one is 0 between
@@ -103,6 +135,12 @@ int mio_hip_llm_batch_logits(mio_hip_llm *m, float *logits);
 /* mio_hip_llm_kv_rows on slot `slot`: f16 bit patterns k, v [n_kv][n_pos][head_dim] of cache rows
  * [0, n_pos) of layer il. A short-conv layer, or a slot or layer out of range: MIO_ERR_INVALID. */
 int mio_hip_llm_batch_kv_rows(mio_hip_llm *m, int slot, int il, int n_pos, uint16_t *k, uint16_t *v);
+/* Its inverse (mio_hip_llm_set_kv_rows on slot `slot`): f16 bit patterns k, v [n_kv][n_pos][head_dim]
+ * into cache rows [p0, p0 + n_pos) of layer il. MIO_ERR_INVALID before the batch state exists (a
+ * batched call or mio_hip_llm_debug_attention_multi with slots > 0 allocates it), for a short-conv
+ * layer, and for a slot, layer or range outside it. */
+int mio_hip_llm_batch_set_kv_rows(mio_hip_llm *m, int slot, int il, int p0, int n_pos, const uint16_t *k,
+                                  const uint16_t *v);
 /* mio_hip_llm_conv_ring (get) on slot `slot`: ring[4][n_embd] of the lfm2 short-conv layer il;
  * an attention layer, or a slot or layer out of range: MIO_ERR_INVALID. */
 int mio_hip_llm_batch_conv_ring(mio_hip_llm *m, int slot, int il, float *ring);

@@ -336,5 +336,11 @@ void launch_debug_act_quant(int type, const float *x, const float *w, int K, flo
 size_t debug_act_bytes(int K);
 void launch_debug_mmq(const QMat &W, const QMat &up, int mode, const float *x, int nt, char *act, float *y,
                       hipStream_t s);
+// The multi-token layers' attention of one layer alone (LayerRun::attention, as launch_layers
+// calls it): nt tokens of pb over n_chunks chunks; kc / vc = the layer's rows of sequence 0's
+// cache; decode: k_bt_attention, else k_pf_rope + k_pf_attention; att_q as merger_records gives it.
+void launch_debug_attention_multi(const LlmDims &d, const LayerW &L, _Float16 *kc, _Float16 *vc,
+                                  const PrefillBuffers &pb, int nt, int n_chunks, bool decode, int att_q,
+                                  hipStream_t s);
 
 }  // namespace mio

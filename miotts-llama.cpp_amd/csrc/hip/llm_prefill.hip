@@ -1496,6 +1496,14 @@ void launch_debug_mmq(const QMat &W, const QMat &up, int mode, const float *x, i
     launch_mmq(&sg, &W.type, 1, mode, MmqArgs{act, act_bytes(W.k), W.k, nt, y, W.rows, up}, s);
 }
 
+// parity entry (mio_hip_llm_debug_attention_multi): LayerRun::attention of one layer, alone
+void launch_debug_attention_multi(const LlmDims &d, const LayerW &L, _Float16 *kc, _Float16 *vc,
+                                  const PrefillBuffers &pb, int nt, int n_chunks, bool decode, int att_q,
+                                  hipStream_t s) {
+    const LayerRun r{d, pb, nt, decode, s};
+    r.attention(L, kc, vc, n_chunks, att_q);
+}
+
 size_t batch_lm_head_lds(const LlmDims &d, int B, int type) {
     return pf_lds_bytes(rec_k(d.n_embd, type), B, 0) + (size_t)MW * B * 128 * 4;
 }

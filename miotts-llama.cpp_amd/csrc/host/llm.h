@@ -69,6 +69,15 @@ int llm_batch_state(mio_hip_llm *m, int *B, int32_t *pos, int32_t *step, int32_t
 int llm_batch_logits(mio_hip_llm *m, float *logits);
 int llm_batch_kv_rows(mio_hip_llm *m, int slot, int il, int n_pos, uint16_t *k, uint16_t *v);
 int llm_batch_conv_ring(mio_hip_llm *m, int slot, int il, float *ring);
+// The inverse of llm_batch_kv_rows: rows into positions [p0, p0 + n_pos) of slot `slot`'s caches.
+int llm_batch_set_kv_rows(mio_hip_llm *m, int slot, int il, int p0, int n_pos, const uint16_t *k, const uint16_t *v);
+// One call of the multi-token layers' attention of layer il for nt tokens on injected raw q|k|v
+// rows qkv[nt][(H + 2 Hkv) hd] (include/mio_hip_test.h mio_hip_llm_debug_attention_multi has the
+// arguments): mode 0 the prefill pair, 1 the batched step; slots 0 the handle's cache, else the
+// batch caches. att[nt][H hd], rec (may be null) the O matvec's act records, tickets[nt Hkv].
+int llm_debug_attention_multi(mio_hip_llm *m, int il, int mode, int slots, int nt, const int32_t *pos,
+                              const int32_t *seq, const int32_t *frozen, const float *qkv, int att_q, int n_chunks,
+                              int reset, float *att, uint8_t *rec, int32_t *tickets);
 // The engines a batched step of B streams would run per layer and site, plan[n_layer][*n_sites],
 // and the lm_head's (batch_step_plan's codes, llm_kernels.h). Launches nothing.
 int llm_batch_plan(mio_hip_llm *m, int B, int32_t *plan, int *n_sites, int32_t *lm_head);

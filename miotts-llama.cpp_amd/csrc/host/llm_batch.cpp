@@ -13,6 +13,8 @@ namespace {
 
 size_t batch_seq_ring(const mio_hip_llm *m) { return (size_t)m->n_layer * mio::kConvSlots * m->dims.n_embd; }
 
+}  // namespace
+
 // Batch state for B streams (re-allocated when B changes; graphs re-captured).
 int batch_ensure(mio_hip_llm *m, int B) {
     auto &bt = m->bt;
@@ -53,6 +55,8 @@ int batch_ensure(mio_hip_llm *m, int B) {
     MIO_HIP_CHECK(hipStreamSynchronize(m->d->stream));
     return MIO_OK;
 }
+
+namespace {
 
 // The multi-token layers' view of the batch: token t sits at position pos[t * pos_stride] of
 // stream seq[t] (its cache and short-conv ring).

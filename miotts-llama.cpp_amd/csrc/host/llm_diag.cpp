@@ -6,6 +6,7 @@
 
 #include "gguf.h"
 #include "llm_model.h"
+#include "mio_hip_test.h"
 #include "quant.h"
 
 extern "C" int mio_hip_llm_step_kinds(const mio_hip_llm *m, int *kinds, int cap, int *n) {
@@ -265,6 +266,117 @@ int mio::llm_batch_kv_rows(mio_hip_llm *m, int slot, int il, int n_pos, uint16_t
         MIO_HIP_CHECK(hipMemcpyAsync(v + dst, m->bt.vc + src, (size_t)n_pos * D.hd * 2, hipMemcpyDeviceToHost, s));
     }
     MIO_HIP_CHECK(hipStreamSynchronize(s));
+    return MIO_OK;
+}
+
+// The inverse of llm_batch_kv_rows: rows [n_kv][n_pos][head_dim] into positions [p0, p0 + n_pos)
+// of layer il of slot `slot`'s caches.
+int mio::llm_batch_set_kv_rows(mio_hip_llm *m, int slot, int il, int p0, int n_pos, const uint16_t *k,
+                               const uint16_t *v) {
+    MIO_REQUIRE(m && k && v, MIO_ERR_INVALID, "llm_batch_set_kv_rows: null argument");
+    MIO_REQUIRE(m->bt.B > 0, MIO_ERR_INVALID, "llm_batch_set_kv_rows: this handle has no batch state yet");
+    MIO_REQUIRE(slot >= 0 && slot < m->bt.B && il >= 0 && il < m->n_layer && p0 >= 0 && n_pos >= 0 &&
+                    p0 <= m->dims.n_ctx && n_pos <= m->dims.n_ctx - p0,
+                MIO_ERR_INVALID, "llm_batch_set_kv_rows: slot %d / layer %d / rows [%d, +%d) out of range", slot, il, p0,
+                n_pos);
+    MIO_REQUIRE(!m->layers[il].conv, MIO_ERR_INVALID, "llm_batch_set_kv_rows: layer %d is a short-conv layer", il);
+    int rc = mio::bind(m->d);
+    if (rc) return rc;
+    const mio::LlmDims &D = m->dims;
+    hipStream_t s = m->d->stream;
+    const size_t seq_kv = (size_t)m->n_layer * D.n_kv * D.n_ctx * D.hd;  // batch_pb's seq_kv
+    for (int h = 0; h < D.n_kv && n_pos > 0; ++h) {
+        const size_t dst = (size_t)slot * seq_kv + (((size_t)il * D.n_kv + h) * D.n_ctx + p0) * D.hd,
+                     src = (size_t)h * n_pos * D.hd;
+        MIO_HIP_CHECK(hipMemcpyAsync(m->bt.kc + dst, k + src, (size_t)n_pos * D.hd * 2, hipMemcpyHostToDevice, s));
+        MIO_HIP_CHECK(hipMemcpyAsync(m->bt.vc + dst, v + src, (size_t)n_pos * D.hd * 2, hipMemcpyHostToDevice, s));
+    }
+    MIO_HIP_CHECK(hipStreamSynchronize(s));
+    return MIO_OK;
+}
+
+// One call of the multi-token layers' attention (LayerRun::attention of llm_prefill.hip) of layer
+// il on injected q|k|v rows (parity tests): mode 0 k_pf_rope + k_pf_attention, 1 k_bt_attention.
+// slots 0: the handle's own cache with prefill_issue's view (one sequence, seq_kv 0); else the
+// batch caches with batch_pb's view (batch_ensure where the state has fewer slots). The per-token
+// lists are uploaded to a scratch block of this call: positions one int apart (mode 0) or as the
+// pos / done words of a StepState per token (mode 1, step_pb's layout).
+int mio::llm_debug_attention_multi(mio_hip_llm *m, int il, int mode, int slots, int nt, const int32_t *pos,
+                                   const int32_t *seq, const int32_t *frozen, const float *qkv, int att_q,
+                                   int n_chunks, int reset, float *att, uint8_t *rec, int32_t *tickets) {
+    MIO_REQUIRE(m && pos && seq && qkv && att && tickets, MIO_ERR_INVALID, "llm_debug_attention_multi: null argument");
+    MIO_REQUIRE(il >= 0 && il < m->n_layer && (mode == 0 || mode == 1) && slots >= 0 && slots <= mio::kBatchMax &&
+                    nt >= 1 && nt <= mio::kPrefillB && att_q >= -1 && att_q <= 1,
+                MIO_ERR_INVALID, "llm_debug_attention_multi: layer %d / mode %d / slots %d / nt %d / att_q %d", il, mode,
+                slots, nt, att_q);
+    MIO_REQUIRE(!m->layers[il].conv, MIO_ERR_INVALID, "llm_debug_attention_multi: layer %d is a short-conv layer", il);
+    const mio::LlmDims &D = m->dims;
+    const int gh = D.n_head / D.n_kv * D.hd;
+    MIO_REQUIRE(att_q < 0 || gh % (att_q == 1 ? 256 : 32) == 0, MIO_ERR_INVALID,
+                "llm_debug_attention_multi: att_q %d needs whole blocks per kv head (G * hd = %d)", att_q, gh);
+    MIO_REQUIRE(!slots || (mio::batch_supported(D, slots, m->lm.type) && m->bf16_mt()), MIO_ERR_UNSUPPORTED,
+                "llm_debug_attention_multi: %d slots not supported", slots);
+    int pmax = 0;
+    for (int t = 0; t < nt; ++t) {
+        MIO_REQUIRE(pos[t] >= 0 && pos[t] < D.n_ctx && seq[t] >= 0 && seq[t] < std::max(slots, 1), MIO_ERR_INVALID,
+                    "llm_debug_attention_multi: token %d at position %d of sequence %d", t, pos[t], seq[t]);
+        MIO_REQUIRE(mode == 1 || !frozen || !frozen[t], MIO_ERR_INVALID,
+                    "llm_debug_attention_multi: token %d frozen in a prefill launch", t);
+        for (int u = 0; u < t; ++u)  // a row has one writer; the batched step has one token per sequence
+            MIO_REQUIRE(seq[u] != seq[t] || (mode == 0 && pos[u] != pos[t]), MIO_ERR_INVALID,
+                        "llm_debug_attention_multi: tokens %d and %d share %s", u, t,
+                        mode ? "a sequence" : "a cache row");
+        pmax = std::max(pmax, pos[t]);
+    }
+    const int need = pmax / mio::kAttChunk + 1;
+    if (n_chunks == 0) n_chunks = mode ? D.max_splits : need;  // launch_batch_step's / prefill_issue's count
+    MIO_REQUIRE(n_chunks >= need && n_chunks <= D.max_splits, MIO_ERR_INVALID,
+                "llm_debug_attention_multi: %d chunks (%d..%d)", n_chunks, need, D.max_splits);
+    int rc = mio::bind(m->d);
+    if (rc) return rc;
+    if (slots > m->bt.B && (rc = batch_ensure(m, slots))) return rc;
+    hipStream_t s = m->d->stream;
+    const size_t n_qkv = (size_t)(D.n_head + 2 * D.n_kv) * D.hd, KO = (size_t)D.n_head * D.hd;
+    const size_t rec_bytes = mio::debug_act_bytes((int)KO);
+    constexpr int kStateInts = (int)(sizeof(mio::StepState) / sizeof(int));
+    const int pstride = mode ? kStateInts : 1;
+    std::vector<int> lists((size_t)nt * pstride + nt, 0);
+    for (int t = 0; t < nt; ++t) {
+        lists[(size_t)t * pstride] = pos[t];
+        if (mode) lists[(size_t)t * pstride + 3] = frozen && frozen[t] ? 1 : 0;  // StepState.done
+        lists[(size_t)nt * pstride + t] = seq[t];
+    }
+    mio::Scratch<int> dl;
+    MIO_HIP_CHECK(hipMalloc((void **)dl.put(), lists.size() * sizeof(int)));
+    MIO_HIP_CHECK(hipMemcpyAsync(dl, lists.data(), lists.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    MIO_HIP_CHECK(hipMemcpyAsync(m->pf.qkv, qkv, (size_t)nt * n_qkv * 4, hipMemcpyHostToDevice, s));
+    if (reset)
+        MIO_HIP_CHECK(hipMemsetAsync(m->pf.att_cnt, 0, (size_t)mio::kPrefillB * D.n_kv * sizeof(int), s));
+    // rows [0, nt] of pb.att hold the sentinel (row nt where pb.att has one: the guard)
+    const int guard = nt < mio::kPrefillB ? 1 : 0;
+    std::vector<uint32_t> rows((size_t)(nt + guard) * KO, MIO_DEBUG_SENTINEL_F32);
+    MIO_HIP_CHECK(hipMemcpyAsync(m->pf.att, rows.data(), rows.size() * 4, hipMemcpyHostToDevice, s));
+    mio::PrefillBuffers pb = m->pf;
+    pb.pos = dl, pb.pos_stride = pstride;
+    if (slots) {  // batch_pb
+        pb.seq = dl + (size_t)nt * pstride, pb.seq_stride = 1;
+        pb.seq_kv = (size_t)m->n_layer * D.n_kv * D.n_ctx * D.hd;
+    } else {  // prefill_issue
+        pb.seq = m->d_iota, pb.seq_stride = 0;
+        pb.seq_kv = 0;
+    }
+    const size_t layer_kv = (size_t)D.n_kv * D.n_ctx * D.hd;
+    mio::launch_debug_attention_multi(D, m->layers[il], (slots ? m->bt.kc : m->kc) + il * layer_kv,
+                                      (slots ? m->bt.vc : m->vc) + il * layer_kv, pb, nt, n_chunks, mode == 1, att_q, s);
+    MIO_HIP_CHECK(hipGetLastError());
+    MIO_HIP_CHECK(hipMemcpyAsync(rows.data(), m->pf.att, rows.size() * 4, hipMemcpyDeviceToHost, s));
+    if (rec) MIO_HIP_CHECK(hipMemcpyAsync(rec, m->pf.act, (size_t)nt * rec_bytes, hipMemcpyDeviceToHost, s));
+    MIO_HIP_CHECK(hipMemcpyAsync(tickets, m->pf.att_cnt, (size_t)nt * D.n_kv * sizeof(int), hipMemcpyDeviceToHost, s));
+    MIO_HIP_CHECK(hipStreamSynchronize(s));
+    std::memcpy(att, rows.data(), (size_t)nt * KO * 4);
+    for (size_t e = 0; guard && e < KO; ++e)
+        MIO_REQUIRE(rows[(size_t)nt * KO + e] == MIO_DEBUG_SENTINEL_F32, MIO_ERR_HIP,
+                    "llm_debug_attention_multi: row %d of the outputs (past the %d tokens) was written", nt, nt);
     return MIO_OK;
 }
 

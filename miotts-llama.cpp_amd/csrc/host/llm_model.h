@@ -170,5 +170,9 @@ int prefill(mio_hip_llm *m, int n);
 constexpr int kRunDepth = 2;
 int run_wait(mio_hip_llm *m, int k);
 int run_mark(mio_hip_llm *m, int k);
+// llm_batch.cpp: the batch state (caches, states, logits) of B streams, allocated zeroed; a
+// state of another slot count is released first (its caches go). The batched entries call it, and
+// the parity entry that runs the multi-token attention on the slots' caches (llm_diag.cpp).
+int batch_ensure(mio_hip_llm *m, int B);
 
 #pragma GCC visibility pop

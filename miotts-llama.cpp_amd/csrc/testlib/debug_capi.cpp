@@ -221,6 +221,19 @@ extern "C" int mio_hip_llm_batch_conv_ring(mio_hip_llm *m, int slot, int il, flo
     return mio::llm_batch_conv_ring(m, slot, il, ring);
 }
 
+extern "C" int mio_hip_llm_batch_set_kv_rows(mio_hip_llm *m, int slot, int il, int p0, int n_pos, const uint16_t *k,
+                                             const uint16_t *v) {
+    return mio::llm_batch_set_kv_rows(m, slot, il, p0, n_pos, k, v);
+}
+
+extern "C" int mio_hip_llm_debug_attention_multi(mio_hip_llm *m, int il, int mode, int slots, int nt,
+                                                 const int32_t *pos, const int32_t *seq, const int32_t *frozen,
+                                                 const float *qkv, int att_q, int n_chunks, int reset, float *att,
+                                                 uint8_t *rec, int32_t *tickets) {
+    return mio::llm_debug_attention_multi(m, il, mode, slots, nt, pos, seq, frozen, qkv, att_q, n_chunks, reset, att,
+                                          rec, tickets);
+}
+
 extern "C" int mio_debug_batch_plan(mio_hip_llm *m, int B, int32_t *plan, int *n_sites, int32_t *lm_head) {
     return mio::llm_batch_plan(m, B, plan, n_sites, lm_head);
 }

@@ -163,6 +163,9 @@ def _declare(L: ctypes.CDLL) -> None:
         "mio_hip_llm_batch_logits": (c_int, [_vp, _vp]),
         "mio_hip_llm_batch_kv_rows": (c_int, [_vp, c_int, c_int, c_int, _vp, _vp]),
         "mio_hip_llm_batch_conv_ring": (c_int, [_vp, c_int, c_int, _vp]),
+        "mio_hip_llm_batch_set_kv_rows": (c_int, [_vp, c_int, c_int, c_int, c_int, _vp, _vp]),
+        "mio_hip_llm_debug_attention_multi": (c_int, [_vp, c_int, c_int, c_int, c_int, _vp, _vp, _vp, _vp, c_int,
+                                                      c_int, c_int, _vp, _vp, _vp]),
         "mio_debug_batch_plan": (c_int, [_vp, c_int, _vp, ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_int32)]),
         "mio_hip_llm_set_sampling": (c_int, [_vp, ctypes.POINTER(Sampling)]),
         "mio_hip_llm_get_sampling": (c_int, [_vp, ctypes.POINTER(Sampling)]),
@@ -756,6 +759,46 @@ class Llm:
         v = np.empty_like(k)
         check(lib().mio_hip_llm_batch_kv_rows(self.h, slot, il, n_pos, _ptr(k), _ptr(v)))
         return k, v
+
+    def batch_set_kv_rows(self, slot: int, il: int, p0: int, k: np.ndarray, v: np.ndarray) -> None:
+        """set_kv_rows on slot `slot` of the batched decode's caches (the inverse of batch_kv_rows;
+        test-support library)."""
+        k = np.ascontiguousarray(k, np.float16)
+        v = np.ascontiguousarray(v, np.float16)
+        assert k.shape == v.shape and k.ndim == 3 and k.shape[0] == self.n_kv and k.shape[2] == self.head_dim, k.shape
+        check(lib().mio_hip_llm_batch_set_kv_rows(self.h, slot, il, p0, k.shape[1], _ptr(k), _ptr(v)))
+
+    def debug_attention_multi(self, il: int, mode: int, slots: int, pos, seq, qkv: np.ndarray, frozen=None,
+                              att_q: int = -1, n_chunks: int = 0, reset: bool = True, nt: int = None):
+        """One call of the multi-token engine's attention of layer il (mode 0: the prefill pair, 1:
+        the batched step) for the tokens at pos[t] of sequence seq[t] on raw q|k|v rows qkv [nt,
+        (n_head + 2 n_kv) * head_dim]; slots 0: the handle's own cache, else the batch caches
+        (mio_hip_llm_debug_attention_multi, test-support library). Returns (att [nt, n_head,
+        head_dim], records, tickets [nt, n_kv]); records is None without att_q, else a dict of the
+        O matvec's act record fields per token: qs int8 [nt, K], d float32 [nt, K / 32 + 8], bs
+        int16 [nt, K / 16 + 8], K = n_head * head_dim. nt: passed as given (refusal tests)."""
+        pos = np.ascontiguousarray(pos, np.int32).reshape(-1)
+        seq = np.ascontiguousarray(seq, np.int32).reshape(-1)
+        n = pos.size
+        fr = None if frozen is None else np.ascontiguousarray(frozen, np.int32).reshape(-1)
+        qkv = np.ascontiguousarray(qkv, np.float32).reshape(n, -1)
+        assert seq.size == n and (fr is None or fr.size == n)
+        assert qkv.shape[1] == (self.n_head + 2 * self.n_kv) * self.head_dim, qkv.shape
+        K = self.n_head * self.head_dim
+        nd, nb = K // 32 + 8, K // 16 + 8
+        rb = (K + 4 * nd + 2 * nb + 15) & ~15
+        att = np.empty((n, self.n_head, self.head_dim), np.float32)
+        rec = np.zeros((n, rb), np.uint8)
+        tickets = np.full((n, self.n_kv), -1, np.int32)
+        check(lib().mio_hip_llm_debug_attention_multi(self.h, il, mode, slots, n if nt is None else nt, _ptr(pos),
+                                                      _ptr(seq), None if fr is None else _ptr(fr), _ptr(qkv), att_q,
+                                                      n_chunks, int(reset), _ptr(att), _ptr(rec), _ptr(tickets)))
+        records = None
+        if att_q >= 0:
+            records = {"qs": rec[:, :K].view(np.int8),
+                       "d": np.ascontiguousarray(rec[:, K:K + 4 * nd]).view(np.float32),
+                       "bs": np.ascontiguousarray(rec[:, K + 4 * nd:K + 4 * nd + 2 * nb]).view(np.int16)}
+        return att, records, tickets
 
     def batch_conv_ring(self, slot: int, il: int) -> np.ndarray:
         """conv_ring of slot `slot` of the batched decode: [4, n_embd] of short-conv layer il."""

@@ -23,7 +23,9 @@ tests need no allowance for flipped roundings.
 
 `bound` is the f32 error model of the kernels (derived in tests/test_attention_gpu.py);
 `chunked` restates the kernels' chunk / merge-batch structure in float64, which must agree with
-the plain softmax to rounding and carries the mutants of the CPU teeth test.
+the plain softmax to rounding and carries the mutants of the CPU teeth test. `multi` is the same
+operation for several tokens of several sequences in one launch (the multi-token engine's
+attention, tests/test_attention_multi_gpu.py), with mutants of its own.
 """
 from __future__ import annotations
 
@@ -131,10 +133,14 @@ class Model:
         pair = np.empty(hd, np.int64)   # element -> index of its rotation pair
         pair[i0] = pair[i1] = np.arange(hd // 2)
 
-        def bump(i, mag):
+        def bump(i, mag, away=0.0):
             # by a fraction of the element, or of the terms beside it where it is small against
-            # them (a zero raw value beside a bias)
-            raw[i] += np.float32((step - 1.0) * max(abs(raw[i]), mag)) * (-1 if raw[i] < 0 else 1)
+            # them (a zero raw value beside a bias). Beside a bias the element's own direction can
+            # shrink its term and then its pair's in turn, a cancelling rotation staying at y = 0
+            # while both decay: past the first 200 rounds (which stay as they were, and with them
+            # every input that converges there) the bump goes where |y| grows (away = y dy/draw)
+            sign = (-1 if away < 0 else 1) if away and rnd >= 200 and not self.qk_norm else (-1 if raw[i] < 0 else 1)
+            raw[i] += np.float32((step - 1.0) * max(abs(raw[i]), mag)) * sign
 
         for rnd in range(max_rounds):
             # 2^-13 .. 2^-12, another fraction every round: a fixed step can equal the f16 spacing
@@ -153,9 +159,12 @@ class Model:
                     # y[i0] = x0 c - x1 s, y[i1] = x0 s + x1 c
                     t0, t1 = (x[i0[j]] * c[j], x[i1[j]] * s[j]) if e == i0[j] else (x[i0[j]] * s[j], x[i1[j]] * c[j])
                     # under a norm the raw scale is arbitrary: there the element's own size is used
-                    bump(base + h * hd + (i0[j] if abs(t0) >= abs(t1) else i1[j]), 0.0 if self.qk_norm else mg[h, e])
+                    first = abs(t0) >= abs(t1)
+                    coef = (c[j] if first else -s[j]) if e == i0[j] else (s[j] if first else c[j])
+                    y = vals[0 if base == 0 else 1][h, e]
+                    bump(base + h * hd + (i0[j] if first else i1[j]), 0.0 if self.qk_norm else mg[h, e], y * coef)
             for h, e in zip(*np.nonzero(av)):
-                bump((H + Hk) * hd + h * hd + e, mags[2][h, e])
+                bump((H + Hk) * hd + h * hd + e, mags[2][h, e], vals[2][h, e])
         raise AssertionError(f"nudge: still ambiguous after {max_rounds} rounds")
 
 
@@ -239,6 +248,128 @@ def chunked(q: np.ndarray, K: np.ndarray, V: np.ndarray, mutant: str = None, arg
     return O / L
 
 
+# ---------------------------------------------------------------- several tokens in one launch
+MULTI_MUTANTS = ("see_next", "injected_row", "other_seq", "neighbour_row", "skip_low_chunk")
+
+
+def multi(model: "Model", caches: dict, tokens: list, mutant: str = None):
+    """The multi-token launches (k_pf_rope + k_pf_attention, k_bt_attention; llm_prefill.hip) of
+    layer 0 in float64. caches: {seq: (K16, V16)} f16 [Hkv, n, hd] (rows from n_ctx down to the
+    highest position + 2 serve); tokens: [(seq, pos, raw q|k|v row)] in launch order. Per sequence
+    every token's prepared k / v row replaces cache row pos first; token t then attends rows
+    0..pos_t of its own sequence.
+    -> (att [nt, H, hd], bound [nt, H, hd] (None for a mutant), rows [(k16, v16)] per token).
+    mutant (teeth of the tests): 'see_next' a token also sees row pos + 1 (the next token's, or
+    the cache's behind the last one: a missing causal mask among rows written before any token
+    attends); 'injected_row' a token reads the cache's row at pos as it was, not its own;
+    'other_seq' a token reads the next sequence's cache; 'neighbour_row' token t's output lands
+    in row t + 1 (cyclically); 'skip_low_chunk' a token in a higher chunk than the launch's lowest
+    token merges without chunk 0 (a neighbour's chunk count)."""
+    assert mutant is None or mutant in MULTI_MUTANTS
+    H, Hk, G, hd = model.n_head, model.n_kv, model.G, model.hd
+    prep = [model.prepare(0, raw, pos) for _, pos, raw in tokens]
+    n = max(pos for _, pos, _ in tokens) + 2
+    seqs = sorted(caches)
+    KV = {sq: (caches[sq][0][:, :n].astype(np.float64), caches[sq][1][:, :n].astype(np.float64)) for sq in seqs}
+    for (sq, pos, _), (_, k, v) in zip(tokens, prep):
+        KV[sq][0][:, pos], KV[sq][1][:, pos] = k, v
+    nt = len(tokens)
+    att = np.empty((nt, H, hd))
+    bnd = None if mutant else np.empty((nt, H, hd))
+    low = min(pos // CHUNK for _, pos, _ in tokens)
+    for t, ((sq, pos, _), (q, _, _)) in enumerate(zip(tokens, prep)):
+        src = seqs[(seqs.index(sq) + 1) % len(seqs)] if mutant == "other_seq" else sq
+        T = min(pos + 2, KV[src][0].shape[1]) if mutant == "see_next" else pos + 1
+        for kv in range(Hk):
+            Kh, Vh = KV[src][0][kv, :T], KV[src][1][kv, :T]
+            if mutant == "injected_row":
+                Kh, Vh = Kh.copy(), Vh.copy()
+                Kh[pos], Vh[pos] = caches[sq][0][kv, pos], caches[sq][1][kv, pos]
+            for h in range(kv * G, (kv + 1) * G):
+                if mutant == "skip_low_chunk" and pos // CHUNK > low:
+                    att[t, h] = chunked(q[h], Kh, Vh, "skip_chunk", 0)
+                    continue
+                att[t, h], s, w = attend(q[h], Kh, Vh)
+                if bnd is not None:
+                    bnd[t, h] = bound(q[h], Kh, Vh, s, w)
+    if mutant == "neighbour_row":
+        att = np.roll(att, 1, axis=0)
+    return att, bnd, [(k, v) for _, k, v in prep]
+
+
+def interleave(lists: list) -> list:
+    """Round robin over the lists until all are spent."""
+    out = []
+    for i in range(max(len(l) for l in lists)):
+        out += [l[i] for l in lists if i < len(l)]
+    return out
+
+
+# The multi-token cases (tests/test_attention_multi_gpu.py; their teeth in test_attention_ref.py).
+# (first position, tokens) of the prefill windows on the 32768-row cache: one chunk; one and two
+# chunks in one grid; 8 and 9 records (the merge-batch edge); mid range; the last chunk edge; the
+# end of the cache; single tokens
+MULTI_WINDOWS = ((0, 8), (60, 8), (505, 16), (4090, 11), (32700, 8), (32760, 8), (0, 1), (64, 1))
+MULTI_PATTERNS = ("census", "flat_census", "peaked40", "dominant", "far_apart", "vsubnormal")
+MULTI_N_CTX = 2048                      # of the full chunk, the admission lists and the batched step
+FULL_CHUNK = (1920, 128)                # kPrefillB tokens ending at the cache's last row
+FULL_PATTERNS = ("census", "peaked40")  # also the batched step's
+ADMISSION = ((0, 62, 5), (2, 1020, 8), (1, 0, 3))  # (slot, first position, tokens), interleaved
+STEP_POSITIONS = (0, 1, 63, 64, 65, 511, 512, 513, 1023, 1024, 2047)
+STEP_SLOTS = (1, 3, 16)
+# nudge rounds of these cases' raw rows: a k element whose rotation cancels (|y| below 2^-9 of its
+# terms: census keys beside a qwen2 bias) leaves its margin only after the bumps have added up
+NUDGE_ROUNDS = 2000
+
+
+def step_positions(slots: int) -> list:
+    """Ragged positions of the batched step's slots: 65, 513, 2047, 63, ... (every one of
+    STEP_POSITIONS among 16 slots)."""
+    return [STEP_POSITIONS[(3 * b + 4) % len(STEP_POSITIONS)] for b in range(slots)]
+
+
+def window_tokens(C: "Cases", pattern: str, p0: int, nt: int, seq: int = 0) -> list:
+    return [(seq, p, C.raw(p, pattern == "census", NUDGE_ROUNDS)) for p in range(p0, p0 + nt)]
+
+
+def window_edits(C: "Cases", pattern: str, p0: int) -> list:
+    """Cases.edits at the window's first position (rows below every token of the window); a
+    pattern without sub-cases there runs on its plain state."""
+    return C.edits(pattern, p0) or [("", [])]
+
+
+def stale(V: np.ndarray, p0: int, nt: int) -> None:
+    """The injected V rows [p0, p0 + nt) rotated by one dimension, in place: the rows a launch
+    overwrites hold something else than it writes (the census row of a position is the very row
+    its token appends), so a token that reads the cache's row instead of its own shows."""
+    V[:, p0:p0 + nt] = np.roll(V[:, p0:p0 + nt], 1, axis=2)
+
+
+def slot_state(C: "Cases", pattern: str, p0: int, nt: int = 1):
+    """A slot's cache [Hkv, n_ctx, hd] for nt tokens from p0 on: the pattern's state with the last
+    sub-case of window_edits in place (dominant: the dominant row just below p0) and the tokens'
+    rows stale."""
+    K, V = C.state(pattern)
+    K, V = K.copy(), V.copy()
+    for t, kr, vr in window_edits(C, pattern, p0)[-1][1]:
+        K[:, t], V[:, t] = kr, vr
+    stale(V, p0, nt)
+    return K, V
+
+
+def admission_case(S: list, pattern: str):
+    """(caches, tokens) of the flattened admission list: S[slot] = that slot's Cases."""
+    caches = {s: slot_state(S[s], pattern, p0, n) for s, p0, n in ADMISSION}
+    return caches, interleave([window_tokens(S[s], pattern, p0, n, s) for s, p0, n in ADMISSION])
+
+
+def step_case(S: list, pattern: str, slots: int, positions: list = None):
+    """(caches, tokens) of one batched step: slot b's token at step_positions(slots)[b]."""
+    positions = positions or step_positions(slots)
+    caches = {s: slot_state(S[s], pattern, p) for s, p in enumerate(positions)}
+    return caches, [(s, p, S[s].raw(p, pattern == "census", NUDGE_ROUNDS)) for s, p in enumerate(positions)]
+
+
 # ---------------------------------------------------------------- cases of the attention tests
 N_CTX = 32768
 # first chunk edge; 8 -> 9 and 16 -> 17 records (merge batches); mid range; the last chunk
@@ -274,7 +405,7 @@ class Cases:
         self.seed = seed
 
     # ---- raw q|k|v rows
-    def raw(self, pos: int, census: bool = False) -> np.ndarray:
+    def raw(self, pos: int, census: bool = False, max_rounds: int = 200) -> np.ndarray:
         m = self.m
         H, Hk, hd = m.n_head, m.n_kv, m.hd
         L = m.layers[0]
@@ -296,7 +427,7 @@ class Cases:
             v[:] = 0.0
             v[:, pos % hd] = 1.0
         raw = np.concatenate([x.reshape(-1), k.reshape(-1), v.reshape(-1)]).astype(np.float32)
-        return m.nudge(0, raw, pos)
+        return m.nudge(0, raw, pos, max_rounds)
 
     # ---- cached states
     def keys(self, c: np.ndarray) -> np.ndarray:

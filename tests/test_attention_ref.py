@@ -21,6 +21,20 @@ head: a kernel with that defect would fail the GPU test at that case.
 A whole chunk missing from the census at a position that is a multiple of 64 removes one count
 from each of hd = 64 dimensions alike and leaves the mean unchanged: the census sees a skipped
 chunk at hd 128 (and at 4096 + 1 positions), the dominant and peaked patterns see it at hd 64.
+
+Several tokens in one launch (tests/test_attention_multi_gpu.py; np_attn.multi and its mutants):
+for every launch shape of that file (each prefill window, the full chunk, the admission list, the
+batched step on 1, 3 and 16 slots) and every pattern it runs there, the unmutated reference
+evaluated chunk-wise stays inside the bound, and every mutant that can occur in the shape leaves
+the bound in at least one pattern (the GPU test runs all of them on the shape):
+
+  a token also sees row pos + 1            every shape
+  a token reads the injected row at pos    every shape (the injected rows are stale: np_attn.stale)
+  a token's output lands in the next row   two tokens or more
+  a token merges with a neighbour's        tokens with different chunk counts in one launch
+  chunk count (no chunk 0)
+  a token reads another sequence's cache   launches on batch slots (the handle's own cache is
+                                           one sequence at offset 0: there is no other to read)
 """
 import numpy as np
 import pytest
@@ -149,3 +163,92 @@ def test_mutants_leave_the_bound(cases, preset):
     print(ratios)
     weak = {k: v for k, v in ratios.items() if not v > 1.0}
     assert not weak, weak
+
+
+# ---------------------------------------------------------------- several tokens in one launch
+def _multi_teeth(model, cases, mutants):
+    """cases: [(label, caches, tokens)], one per pattern and sub-case of one launch shape. The
+    unmutated reference, evaluated chunk-wise, stays inside the bound in every case; returns
+    {mutant: {label: worst err / bound over the launch's outputs}}."""
+    out = {mu: {} for mu in mutants}
+    for label, caches, tokens in cases:
+        att, bnd, _ = A.multi(model, caches, tokens)
+        assert np.isfinite(bnd).all() and (bnd > 0).all(), label
+        for t in {0, len(tokens) - 1}:  # the chunk / merge-batch restatement of the same launch
+            sq, pos, raw = tokens[t]
+            q = model.prepare(0, raw, pos)[0]
+            K, V = caches[sq][0][:, :pos + 1].astype(np.float64), caches[sq][1][:, :pos + 1].astype(np.float64)
+            for s2, p2, r2 in tokens:
+                if s2 == sq and p2 <= pos:
+                    _, K[:, p2], V[:, p2] = model.prepare(0, r2, p2)
+            for h in (0, model.n_head - 1):
+                kv = h // model.G
+                assert _worst(A.chunked(q[h], K[kv], V[kv]), att[t, h], bnd[t, h]) < 1e-6, (label, t, h)
+        for mu in mutants:
+            out[mu][label] = _worst(A.multi(model, caches, tokens, mu)[0], att, bnd)
+    return out
+
+
+def _assert_teeth(ratios, where):
+    """Every mutant leaves the bound in at least one pattern of the launch shape: the GPU test
+    runs every pattern on it, so a kernel with that defect fails there."""
+    print(where, {mu: {k: float(f"{v:.3g}") for k, v in r.items()} for mu, r in ratios.items()})
+    weak = {mu: r for mu, r in ratios.items() if not max(r.values()) > 1.0}
+    assert not weak, (where, weak)
+
+
+def _window_mutants(p0, nt):
+    mutants = ["see_next", "injected_row"]
+    if nt > 1:
+        mutants.append("neighbour_row")
+    if p0 // A.CHUNK != (p0 + nt - 1) // A.CHUNK:  # tokens with different chunk counts
+        mutants.append("skip_low_chunk")
+    return mutants
+
+
+@pytest.mark.parametrize("window", A.MULTI_WINDOWS, ids=lambda w: f"{w[0]}+{w[1]}")
+@pytest.mark.parametrize("preset", (5, 17))
+def test_multi_token_mutants_leave_the_bound(cases, preset, window):
+    """The prefill windows of tests/test_attention_multi_gpu.py, every pattern: a token that also
+    sees the row behind its position, that reads the cache's row at its position, whose output lands
+    in the next row, or (windows across a chunk edge) that merges without its lowest chunk."""
+    _, C = cases[preset]
+    p0, nt = window
+    runs = []
+    for pattern in A.MULTI_PATTERNS:
+        K16, V16 = C.state(pattern)
+        tokens = A.window_tokens(C, pattern, p0, nt)
+        for label, edit in A.window_edits(C, pattern, p0):
+            K, V = K16[:, :p0 + nt + 1].copy(), V16[:, :p0 + nt + 1].copy()
+            for t, kr, vr in edit:
+                K[:, t], V[:, t] = kr, vr
+            A.stale(V, p0, nt)
+            runs.append((f"{pattern} {label}".strip(), {0: (K, V)}, tokens))
+    _assert_teeth(_multi_teeth(C.m, runs, _window_mutants(p0, nt)), (preset, window))
+
+
+@pytest.fixture(scope="module")
+def slot_cases(cases):
+    """Per preset, one Cases per slot (seed = slot + 1) at the short context of the multi-sequence
+    launches."""
+    return {p: [A.Cases(A.Model(cases[p][0]), seed=s + 1, n_ctx=A.MULTI_N_CTX) for s in range(max(A.STEP_SLOTS))]
+            for p in (5, 17)}
+
+
+@pytest.mark.parametrize("preset", (5, 17))
+def test_multi_sequence_mutants_leave_the_bound(slot_cases, preset):
+    """The full chunk, the flattened admission list and the batched step of the GPU test: beside the
+    window mutants, a token that reads another sequence's cache."""
+    S = slot_cases[preset]
+    mod = S[0].m
+    p0, nt = A.FULL_CHUNK
+    runs = [(pattern, {0: A.slot_state(S[0], pattern, p0, nt)}, A.window_tokens(S[0], pattern, p0, nt))
+            for pattern in A.FULL_PATTERNS]
+    _assert_teeth(_multi_teeth(mod, runs, _window_mutants(p0, nt)), (preset, "full chunk"))
+    runs = [(pattern,) + A.admission_case(S, pattern) for pattern in A.MULTI_PATTERNS]
+    _assert_teeth(_multi_teeth(mod, runs, A.MULTI_MUTANTS), (preset, "admission"))
+    for slots in A.STEP_SLOTS:
+        runs = [(pattern,) + A.step_case(S, pattern, slots) for pattern in A.FULL_PATTERNS]
+        # one token per sequence: the row behind it is the cache's; one slot has no neighbour
+        mutants = ("see_next", "injected_row") if slots == 1 else A.MULTI_MUTANTS
+        _assert_teeth(_multi_teeth(mod, runs, mutants), (preset, "step", slots))

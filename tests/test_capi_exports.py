@@ -40,7 +40,8 @@ def test_test_support_symbols_live_in_the_test_library():
     declared = _declared_symbols(test_header=True)
     assert {"mio_synth_llm_gguf", "mio_hip_debug_matvec", "mio_quantize_rows", "mio_hip_llm_set_kv_rows",
             "mio_hip_llm_debug_attention", "mio_hip_llm_batch_state", "mio_hip_llm_batch_logits",
-            "mio_hip_llm_batch_kv_rows", "mio_hip_llm_batch_conv_ring", "mio_debug_batch_plan"} <= declared
+            "mio_hip_llm_batch_kv_rows", "mio_hip_llm_batch_conv_ring", "mio_debug_batch_plan",
+            "mio_hip_llm_batch_set_kv_rows", "mio_hip_llm_debug_attention_multi"} <= declared
     assert libs.test is not None
     missing = [n for n in sorted(declared) if not hasattr(libs.test, n)]
     assert not missing, f"declared but not exported: {missing}"
