@@ -126,6 +126,24 @@ int mio_hip_codec_decode_pcm(mio_hip_codec *c, const int32_t *codes, int n_codes
 int mio_hip_codec_decode_pcm_batch(mio_hip_codec *c, const int32_t *const *codes, const int *n_codes, int B,
                                    const float *global_emb, float *const *out_pcm, int *out_len,
                                    unsigned flags, void *stream);
+/* B utterances (1 <= B <= 16, every n_codes[b] >= 1) of different lengths, each with its own
+ * voice global_emb[b] ([128]), as ONE packed decode: the activations are concatenated along the
+ * row axis ([sum of rows][channels]) and run through one launch set whose attention, convolutions,
+ * GroupNorm statistics, ConvTranspose windows and AdaLN conditioning stop at the utterance
+ * boundaries (a row's value depends on its own utterance only). The fused iSTFT then runs once
+ * per utterance on its slice of the packed spectrogram. out_pcm[b] receives
+ * n_codes[b] * samples_per_token samples (*out_len[b]). With the default settings they are
+ * bit-identical to mio_hip_codec_decode_pcm of the same codes and voice (every GEMM runs with the
+ * K-groups the utterance's own decode takes, every other kernel sums in the single decode's
+ * default order); an A/B switch of the environment that changes the single decode's order of
+ * summation (MIO_GN = 1 or 5) is not followed here, and the two then agree to rounding only.
+ * Flags as mio_hip_codec_decode_pcm_batch (no MIO_CODEC_INCREMENTAL). Null pointers,
+ * B, the lengths and, for host codes, every code of every utterance are checked before anything
+ * is allocated or queued: a refused call leaves no work on the device. last_flops / last_timings
+ * ([0] the packed decode, [1] the iSTFTs) report the call. */
+int mio_hip_codec_decode_pcm_packed(mio_hip_codec *c, const int32_t *const *codes, const int *n_codes, int B,
+                                    const float *const *global_emb, float *const *out_pcm, int *out_len,
+                                    unsigned flags, void *stream);
 /* Debug/parity: run up to `stage` and copy that activation to host `out` (stage list as
  * in oracle/mio_oracle.h: 0 embed .. 7+U spectrogram). rows/cols receive its shape. */
 int mio_hip_codec_decode_stage(mio_hip_codec *c, const int32_t *codes, int n_codes,

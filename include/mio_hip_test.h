@@ -223,6 +223,15 @@ int mio_hip_debug_codec_cond_gemv(mio_hip_device *d, const float *W, const float
 int mio_hip_debug_codec_embed(mio_hip_device *d, const float *table, int n_rows, int D, const int32_t *codes,
                               int T, float *x, int *guards_ok);
 
+/* The packed counterpart of mio_hip_codec_decode_stage: runs mio_hip_codec_decode_pcm_packed's
+ * launch set for B utterances (host codes[b][n_codes[b]], one embedding global_emb[b] each) up to
+ * `stage` and copies the packed activation to `out` ([rows][cols], utterance b in rows
+ * [seg_off[b], seg_off[b + 1])); seg_off receives B + 1 offsets. `out` has room for out_cap
+ * floats: a stage of more is refused and nothing is written. Refusals as the packed entry. */
+int mio_hip_debug_codec_decode_stage_packed(mio_hip_codec *c, const int32_t *const *codes, const int *n_codes,
+                                            int B, const float *const *global_emb, int stage, float *out,
+                                            size_t out_cap, int *rows, int *cols, int *seg_off);
+
 /* ---------------- synthetic model files ----------------
  * No GGUF model files exist offline. These write files with the
  * reference's tensor names and KV keys (miocodec.cpp:448-481, 599-728;

@@ -141,10 +141,22 @@ public:
                                    const std::vector<std::string> & texts,
                                    const std::vector<std::string> & output_paths,
                                    const Options & options);
+    // (extension) the same with one voice per utterance (voices.size() == texts.size()): the
+    // codec decodes each group of up to 16 utterances, whatever their lengths and voices, as one
+    // packed decode (mio_hip_codec_decode_pcm_packed). Each file has the bytes synthesize_to_file
+    // writes with that voice.
+    bool synthesize_batch_to_files(const std::vector<VoiceModel> & voices,
+                                   const std::vector<std::string> & texts,
+                                   const std::vector<std::string> & output_paths,
+                                   const Options & options);
 
     struct Impl;  // GPU handles (device, LLM runner, codec, tokenizer)
 
 private:
+    bool batch_to_files(const VoiceModel * voices, bool per_utterance,
+                        const std::vector<std::string> & texts,
+                        const std::vector<std::string> & output_paths,
+                        const Options & options);
     Config config_;
     std::unique_ptr<Impl> impl_;
 };

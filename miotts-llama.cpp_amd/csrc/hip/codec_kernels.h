@@ -81,4 +81,60 @@ void launch_embed(const float *table, const int *codes, int T, int D, float *x, 
 void launch_cond_gemv(const float *W, const float *b, const float *e, int R, int A, float *y, int e_f16,
                       hipStream_t s);
 
+// ---------------------------------------------------------------- packed decode
+// (csrc/hip/codec_packed.hip) B <= kSegMax utterances concatenated along the row axis. `off`
+// is a device array of B + 1 ascending row offsets (segment b = rows [off[b], off[b + 1]),
+// never empty) at the resolution of the activation the kernel works on. Every packed
+// activation stays under 2 GiB (32-bit buffer offsets; the host entry checks it).
+constexpr int kSegMax = 16;
+
+// K-groups launch_gemm_f32 gives a GEMM of `tiles` 64 x 64 tiles (1, 2 or 4). The packed decode
+// runs every GEMM with the K-groups its segments' single decodes take, so that a segment's rows
+// are its single-decode rows bit for bit.
+int gemm_kgroups(long tiles);
+
+// C = A * B^T with a tap-window A clipped to the row's segment and a per-segment epilogue.
+// GEMM row m of segment b (m_off) reads source rows a_off[b] + (m - m_off[b]) - (taps - 1) + j,
+// j < taps, of that segment only (others are zero). EPI_GATED (taps 1, m_off = a_off = c_off):
+// C[m][n] += aux[b * aux_ld + n] * acc. EPI_CONVT_SNAKE: row f * (m - m_off[b]) + n / cout - trim
+// of segment b's c_off rows = snake(acc + bias). K % 4 == 0, a_seg % 4 == 0 as GemmArgs.
+// The launch covers GEMM rows [m_begin, M) = segments [0, nseg) of the three tables (pass them
+// from the run's first segment on) and sums every output in the order of launch_gemm_f32_cfg
+// with kg K-groups.
+struct SegGemmArgs {
+    const float *A;
+    int a_seg, taps;
+    const float *B;   // [N][K], K = taps * a_seg
+    int M, N, K;      // M = m_off[nseg]
+    int m_begin, kg;  // m_begin = m_off[0]; kg = 1, 2, 4
+    float *C;
+    int ldc;
+    const float *bias, *aux, *aux2;
+    int aux_ld;       // floats between two segments' gates (EPI_GATED)
+    int f, trim, cout;
+    int a_f16;
+    int nseg;
+    const int *m_off, *a_off, *c_off;
+};
+void launch_seg_gemm(const SegGemmArgs &a, int epi /*EPI_GATED | EPI_CONVT_SNAKE*/, hipStream_t s);
+// launch_conv_f16 over packed rows (a.L = off[B]) with zero padding at every segment edge.
+// M-tile 64: a tile whose rows and taps lie in one segment runs the single decode's loads.
+constexpr int kSegConvTileM = 64;
+void launch_seg_conv_f16(const ConvArgs &a, const int *off, int B, hipStream_t s);
+// launch_rownorm mode 2 with shift / scale [B][ld], row m taking its segment's.
+void launch_seg_rownorm(const float *x, float *y, int M, int D, float eps, const float *shift, const float *scale,
+                        int ld, const int *off, int B, hipStream_t s);
+// launch_groupnorm_apply with (mean, rstd) per (segment, group); Lmax = the longest segment.
+// part: kSegGnPartDoubles doubles ([2][kSegMax][128 slices][64 groups]). Three launches.
+constexpr int kSegGnPartDoubles = 2 * kSegMax * 128 * 64;
+void launch_seg_groupnorm_apply(const float *x, const int *off, int B, int Lmax, int C, int G, float eps,
+                                const float *gamma, const float *beta, double *part, _Float16 *xa, hipStream_t s);
+// launch_band_attention per segment: band clipped to the segment, rope [Smax][32] by the
+// position inside it.
+void launch_seg_band_attention(const float *qkv, float *out, const int *off, int B, int Smax, int H, int window,
+                               const float2 *rope, hipStream_t s);
+// y[b][r] = W[r][:] . silu(e[b]) + bias[r] for B <= kSegMax embeddings e [B][A]; y [B][R]
+void launch_cond_gemv_batch(const float *W, const float *b, const float *e, int R, int A, int B, float *y, int e_f16,
+                            hipStream_t s);
+
 }  // namespace mio

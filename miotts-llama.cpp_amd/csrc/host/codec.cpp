@@ -12,12 +12,14 @@
 //    (:623, :638, :663, :712) and the host interleave (:801-808) disappear: the head
 //    GEMM writes the [frame][bin][re,im] spectrogram directly, and decode_pcm feeds it
 //    to the fused iSTFT without leaving the GPU.
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <initializer_list>
 #include <string>
 #include <vector>
 
+#include "codec_debug.h"
 #include "codec_kernels.h"
 #include "common.h"
 #include "gguf.h"
@@ -97,9 +99,25 @@ struct mio_hip_codec {
     std::vector<int32_t> pc_codes;
     int pc_last_reused = 0;  // rows the last decode took from the cache (diagnostic)
     double last_flops = 0.0;  // algorithmic FLOPs of the last decode_pcm (codec_roofline)
+    // mio_hip_codec_decode_pcm_packed: the segment tables, the B embeddings, their conditioning
+    // vectors and the GroupNorm partials (one fixed-size block, see plan_packed), the PCM of
+    // the per-segment iSTFTs of a call with host outputs, and the pinned host staging of what is
+    // uploaded (tables, embeddings, codes): pk_up is recorded behind the uploads, and the next
+    // call waits for it before it rewrites the staging
+    char *pk = nullptr;
+    float *pk_pcm = nullptr;
+    size_t pk_pcm_cap = 0;
+    char *pk_stage = nullptr;
+    size_t pk_stage_cap = 0;
+    hipEvent_t pk_up = nullptr;
+    std::vector<int> pk_tab;
 
     ~mio_hip_codec() {
         if (d) hipSetDevice(d->dev);
+        if (pk_up) hipEventSynchronize(pk_up), hipEventDestroy(pk_up);
+        if (pk_stage) hipHostFree(pk_stage);
+        if (pk) hipFree(pk);
+        if (pk_pcm) hipFree(pk_pcm);
         for (void *p : allocs) hipFree(p);
         if (rope) hipFree(rope);
         if (ws) hipFree(ws);
@@ -983,6 +1001,431 @@ extern "C" int mio_hip_codec_decode_pcm_batch(mio_hip_codec *c, const int32_t *c
     MIO_HIP_CHECK(hipEventRecord(c->ev[2], s));
     c->timed = true;
     c->last_flops = flops;
+    if (!(flags & MIO_OUT_DEVICE)) MIO_HIP_CHECK(hipStreamSynchronize(s));
+    return MIO_OK;
+}
+
+// ---------------------------------------------------------------- packed decode
+// B utterances concatenated along the row axis, one launch set (csrc/hip/codec_packed.hip).
+namespace {
+
+// Segment tables, kSegMax + 1 row offsets each: codes, the decoder's 2T rows, every upsampler
+// stage's output rows, and every upsampler stage's GEMM rows (a ConvT with kernel > stride has
+// (K - trim - 1) / f more GEMM rows than source rows per segment).
+enum { PK_T = 0, PK_S = 1, PK_U = 2, PK_M = 6, PK_TABLES = 10, PK_LD = mio::kSegMax + 1 };
+
+struct Pk {
+    int B = 0;
+    const int *h = nullptr;  // host tables [PK_TABLES][PK_LD]
+    int *d = nullptr;        // the same on the device
+    float *emb = nullptr, *cond = nullptr;
+    double *gnp = nullptr;
+    size_t pcm_off[mio::kSegMax + 1] = {};  // floats, per segment, in c->pk_pcm
+    const int *host(int r) const { return h + r * PK_LD; }
+    const int *dev(int r) const { return d + r * PK_LD; }
+    int total(int r) const { return host(r)[B]; }
+    int longest(int r) const {
+        int m = 0;
+        for (int b = 0; b < B; ++b) m = std::max(m, host(r)[b + 1] - host(r)[b]);
+        return m;
+    }
+};
+
+// byte offsets of the embeddings and of the codes in the pinned staging (tables at 0)
+constexpr size_t kPkStageEmb = 1024;
+size_t pk_stage_codes(const mio_hip_codec *c) { return kPkStageEmb + (size_t)mio::kSegMax * c->adaln * 4; }
+
+// the table of the spectrogram's rows (frames)
+int frames_table(const mio_hip_codec *c) { return c->up_stages ? PK_U + c->up_stages - 1 : PK_S; }
+
+// Arguments of the packed entries, checked before anything is allocated or queued.
+int packed_check(const mio_hip_codec *c, const int32_t *const *codes, const int *n_codes, int B,
+                 const float *const *embs, unsigned flags) {
+    MIO_REQUIRE(c && codes && n_codes && embs, MIO_ERR_INVALID, "codec_decode_pcm_packed: null argument");
+    MIO_REQUIRE(B >= 1 && B <= mio::kSegMax, MIO_ERR_INVALID, "codec_decode_pcm_packed: %d utterances outside [1, %d]",
+                B, mio::kSegMax);
+    MIO_REQUIRE(!(flags & MIO_CODEC_INCREMENTAL), MIO_ERR_INVALID, "codec_decode_pcm_packed: no incremental decodes");
+    for (int b = 0; b < B; ++b)
+        MIO_REQUIRE(codes[b] && embs[b] && n_codes[b] >= 1, MIO_ERR_INVALID,
+                    "codec_decode_pcm_packed: utterance %d: null codes or embedding, or no codes", b);
+    if (!(flags & MIO_IN_DEVICE))
+        for (int b = 0; b < B; ++b)
+            for (int i = 0; i < n_codes[b]; ++i)
+                MIO_REQUIRE(codes[b][i] >= 0 && codes[b][i] < c->n_codes, MIO_ERR_INVALID,
+                            "miocodec: utterance %d: code %d at %d outside [0, %d)", b, codes[b][i], i, c->n_codes);
+    return MIO_OK;
+}
+
+// Tables, workspace and the packed block, all allocated here (before the first launch).
+// The workspace is plan_ws's for sum T + B codes: a stage's packed rows are
+// sum_b (F 2T_b + D) against F 2(sum T + B) + D for the single chain (F the product of the
+// stage factors, 0 <= D < 2F the kernel-minus-stride remainders), so B more codes cover them.
+// host_pcm: the call returns its PCM in host memory, so the iSTFTs write to the handle's buffer.
+int plan_packed(mio_hip_codec *c, const int *n_codes, int B, bool host_pcm, Ws &w, Pk &pk) {
+    std::vector<int> &t = c->pk_tab;
+    t.assign((size_t)PK_TABLES * PK_LD, 0);
+    long tsum = 0;
+    for (int b = 0; b < B; ++b) tsum += n_codes[b];
+    MIO_REQUIRE(tsum + B < (1 << 24), MIO_ERR_INVALID, "codec_decode_pcm_packed: %ld codes", tsum);
+    for (int b = 0; b < B; ++b) {
+        t[PK_T * PK_LD + b + 1] = t[PK_T * PK_LD + b] + n_codes[b];
+        t[PK_S * PK_LD + b + 1] = t[PK_S * PK_LD + b] + 2 * n_codes[b];
+        int L = 2 * n_codes[b];
+        for (int st = 0; st < c->up_stages; ++st) {
+            const UpW &u = c->ups[st];
+            const int Lout = (L - 1) * u.f + u.K - 2 * u.trim;
+            t[(PK_U + st) * PK_LD + b + 1] = t[(PK_U + st) * PK_LD + b] + Lout;
+            t[(PK_M + st) * PK_LD + b + 1] = t[(PK_M + st) * PK_LD + b] + (Lout - 1 + u.trim) / u.f + 1;
+            L = Lout;
+        }
+    }
+    pk.B = B;
+    pk.h = t.data();
+    int rc = plan_ws(c, (int)tsum + B, w, true);
+    if (rc) return rc;
+    {   // 32-bit buffer offsets in every kernel: the widest packed activations under 2 GiB
+        const double T = (double)tsum + B, S = 2 * T;
+        double worst = std::max({T * 3 * c->pre_dim, T * c->pre_ff, S * 3 * c->dec_dim, S * c->dec_ff,
+                                 (double)w.Lf * 2 * c->n_freq, (double)w.Lf * c->dec_dim});
+        for (int st = 0; st < c->up_stages; ++st)
+            worst = std::max(worst, (double)w.uL[st] * std::max(c->ups[st].Cout, c->ups[st].taps * c->ups[st].Cin));
+        MIO_REQUIRE(worst * 4 < 2147483648.0, MIO_ERR_INVALID,
+                    "codec_decode_pcm_packed: %ld codes make an activation of 2 GiB or more", tsum);
+    }
+    const size_t o_emb = 1024, o_cond = align_up(o_emb + (size_t)mio::kSegMax * c->adaln * 4, 256),
+                 o_gnp = align_up(o_cond + (size_t)mio::kSegMax * c->cond_rows * 4, 256),
+                 bytes = o_gnp + (size_t)mio::kSegGnPartDoubles * 8;
+    static_assert(PK_TABLES * PK_LD * 4 <= 1024, "segment tables");
+    if (!c->pk) MIO_HIP_CHECK(hipMalloc(&c->pk, bytes));
+    pk.d = (int *)c->pk;
+    pk.emb = (float *)(c->pk + o_emb);
+    pk.cond = (float *)(c->pk + o_cond);
+    pk.gnp = (double *)(c->pk + o_gnp);
+    const int *F = pk.host(frames_table(c));
+    for (int b = 0; b < B; ++b)
+        pk.pcm_off[b + 1] = align_up(pk.pcm_off[b] + (size_t)(F[b + 1] - F[b]) * c->hop + c->n_fft, 64);
+    if (host_pcm && pk.pcm_off[B] > c->pk_pcm_cap) {
+        if (c->pk_pcm) hipFree(c->pk_pcm);
+        c->pk_pcm = nullptr, c->pk_pcm_cap = 0;
+        MIO_HIP_CHECK(hipMalloc(&c->pk_pcm, pk.pcm_off[B] * 4));
+        c->pk_pcm_cap = pk.pcm_off[B];
+    }
+    // pinned staging: tables | kSegMax embeddings | codes. The previous call's uploads read it
+    // asynchronously, so they are waited for before it is rewritten (packed_inputs) or regrown.
+    if (!c->pk_up) MIO_HIP_CHECK(hipEventCreateWithFlags(&c->pk_up, hipEventDisableTiming));
+    MIO_HIP_CHECK(hipEventSynchronize(c->pk_up));
+    const size_t need = pk_stage_codes(c) + (size_t)tsum * 4;
+    if (need > c->pk_stage_cap) {
+        if (c->pk_stage) hipHostFree(c->pk_stage);
+        c->pk_stage = nullptr, c->pk_stage_cap = 0;
+        MIO_HIP_CHECK(hipHostMalloc((void **)&c->pk_stage, need, hipHostMallocDefault));
+        c->pk_stage_cap = need;
+    }
+    return MIO_OK;
+}
+
+// Tables, codes and embeddings to the device. What comes from the host is gathered into the
+// handle's pinned staging (plan_packed has waited for the previous call's uploads), one copy
+// each; pk_up marks the point of the stream behind which the staging may change again.
+int packed_inputs(mio_hip_codec *c, const Ws &w, const Pk &pk, const int32_t *const *codes, const int *n_codes,
+                  const float *const *embs, unsigned flags, hipStream_t s) {
+    const int B = pk.B, A = c->adaln;
+    const size_t tab_bytes = (size_t)PK_TABLES * PK_LD * 4;
+    std::memcpy(c->pk_stage, pk.h, tab_bytes);
+    MIO_HIP_CHECK(hipMemcpyAsync(pk.d, c->pk_stage, tab_bytes, hipMemcpyHostToDevice, s));
+    const int *T = pk.host(PK_T);
+    if (flags & MIO_IN_DEVICE) {
+        for (int b = 0; b < B; ++b) {
+            MIO_HIP_CHECK(hipMemcpyAsync(w.codes + T[b], codes[b], (size_t)n_codes[b] * 4, hipMemcpyDeviceToDevice, s));
+            MIO_HIP_CHECK(hipMemcpyAsync(pk.emb + (size_t)b * A, embs[b], (size_t)A * 4, hipMemcpyDeviceToDevice, s));
+        }
+    } else {
+        float *he = (float *)(c->pk_stage + kPkStageEmb);
+        int32_t *hc = (int32_t *)(c->pk_stage + pk_stage_codes(c));
+        for (int b = 0; b < B; ++b) {
+            std::memcpy(hc + T[b], codes[b], (size_t)n_codes[b] * 4);
+            std::memcpy(he + (size_t)b * A, embs[b], (size_t)A * 4);
+        }
+        MIO_HIP_CHECK(hipMemcpyAsync(w.codes, hc, (size_t)T[B] * 4, hipMemcpyHostToDevice, s));
+        MIO_HIP_CHECK(hipMemcpyAsync(pk.emb, he, (size_t)B * A * 4, hipMemcpyHostToDevice, s));
+    }
+    MIO_HIP_CHECK(hipEventRecord(c->pk_up, s));
+    return MIO_OK;
+}
+
+void seg_band_launch(const float *qkv, float *out, const Pk &pk, int res, int H, int win, const float2 *rope,
+                     hipStream_t s) {
+    const int h = win / 2;
+    for (int b = 0; b < pk.B; ++b) {
+        const int S = pk.host(res)[b + 1] - pk.host(res)[b];
+        double pairs = 0;
+        for (int i = 0; i < S; ++i) pairs += std::min(S - 1, i + h) - std::max(0, i - h) + 1;
+        t_flops += 4.0 * pairs * H * 64;
+    }
+    mio::launch_seg_band_attention(qkv, out, pk.dev(res), pk.B, pk.longest(res), H, win, rope, s);
+}
+
+void seg_resnet(mio_hip_codec *c, const ResW &r, float *x, float *t, const Pk &pk, int res, int C, const Ws &w,
+                hipStream_t s) {
+    const int L = pk.total(res), Lmax = pk.longest(res);
+    const int *off = pk.dev(res);
+    mio::ConvArgs a{};
+    a.L = L, a.Cin = C, a.taps = 3, a.pad = 1, a.Cout = C, a.Xa = w.xa;
+    mio::launch_seg_groupnorm_apply(x, off, pk.B, Lmax, C, c->groups, c->gn_eps, r.gn1_w, r.gn1_b, pk.gnp, w.xa, s);
+    a.B = r.w1, a.bias = r.b1, a.Y = t, a.resid = nullptr;
+    t_flops += 2.0 * a.L * a.Cout * a.taps * a.Cin;
+    mio::launch_seg_conv_f16(a, off, pk.B, s);
+    mio::launch_seg_groupnorm_apply(t, off, pk.B, Lmax, C, c->groups, c->gn_eps, r.gn2_w, r.gn2_b, pk.gnp, w.xa, s);
+    a.B = r.w2, a.bias = r.b2, a.Y = x, a.resid = x;
+    t_flops += 2.0 * a.L * a.Cout * a.taps * a.Cin;
+    mio::launch_seg_conv_f16(a, off, pk.B, s);
+}
+
+// Runs [b0, b1) of consecutive segments whose single decodes run a GEMM of N columns (rows:
+// table `res`) with the same K-groups kg: f(b0, b1, kg). A packed GEMM is one launch per run
+// with that kg, so a segment's sums run in its single decode's order; utterances of similar
+// lengths are one run.
+template <class F>
+void kg_runs(const Pk &pk, int res, int N, F &&f) {
+    const int *o = pk.host(res);
+    auto kg = [&](int b) { return mio::gemm_kgroups((long)((o[b + 1] - o[b] + 63) / 64) * ((N + 63) / 64)); };
+    for (int b0 = 0; b0 < pk.B;) {
+        const int k = kg(b0);
+        int b1 = b0 + 1;
+        while (b1 < pk.B && kg(b1) == k) ++b1;
+        f(b0, b1, k);
+        b0 = b1;
+    }
+}
+
+// A row-independent GEMM (a_row_off 0; EPI_CONVT: kernel = stride, no trim) over the packed
+// rows of table `res`, through the single decode's kernel, run by run.
+void packed_gemm(const Pk &pk, int res, const mio::GemmArgs &g, int epi, hipStream_t s) {
+    t_flops += 2.0 * g.M * g.N * g.K;
+    kg_runs(pk, res, g.N, [&](int b0, int b1, int kg) {
+        const int row0 = pk.host(res)[b0], rows = pk.host(res)[b1] - row0;
+        mio::GemmArgs r = g;
+        r.A = g.A + (size_t)row0 * g.a_seg, r.a_rows = rows, r.M = rows;
+        const int up = epi == mio::EPI_CONVT ? g.f : 1;
+        r.C = g.C + (size_t)up * row0 * g.ldc, r.rows_out = up * rows;
+        mio::launch_gemm_f32_cfg(r, epi, kg, 11, s);
+    });
+}
+
+// run_decode on packed rows; stop_stage / stage_buf / rows / cols as there, *res = the table
+// of the stage's rows.
+int run_packed(mio_hip_codec *c, Ws &w, const Pk &pk, hipStream_t s, int stop_stage, const float **stage_buf,
+               int *rows, int *cols, int *res) {
+    const int B = pk.B, T = pk.total(PK_T), S = pk.total(PK_S), Dp = c->pre_dim, Dd = c->dec_dim;
+    int stage = 0;
+    auto done = [&](const float *buf, int r, int cc, int table) {
+        if (stage == stop_stage) {
+            *stage_buf = buf, *rows = r, *cols = cc, *res = table;
+            return true;
+        }
+        ++stage;
+        return false;
+    };
+    mio::launch_embed(c->tok, w.codes, T, Dp, w.xT, s);
+    if (done(w.xT, T, Dp, PK_T)) return MIO_OK;
+    for (int i = 0; i < c->pre_layers; ++i) {
+        const PreW &p = c->pre[i];
+        mio::launch_rownorm(w.xT, w.hT, T, Dp, c->eps, 1, p.ln1_w, p.ln1_b, s);
+        packed_gemm(pk, PK_T, gemm(w.hT, Dp, T, p.qkv, 3 * Dp, w.qkvT, 3 * Dp, p.h16_qkv), mio::EPI_STORE, s);
+        seg_band_launch(w.qkvT, w.aT, pk, PK_T, c->pre_heads, c->pre_win, c->rope, s);
+        packed_gemm(pk, PK_T, gemm(w.aT, Dp, T, p.wo, Dp, w.xT, Dp, p.h16_wo), mio::EPI_RESID, s);
+        mio::launch_rownorm(w.xT, w.hT, T, Dp, c->eps, 1, p.ln2_w, p.ln2_b, s);
+        packed_gemm(pk, PK_T, gemm(w.hT, Dp, T, p.gu, 2 * c->pre_ff, w.fT, c->pre_ff, p.h16_gu), mio::EPI_SWIGLU, s);
+        packed_gemm(pk, PK_T, gemm(w.fT, c->pre_ff, T, p.wd, Dp, w.xT, Dp, p.h16_wd), mio::EPI_RESID, s);
+    }
+    mio::launch_rownorm(w.xT, w.hT, T, Dp, c->eps, 1, c->pre_norm_w, c->pre_norm_b, s);
+    {
+        mio::GemmArgs g = gemm(w.hT, Dp, T, c->pre_out_w, Dd, w.yT, Dd, c->h16_pre_out);
+        g.bias = c->pre_out_b;
+        packed_gemm(pk, PK_T, g, mio::EPI_STORE, s);
+    }
+    if (done(w.yT, T, Dd, PK_T)) return MIO_OK;
+    {   // kernel = stride = 2, no trim: row 2m + r of the packed output, whatever the segment
+        mio::GemmArgs g = gemm(w.yT, Dd, T, c->ups_w, 2 * Dd, w.xS, Dd, c->h16_ups);
+        g.bias = c->ups_b, g.f = 2, g.trim = 0, g.cout = Dd, g.rows_out = S;
+        packed_gemm(pk, PK_T, g, mio::EPI_CONVT, s);
+    }
+    if (done(w.xS, S, Dd, PK_S)) return MIO_OK;
+    for (auto &r : c->prior) seg_resnet(c, r, w.xS, w.hS, pk, PK_S, Dd, w, s);
+    if (done(w.xS, S, Dd, PK_S)) return MIO_OK;
+    // AdaLN-Zero decoder: cond[b] = every conditioning vector of voice b
+    const int R = c->cond_rows;
+    t_flops += 2.0 * R * c->adaln * B;
+    mio::launch_cond_gemv_batch(c->cond_w, c->cond_b, pk.emb, R, c->adaln, B, pk.cond, c->h16_cond, s);
+    auto gated = [&](const float *A, int K, const float *Wt, const float *gate, int h16) {
+        mio::SegGemmArgs g{};
+        g.A = A, g.a_seg = K, g.taps = 1, g.B = Wt, g.M = S, g.N = Dd, g.K = K, g.C = w.xS, g.ldc = Dd;
+        g.aux_ld = R, g.a_f16 = h16;
+        t_flops += 2.0 * g.M * g.N * g.K;
+        kg_runs(pk, PK_S, g.N, [&](int b0, int b1, int kg) {
+            g.m_off = g.a_off = g.c_off = pk.dev(PK_S) + b0;
+            g.nseg = b1 - b0, g.m_begin = pk.host(PK_S)[b0], g.M = pk.host(PK_S)[b1], g.kg = kg;
+            g.aux = gate + (size_t)b0 * R;
+            mio::launch_seg_gemm(g, mio::EPI_GATED, s);
+        });
+    };
+    for (int i = 0; i < c->dec_layers; ++i) {
+        const DecW &p = c->dec[i];
+        const float *ca = pk.cond + (size_t)i * 6 * Dd, *cf = ca + 3 * Dd;
+        mio::launch_seg_rownorm(w.xS, w.hS, S, Dd, c->eps, ca, ca + Dd, R, pk.dev(PK_S), B, s);
+        packed_gemm(pk, PK_S, gemm(w.hS, Dd, S, p.qkv, 3 * Dd, w.qkvS, 3 * Dd, p.h16_qkv), mio::EPI_STORE, s);
+        seg_band_launch(w.qkvS, w.aS, pk, PK_S, c->dec_heads, c->dec_win, c->rope, s);
+        gated(w.aS, Dd, p.wo, ca + 2 * Dd, p.h16_wo);
+        mio::launch_seg_rownorm(w.xS, w.hS, S, Dd, c->eps, cf, cf + Dd, R, pk.dev(PK_S), B, s);
+        packed_gemm(pk, PK_S, gemm(w.hS, Dd, S, p.gu, 2 * c->dec_ff, w.fS, c->dec_ff, p.h16_gu), mio::EPI_SWIGLU, s);
+        gated(w.fS, c->dec_ff, p.wd, cf + 2 * Dd, p.h16_wd);
+    }
+    {
+        const float *nc = pk.cond + (size_t)c->dec_layers * 6 * Dd;
+        mio::launch_seg_rownorm(w.xS, w.xS, S, Dd, c->eps, nc, nc + Dd, R, pk.dev(PK_S), B, s);
+    }
+    if (done(w.xS, S, Dd, PK_S)) return MIO_OK;
+    for (auto &r : c->post) seg_resnet(c, r, w.xS, w.hS, pk, PK_S, Dd, w, s);
+    if (done(w.xS, S, Dd, PK_S)) return MIO_OK;
+    // upsampler stages: the tap window and the trimmed ConvT output are per segment
+    const float *src = w.xS;
+    int rin = PK_S;
+    for (int st = 0; st < c->up_stages; ++st) {
+        const UpW &u = c->ups[st];
+        mio::SegGemmArgs g{};
+        g.A = src, g.a_seg = u.Cin, g.taps = u.taps, g.B = u.w, g.M = pk.total(PK_M + st), g.N = u.f * u.Cout;
+        g.K = u.taps * u.Cin, g.C = w.u[st], g.ldc = u.Cout, g.bias = u.b, g.aux = u.alpha_e, g.aux2 = u.beta_e;
+        g.f = u.f, g.trim = u.trim, g.cout = u.Cout, g.a_f16 = u.h16;
+        t_flops += 2.0 * g.M * g.N * g.K;
+        kg_runs(pk, PK_M + st, g.N, [&](int b0, int b1, int kg) {
+            g.m_off = pk.dev(PK_M + st) + b0, g.a_off = pk.dev(rin) + b0, g.c_off = pk.dev(PK_U + st) + b0;
+            g.nseg = b1 - b0, g.m_begin = pk.host(PK_M + st)[b0], g.M = pk.host(PK_M + st)[b1], g.kg = kg;
+            mio::launch_seg_gemm(g, mio::EPI_CONVT_SNAKE, s);
+        });
+        seg_resnet(c, u.res, w.u[st], w.t[st], pk, PK_U + st, u.Cout, w, s);
+        src = w.u[st];
+        rin = PK_U + st;
+        if (done(w.u[st], pk.total(rin), u.Cout, rin)) return MIO_OK;
+    }
+    const int L = pk.total(rin);
+    {
+        mio::GemmArgs g = gemm(src, c->c_last, L, c->op_w, Dd, w.op, Dd, c->h16_op);
+        g.bias = c->op_b, g.aux = c->op_ae, g.aux2 = c->op_be;
+        packed_gemm(pk, rin, g, mio::EPI_SNAKE, s);
+    }
+    if (done(w.op, L, Dd, rin)) return MIO_OK;
+    {
+        mio::GemmArgs g = gemm(w.op, Dd, L, c->head_w, 2 * c->nfp, w.spec, 2 * c->n_freq, c->h16_head);
+        g.bias = c->head_b, g.cout = c->n_freq;
+        packed_gemm(pk, rin, g, mio::EPI_HEAD, s);
+    }
+    if (done(w.spec, L, 2 * c->n_freq, rin)) return MIO_OK;
+    return MIO_OK;
+}
+
+}  // namespace
+
+// The packed counterpart of mio_hip_codec_decode_stage (csrc/host/codec_debug.h; C-ABI wrapper
+// in the test library): seg_off receives the B + 1 row offsets of that stage.
+int mio::codec_decode_stage_packed(mio_hip_codec *c, const int32_t *const *codes, const int *n_codes, int B,
+                                   const float *const *embs, int stage, float *out, size_t out_cap, int *rows,
+                                   int *cols, int *seg_off) {
+    int rc = packed_check(c, codes, n_codes, B, embs, 0);
+    if (rc) return rc;
+    MIO_REQUIRE(out && seg_off, MIO_ERR_INVALID, "codec_decode_stage_packed: null output");
+    if ((rc = mio::bind(c->d))) return rc;
+    hipStream_t s = c->d->stream;
+    Ws w;
+    Pk pk;
+    if ((rc = plan_packed(c, n_codes, B, false, w, pk))) return rc;
+    if ((rc = packed_inputs(c, w, pk, codes, n_codes, embs, 0, s))) return rc;
+    const float *buf = nullptr;
+    int r = 0, cc = 0, res = 0;
+    if ((rc = run_packed(c, w, pk, s, stage, &buf, &r, &cc, &res))) return rc;
+    MIO_HIP_CHECK(hipGetLastError());
+    if (!buf || (size_t)r * cc > out_cap) {  // nothing is written to `out`; the launches end first
+        MIO_HIP_CHECK(hipStreamSynchronize(s));
+        MIO_REQUIRE(buf, MIO_ERR_INVALID, "codec_decode_stage_packed: stage %d out of range", stage);
+        MIO_REQUIRE(false, MIO_ERR_INVALID, "codec_decode_stage_packed: stage %d holds %d x %d floats, out has room for %zu",
+                    stage, r, cc, out_cap);
+    }
+    MIO_HIP_CHECK(hipMemcpyAsync(out, buf, (size_t)r * cc * 4, hipMemcpyDeviceToHost, s));
+    MIO_HIP_CHECK(hipStreamSynchronize(s));
+    std::memcpy(seg_off, pk.host(res), (size_t)(B + 1) * 4);
+    if (rows) *rows = r;
+    if (cols) *cols = cc;
+    return MIO_OK;
+}
+
+extern "C" int mio_hip_codec_decode_pcm_packed(mio_hip_codec *c, const int32_t *const *codes, const int *n_codes,
+                                               int B, const float *const *global_emb, float *const *out_pcm,
+                                               int *out_len, unsigned flags, void *stream) {
+    int rc = packed_check(c, codes, n_codes, B, global_emb, flags);
+    if (rc) return rc;
+    MIO_REQUIRE(out_pcm, MIO_ERR_INVALID, "codec_decode_pcm_packed: null argument");
+    for (int b = 0; b < B; ++b)
+        MIO_REQUIRE(out_pcm[b], MIO_ERR_INVALID, "codec_decode_pcm_packed: utterance %d: null output", b);
+    if ((rc = mio::bind(c->d))) return rc;
+    hipStream_t s = mio::pick_stream(c->d, stream);
+    // everything the call allocates or creates, before its first launch
+    Ws w;
+    Pk pk;
+    if ((rc = plan_packed(c, n_codes, B, !(flags & MIO_OUT_DEVICE), w, pk))) return rc;
+    if (!c->ev[0])
+        for (auto &e : c->ev) MIO_HIP_CHECK(hipEventCreate(&e));
+    const int NS = std::min(B, 3);  // the per-segment iSTFTs run on the caller's stream and two more
+    while ((int)c->xs.size() < NS - 1) {
+        hipStream_t q = nullptr;
+        hipEvent_t e = nullptr;
+        MIO_HIP_CHECK(hipStreamCreateWithFlags(&q, hipStreamNonBlocking));
+        MIO_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        c->xs.push_back(q), c->xev.push_back(e), c->xws.push_back(nullptr), c->xws_cap.push_back(0);
+    }
+    if ((rc = packed_inputs(c, w, pk, codes, n_codes, global_emb, flags, s))) return rc;
+    MIO_HIP_CHECK(hipEventRecord(c->ev[0], s));
+    const float *buf = nullptr;
+    int r = 0, cc = 0, res = 0;
+    t_flops = 0.0;
+    if ((rc = run_packed(c, w, pk, s, 1 << 20, &buf, &r, &cc, &res))) return rc;
+    c->last_flops = t_flops;
+    MIO_HIP_CHECK(hipEventRecord(c->ev[1], s));
+    // overlap-add must not cross utterances: the fused iSTFT once per segment on its slice of
+    // the packed spectrogram, spread over the lanes, joined on s
+    for (int k = 1; k < NS; ++k) MIO_HIP_CHECK(hipStreamWaitEvent(c->xs[k - 1], c->ev[1], 0));
+    const int *F = pk.host(frames_table(c));
+    auto issue = [&]() -> int {
+        for (int b = 0; b < B; ++b) {
+            hipStream_t ls = b % NS ? c->xs[b % NS - 1] : s;
+            const int frames = F[b + 1] - F[b];
+            const float *spec = w.spec + (size_t)F[b] * 2 * c->n_freq;
+            float *dst = (flags & MIO_OUT_DEVICE) ? out_pcm[b] : c->pk_pcm + pk.pcm_off[b];
+            int len = 0, rc = MIO_OK;
+            if ((rc = mio_hip_istft_out_len(c->ist, frames, c->hop, &len))) return rc;
+            if ((rc = mio_istft_launch_device(c->ist, spec, frames, c->hop, dst, ls))) return rc;
+            if (!(flags & MIO_OUT_DEVICE))
+                MIO_HIP_CHECK(hipMemcpyAsync(out_pcm[b], dst, (size_t)len * 4, hipMemcpyDeviceToHost, ls));
+            if (out_len) out_len[b] = len;
+        }
+        return MIO_OK;
+    };
+    rc = issue();
+    int jrc = MIO_OK;
+    for (int k = 1; k < NS; ++k) {
+        if (hipEventRecord(c->xev[k - 1], c->xs[k - 1]) != hipSuccess ||
+            hipStreamWaitEvent(s, c->xev[k - 1], 0) != hipSuccess) {
+            hipStreamSynchronize(c->xs[k - 1]);  // no join through s: wait for the lane here
+            jrc = MIO_ERR_HIP;
+        }
+    }
+    if (rc) {  // the first error's text stands; host buffers are quiet when the caller sees it
+        if (!(flags & MIO_OUT_DEVICE)) hipStreamSynchronize(s);
+        return rc;
+    }
+    MIO_REQUIRE(jrc == MIO_OK, MIO_ERR_HIP, "codec_decode_pcm_packed: joining the lane streams failed");
+    MIO_HIP_CHECK(hipGetLastError());
+    // last_timings: [0] the packed decode, [1] the per-segment iSTFTs
+    MIO_HIP_CHECK(hipEventRecord(c->ev[2], s));
+    c->timed = true;
     if (!(flags & MIO_OUT_DEVICE)) MIO_HIP_CHECK(hipStreamSynchronize(s));
     return MIO_OK;
 }

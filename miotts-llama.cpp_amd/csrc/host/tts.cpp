@@ -513,15 +513,39 @@ bool TestToSpeech::synthesize_to_file(const VoiceModel &voice, const std::string
 // group of 16, through the one-at-a-time fallback.
 bool TestToSpeech::synthesize_batch_to_files(const VoiceModel &voice, const std::vector<std::string> &texts,
                                              const std::vector<std::string> &output_paths, const Options &options) {
-    if (!is_ready() || !voice.is_ready() || texts.size() != output_paths.size()) {
+    return batch_to_files(&voice, false, texts, output_paths, options);
+}
+
+// One voice per utterance: as above, but the codec decodes each group of up to 16 as ONE packed
+// decode (mio_hip_codec_decode_pcm_packed: utterances of different lengths and voices share a
+// launch set). A packed utterance's PCM is its single decode's bit for bit, so each file has the
+// bytes of the single run with that voice.
+bool TestToSpeech::synthesize_batch_to_files(const std::vector<VoiceModel> &voices,
+                                             const std::vector<std::string> &texts,
+                                             const std::vector<std::string> &output_paths, const Options &options) {
+    if (voices.size() != texts.size() || voices.empty()) {
+        fprintf(stderr, "TestToSpeech: %zu voices for %zu texts\n", voices.size(), texts.size());
+        return false;
+    }
+    return batch_to_files(voices.data(), true, texts, output_paths, options);
+}
+
+// voices: one VoiceModel (per_utterance false) or one per text
+bool TestToSpeech::batch_to_files(const VoiceModel *voices, bool per_utterance, const std::vector<std::string> &texts,
+                                  const std::vector<std::string> &output_paths, const Options &options) {
+    auto V = [&](size_t u) -> const VoiceModel & { return voices[per_utterance ? u : 0]; };
+    bool voices_ready = true;
+    for (size_t u = 0; u < (per_utterance ? texts.size() : 1); ++u) voices_ready = voices_ready && V(u).is_ready();
+    const VoiceModel &voice = voices[0];
+    if (!is_ready() || !voices_ready || texts.size() != output_paths.size()) {
         fprintf(stderr, "TestToSpeech: %s\n",
-                !is_ready() ? "not ready" : (!voice.is_ready() ? "voice model is not ready" : "texts / paths mismatch"));
+                !is_ready() ? "not ready" : (!voices_ready ? "voice model is not ready" : "texts / paths mismatch"));
         return false;
     }
     Impl &I = *impl_;
     if (options.skip_llm || !I.llm) {
         for (size_t i = 0; i < texts.size(); ++i)
-            if (!synthesize_to_file(voice, texts[i], output_paths[i], options)) return false;
+            if (!synthesize_to_file(V(i), texts[i], output_paths[i], options)) return false;
         return true;
     }
     if (texts.empty()) return true;
@@ -552,7 +576,7 @@ bool TestToSpeech::synthesize_batch_to_files(const VoiceModel &voice, const std:
         fprintf(stderr, "TestToSpeech: batched decode unavailable (%s); decoding one utterance at a time\n",
                 mio_hip_last_error());
         for (size_t u = 0; u < N; ++u)
-            if (!synthesize_to_file(voice, texts[u], output_paths[u], options)) return false;
+            if (!synthesize_to_file(V(u), texts[u], output_paths[u], options)) return false;
         return true;
     }
     for (size_t g0 = 0; g0 < N; g0 += kGroup) {
@@ -581,8 +605,13 @@ bool TestToSpeech::synthesize_batch_to_files(const VoiceModel &voice, const std:
             if (!I.ensure(I.d_pcmb[b], I.pcmb_cap[b], codes[b].size() * I.spt * sizeof(float) + 64)) return false;
             cp[b] = codes[b].data(), op[b] = (float *)I.d_pcmb[b], nc[b] = (int)codes[b].size();
         }
-        if (mio_hip_codec_decode_pcm_batch(I.codec->codec, cp.data(), nc.data(), B, voice.embedding().data(), op.data(),
-                                           len.data(), MIO_OUT_DEVICE, nullptr) != MIO_OK) {
+        std::vector<const float *> ep((size_t)B);
+        for (int b = 0; b < B; ++b) ep[b] = V(g0 + b).embedding().data();
+        if ((per_utterance
+                 ? mio_hip_codec_decode_pcm_packed(I.codec->codec, cp.data(), nc.data(), B, ep.data(), op.data(),
+                                                   len.data(), MIO_OUT_DEVICE, nullptr)
+                 : mio_hip_codec_decode_pcm_batch(I.codec->codec, cp.data(), nc.data(), B, voice.embedding().data(),
+                                                  op.data(), len.data(), MIO_OUT_DEVICE, nullptr)) != MIO_OK) {
             fprintf(stderr, "TestToSpeech: codec decode failed: %s\n", mio_hip_last_error());
             return false;
         }

@@ -4,6 +4,7 @@
 #include <cstring>
 #include <vector>
 
+#include "codec_debug.h"
 #include "codec_kernels.h"
 #include "common.h"
 #include "mio_hip_test.h"
@@ -286,4 +287,11 @@ extern "C" int mio_hip_debug_codec_embed(mio_hip_device *d, const float *table, 
     MIO_REQUIRE(pool.ok, MIO_ERR_HIP, "debug_codec_embed: device allocation or upload failed");
     mio::launch_embed(dt, dc, T, D, out.body<float>(), d->stream);
     return conclude(d, out, x, guards_ok);
+}
+
+extern "C" int mio_hip_debug_codec_decode_stage_packed(mio_hip_codec *c, const int32_t *const *codes,
+                                                       const int *n_codes, int B, const float *const *global_emb,
+                                                       int stage, float *out, size_t out_cap, int *rows, int *cols,
+                                                       int *seg_off) {
+    return mio::codec_decode_stage_packed(c, codes, n_codes, B, global_emb, stage, out, out_cap, rows, cols, seg_off);
 }

@@ -122,6 +122,7 @@ def _declare(L: ctypes.CDLL) -> None:
         "mio_hip_codec_decode_pcm": (c_int, [_vp, _vp, c_int, _vp, _vp, ctypes.POINTER(c_int),
                                              ctypes.c_uint, _vp]),
         "mio_hip_codec_decode_pcm_batch": (c_int, [_vp, _vp, _vp, c_int, _vp, _vp, _vp, ctypes.c_uint, _vp]),
+        "mio_hip_codec_decode_pcm_packed": (c_int, [_vp, _vp, _vp, c_int, _vp, _vp, _vp, ctypes.c_uint, _vp]),
         "mio_hip_codec_decode_stage": (c_int, [_vp, _vp, c_int, _vp, c_int, _vp,
                                                ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
         "mio_synth_codec_gguf": (c_int, [ctypes.c_char_p, c_int, ctypes.c_uint64]),
@@ -194,6 +195,8 @@ def _declare(L: ctypes.CDLL) -> None:
                                                        ctypes.POINTER(c_int)]),
         "mio_hip_debug_codec_cond_gemv": (c_int, [_vp, _vp, _vp, _vp, c_int, c_int, c_int, _vp,
                                                   ctypes.POINTER(c_int)]),
+        "mio_hip_debug_codec_decode_stage_packed": (c_int, [_vp, _vp, _vp, c_int, _vp, c_int, _vp, ctypes.c_size_t,
+                                                            ctypes.POINTER(c_int), ctypes.POINTER(c_int), _vp]),
         "mio_hip_debug_codec_embed": (c_int, [_vp, _vp, c_int, c_int, _vp, c_int, _vp, ctypes.POINTER(c_int)]),
         "mio_hip_llm_info": (c_int, [_vp, _i32p]),
         "mio_hip_llm_weight_bytes": (c_int, [_vp, ctypes.POINTER(ctypes.c_uint64)]),
@@ -503,6 +506,57 @@ class Codec:
         lens = self.decode_pcm_batch_device(d_codes, [len(c) for c in codes], d_emb, outs)
         dev.sync()
         return [o.numpy()[:n] for o, n in zip(outs, lens)]
+
+    @staticmethod
+    def _packed_args(codes_list, embs):
+        hc = [np.ascontiguousarray(c, np.int32) for c in codes_list]
+        he = [None if e is None else np.ascontiguousarray(e, np.float32) for e in embs]
+        B = len(hc)
+        # a None embedding is passed as a null pointer (the entry refuses it)
+        cp = (ctypes.c_void_p * max(B, 1))(*[_ptr(c) for c in hc])
+        ep = (ctypes.c_void_p * max(B, 1))(*[None if e is None else _ptr(e) for e in he])
+        nc = (ctypes.c_int * max(B, 1))(*[len(c) for c in hc])
+        return hc, he, B, cp, ep, nc
+
+    def decode_pcm_packed(self, codes_list, embs):
+        """B utterances of different lengths, one voice embedding each, as one packed decode
+        (mio_hip_codec_decode_pcm_packed, host pointers): list of code arrays -> list of PCM."""
+        hc, he, B, cp, ep, nc = self._packed_args(codes_list, embs)
+        ho = [np.empty(len(c) * self.samples_per_token + self.n_fft, np.float32) for c in hc]
+        op = (ctypes.c_void_p * max(B, 1))(*[_ptr(o) for o in ho])
+        ln = (ctypes.c_int * max(B, 1))()
+        check(lib().mio_hip_codec_decode_pcm_packed(self.h, ctypes.cast(cp, _vp), ctypes.cast(nc, _vp), B,
+                                                    ctypes.cast(ep, _vp), ctypes.cast(op, _vp), ctypes.cast(ln, _vp),
+                                                    0, None))
+        return [o[:int(n)] for o, n in zip(ho, ln)]
+
+    def decode_pcm_packed_device(self, codes, n_codes, embs, outs, stream: int = 0):
+        """decode_pcm_packed on DeviceArrays (codes[b], embs[b], outs[b]; nothing is copied to the
+        host and the call does not wait); returns the PCM lengths."""
+        B = len(codes)
+        cp = (ctypes.c_void_p * B)(*[c.ptr for c in codes])
+        ep = (ctypes.c_void_p * B)(*[e.ptr for e in embs])
+        op = (ctypes.c_void_p * B)(*[o.ptr for o in outs])
+        nc = (ctypes.c_int * B)(*[int(n) for n in n_codes])
+        ln = (ctypes.c_int * B)()
+        check(lib().mio_hip_codec_decode_pcm_packed(self.h, ctypes.cast(cp, _vp), ctypes.cast(nc, _vp), B,
+                                                    ctypes.cast(ep, _vp), ctypes.cast(op, _vp), ctypes.cast(ln, _vp),
+                                                    MIO_IN_DEVICE | MIO_OUT_DEVICE, stream or None))
+        return [int(x) for x in ln]
+
+    def decode_stage_packed(self, codes_list, embs, stage: int, max_elems: int):
+        """The packed decode up to `stage` (mio_hip_debug_codec_decode_stage_packed): the rows
+        of that stage per utterance, as a list of [rows_b][cols] arrays. A stage of more than
+        max_elems floats is refused."""
+        hc, he, B, cp, ep, nc = self._packed_args(codes_list, embs)
+        out = np.empty(max_elems, np.float32)
+        r, c = ctypes.c_int(0), ctypes.c_int(0)
+        off = (ctypes.c_int * (B + 1))()
+        check(lib().mio_hip_debug_codec_decode_stage_packed(self.h, ctypes.cast(cp, _vp), ctypes.cast(nc, _vp), B,
+                                                            ctypes.cast(ep, _vp), stage, _ptr(out), max_elems,
+                                                            ctypes.byref(r), ctypes.byref(c), ctypes.cast(off, _vp)))
+        x = out[: r.value * c.value].reshape(r.value, c.value)
+        return [x[off[b]:off[b + 1]] for b in range(B)]
 
     def last_timings(self):
         ms = np.zeros(2, np.float32)
