@@ -81,6 +81,54 @@ int mio_hip_pcm_finish(mio_hip_device *d, const float *samples, int64_t n, int n
 int mio_hip_pcm_normalize(mio_hip_device *d, const float *samples, int64_t n, float *out,
                           float *peak, void *stream);
 
+/* ---------------- output rate: rational resampler ----------------
+ * PCM at f_out = f_in * L / M (L = f_out / gcd, M = f_in / gcd, F = max(L, M)) through a
+ * Kaiser-windowed sinc designed in float64 at create: cutoff 0.9 pi / F at L times the input rate
+ * (stopband from pi / F, the lower Nyquist frequency; passband to 0.8 pi / F), A = 80 dB,
+ * beta = 0.1102 (A - 8.7), length P * L with P the smallest even count of taps per phase that
+ * gives P * L >= (A - 7.95) / (2.285 * 0.2 pi / F) + 1,
+ *   h[n] = L * 0.9 / F * sinc(0.9 / F * (n - (P L - 1) / 2)) * kaiser(P L, beta), rounded to f32,
+ * held as the phase table c[L][P], c[phi][j] = h[j * L + phi]. Output n of a stream is
+ *   y[n] = sum_{t < P} x[floor(n M / L) - P/2 + 1 + t] * c[n M mod L][P - 1 - t]
+ * with x = 0 outside the stream, one f32 fused multiply-add per tap in the order t = 0 .. P - 1
+ * whatever the launch geometry and however the stream is cut into calls; N samples in give
+ * ceil(N * L / M) out. f_out is one of 8000, 16000, 22050, 24000, 32000, 48000 and differs from
+ * f_in, and the table is at most 128 KB (it is kept whole in one compute unit's LDS): anything
+ * else is MIO_ERR_UNSUPPORTED with the rate in the message. d == NULL makes a handle of the design
+ * alone (_info and _coeffs work, nothing runs). All device memory (table, the kept P - 1 samples,
+ * peak partials) is allocated at create; a run allocates nothing. */
+typedef struct mio_hip_resampler mio_hip_resampler;
+int mio_hip_resampler_create(mio_hip_device *d, int f_in, int f_out, mio_hip_resampler **out);
+void mio_hip_resampler_destroy(mio_hip_resampler *h);
+/* info[5] = {L, M, P, delay, tile}: delay = P / 2, the input samples after floor(n M / L) that
+ * output n waits for in a stream (the filter itself is linear-phase about its output's own
+ * instant); tile = the outputs one workgroup forms per round. */
+int mio_hip_resampler_info(const mio_hip_resampler *h, int *info);
+/* c[L][P] as designed (host floats; cap = the floats `out` holds, >= L * P). */
+int mio_hip_resampler_coeffs(const mio_hip_resampler *h, float *out, int cap);
+/* Forgets the stream so far (as a flush does, without emitting anything). */
+int mio_hip_resampler_reset(mio_hip_resampler *h);
+/* The next n samples of the stream (in, a device pointer; n >= 0), each multiplied by gain as it
+ * is loaded (gain 1 = untouched). Emits every output whose taps lie inside the samples seen so
+ * far, as floats to out_f32 or as mio_hip_pcm_finish's int16 to out_pcm16 (device pointers, exactly
+ * one non-null, room for out_cap samples: at most ceil((n + P/2) * L / M) + 1 are written, and a
+ * call that would write more than out_cap is refused before anything runs); *n_out = their
+ * count. flush != 0 emits the rest of the stream against zeros and forgets it. The handle keeps
+ * the count of samples seen and the last P - 1 of them on the device. Queued on `stream`; does
+ * not wait. A stream's calls go to one stream. */
+int mio_hip_resample(mio_hip_resampler *h, const float *in, int64_t n, float gain, float *out_f32,
+                     int16_t *out_pcm16, int64_t out_cap, int64_t *n_out, int flush, void *stream);
+/* mio_hip_pcm_finish at the handle's output rate, for a whole utterance: the peak pass on the n
+ * native-rate samples (16-byte aligned device pointer), then ONE launch that applies the
+ * normalising gain (normalize != 0) to each sample as it loads it, resamples and converts:
+ * ceil(n * L / M) samples (*n_out) to out_pcm16, or as floats to out_f32 (exactly one non-null,
+ * room for out_cap). Equal, bit for bit, to mio_hip_pcm_normalize, mio_hip_resample to floats with
+ * flush, then the int16 conversion. Independent of the handle's stream state. peak as in
+ * mio_hip_pcm_finish. */
+int mio_hip_pcm_finish_rate(mio_hip_resampler *h, const float *samples, int64_t n, int normalize,
+                            float *out_f32, int16_t *out_pcm16, int64_t out_cap, int64_t *n_out,
+                            float *peak, void *stream);
+
 /* ---------------- iSTFT ----------------
  * Replaces istft_cache(n_fft, win_length) (istft.h:6-30, istft.cpp:7-32) and
  * istft(spec, n_frames, hop, cache) (istft.h:38-42, istft.cpp:68-108).

@@ -48,7 +48,12 @@ public:
         size_t prenet_rows_reused = 0;
     };
 
-    struct Config {
+    // output_sample_rate took the four bytes that were padding at the end of Config, so the size
+    // and every earlier offset are unchanged; a program compiled against the earlier header never
+    // wrote those bytes. The tag puts the layout into the constructor's mangled name: such a
+    // program keeps binding to the untagged constructor, which the library still exports and
+    // which reads the rate as 0 (csrc/host/tts.cpp, "earlier entry points").
+    struct [[gnu::__abi_tag__("cfg2")]] Config {
         std::string model_path;
         std::string codec_path;
         int n_threads = 4;
@@ -56,6 +61,11 @@ public:
         float temperature = 0.8f;
         int max_tokens = 700;
         int device = -1;  // extension: GPU index (-1 = MIO_DEVICE / LOCAL_RANK / 0)
+        // extension: the rate of everything written or handed to a callback: 8000, 16000, 22050,
+        // 24000, 32000 or 48000 Hz, resampled on the device in the PCM epilogue (mio_hip.h
+        // "output rate"); 0 or the codec's own rate = as the codec produces it. Checked with the
+        // models: any other rate leaves is_ready() false. sample_rate() reports the rate in use.
+        int output_sample_rate = 0;
     };
 
     // The sampler chain's fields grew Options past the 12 bytes it had. The tag puts the layout

@@ -8,6 +8,7 @@
 // HBM-bound: 4 B read twice (peak pass, convert pass) + 2 B written per sample. Scratch (peak
 // partials) is allocated per call, stream-ordered, so concurrent calls never share it.
 #include "common.h"
+#include "pcm_resample.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -86,6 +87,15 @@ __global__ __launch_bounds__(PT) void k_finish(const float *s, long long n, cons
 }
 
 }  // namespace
+
+// the peak pass alone, for the epilogue at another rate (pcm_resample.hip reduces the partials)
+int mio::pcm_peak_launch(const float *samples, long long n, float *part, int *parts, hipStream_t s) {
+    static_assert(MAX_PARTS == mio::RS_MAX_PARTS, "one partials bound");
+    *parts = (int)std::min<long long>(MAX_PARTS, std::max<long long>(1, (n / 4 + PT * 4 - 1) / (PT * 4)));
+    hipLaunchKernelGGL(k_peak, dim3(*parts), dim3(PT), 0, s, samples, n, part);
+    MIO_HIP_CHECK(hipGetLastError());
+    return MIO_OK;
+}
 
 namespace {
 template <class OutT>

@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <map>
 #include <mutex>
+#include <new>
 #include <string>
 #include <vector>
 
@@ -227,6 +228,12 @@ struct TestToSpeech::Impl {
     mio::BpeTokenizer tok;
     int32_t eos = -1, im_end = -1;
     int sample_rate = 0, n_fft = 0, hop = 0, spt = 0;
+    // Config::output_sample_rate: the resampler of the PCM epilogue (null: the codec's own rate),
+    // the rate written, and the device buffers a streamed chunk passes through
+    mio_hip_resampler *rs = nullptr;
+    int out_rate = 0;
+    void *d_rs_in = nullptr, *d_rs_out = nullptr;
+    size_t rs_in_cap = 0, rs_out_cap = 0;
 
     // PCM of the last decode in HBM (f32) and its PCM16 image (synthesize_to_file)
     void *d_pcm = nullptr, *d_pcm16 = nullptr;
@@ -239,6 +246,9 @@ struct TestToSpeech::Impl {
 
     ~Impl() {
         if (cstream) hipStreamDestroy(cstream);
+        if (rs) mio_hip_resampler_destroy(rs);
+        if (dev && d_rs_in) mio_hip_free(dev, d_rs_in);
+        if (dev && d_rs_out) mio_hip_free(dev, d_rs_out);
         if (llm) mio_hip_llm_free(llm);
         if (dev && d_pcm) mio_hip_free(dev, d_pcm);
         if (dev && d_pcm16) mio_hip_free(dev, d_pcm16);
@@ -312,12 +322,62 @@ struct TestToSpeech::Impl {
         return true;
     }
 
+    // samples at the output rate for n at the codec's (ceil(n L / M), mio_hip.h "output rate")
+    size_t out_samples(size_t n) const {
+        int info[5] = {1, 1, 0, 0, 0};
+        if (rs) mio_hip_resampler_info(rs, info);
+        return (n * (size_t)info[0] + (size_t)info[1] - 1) / (size_t)info[1];
+    }
+
+    // the WAV payload of len device floats: peak normalisation (when asked) and PCM16 on the
+    // device, at the output rate (mio_hip_pcm_finish, or _finish_rate with a resampler)
+    bool finish_pcm16(const float *d_src, int len, bool normalize, std::vector<int16_t> &pcm16) {
+        int64_t n_out = len;
+        const size_t cap = out_samples((size_t)len);
+        if (!ensure(d_pcm16, pcm16_cap, cap * 2 + 64)) return false;
+        const int rc = rs ? mio_hip_pcm_finish_rate(rs, d_src, len, normalize ? 1 : 0, nullptr, (int16_t *)d_pcm16,
+                                                    (int64_t)cap, &n_out, nullptr, nullptr)
+                          : mio_hip_pcm_finish(dev, d_src, len, normalize ? 1 : 0, (int16_t *)d_pcm16, nullptr, nullptr);
+        pcm16.resize((size_t)n_out);
+        if (rc != MIO_OK || (n_out && mio_hip_memcpy_d2h(dev, pcm16.data(), d_pcm16, (size_t)n_out * 2) != MIO_OK)) {
+            fprintf(stderr, "TestToSpeech: PCM epilogue failed: %s\n", mio_hip_last_error());
+            return false;
+        }
+        return true;
+    }
+
+    // one streamed chunk (host floats at the codec's rate; last: the stream's final call, n may
+    // be 0) through the stateful resampler on the codec stream: `out` = the samples it completes
+    bool resample_chunk(const float *p, size_t n, bool last, std::vector<float> &out) {
+        int info[5];
+        mio_hip_resampler_info(rs, info);
+        const size_t cap = out_samples(n + (size_t)info[3]) + 1;
+        if (!ensure(d_rs_in, rs_in_cap, n * sizeof(float) + 64) || !ensure(d_rs_out, rs_out_cap, cap * sizeof(float)))
+            return false;
+        hipStream_t s = cstream ? cstream : dev->stream;
+        int64_t got = 0;
+        if ((n && hipMemcpyAsync(d_rs_in, p, n * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess) ||
+            mio_hip_resample(rs, (const float *)d_rs_in, (int64_t)n, 1.0f, (float *)d_rs_out, nullptr, (int64_t)cap, &got,
+                             last ? 1 : 0, s) != MIO_OK) {
+            fprintf(stderr, "TestToSpeech: resampling failed: %s\n", mio_hip_last_error());
+            return false;
+        }
+        out.resize((size_t)got);
+        if ((got && hipMemcpyAsync(out.data(), d_rs_out, (size_t)got * sizeof(float), hipMemcpyDeviceToHost, s) !=
+                        hipSuccess) ||
+            hipStreamSynchronize(s) != hipSuccess) {
+            fprintf(stderr, "TestToSpeech: resampled PCM copy failed\n");
+            return false;
+        }
+        return true;
+    }
+
     // codes -> host PCM; the peak normalisation of test-to-speech.cpp:232-243 (when asked)
     // runs on the device before the copy (mio_hip_pcm_normalize, bit-exact with the host loop)
     // stream (optional): decode and copy on that stream (the streaming path's codec stream)
     bool decode_codes(const VoiceModel &voice, const std::vector<int> &codes, std::vector<float> &pcm,
                       double *codec_sec, double *istft_sec, bool normalize = false, bool incremental = false,
-                      hipStream_t stream = nullptr) {
+                      hipStream_t stream = nullptr, bool native_rate = false) {
         int len = 0;
         if (!decode_codes_dev(voice, codes, &len, codec_sec, istft_sec, incremental, stream)) return false;
         if (stream) {
@@ -326,6 +386,19 @@ struct TestToSpeech::Impl {
                                        stream) != hipSuccess ||
                         hipStreamSynchronize(stream) != hipSuccess)) {
                 fprintf(stderr, "TestToSpeech: PCM copy failed\n");
+                return false;
+            }
+            return true;
+        }
+        if (rs && !native_rate) {  // at the output rate: the gain (peak of the native-rate signal) fused into the resampler
+            const size_t cap = out_samples((size_t)len);
+            int64_t got = 0;
+            if (!ensure(d_rs_out, rs_out_cap, cap * sizeof(float) + 64)) return false;
+            pcm.resize(cap);
+            if (mio_hip_pcm_finish_rate(rs, (const float *)d_pcm, len, normalize ? 1 : 0, (float *)d_rs_out, nullptr,
+                                        (int64_t)cap, &got, nullptr, nullptr) != MIO_OK ||
+                (got && mio_hip_memcpy_d2h(dev, pcm.data(), d_rs_out, (size_t)got * sizeof(float)) != MIO_OK)) {
+                fprintf(stderr, "TestToSpeech: PCM epilogue failed: %s\n", mio_hip_last_error());
                 return false;
             }
             return true;
@@ -383,6 +456,18 @@ TestToSpeech::TestToSpeech(const Config &config) : config_(config), impl_(std::m
     I.n_fft = miocodec_n_fft(I.codec);
     I.hop = miocodec_hop_length(I.codec);
     I.spt = miocodec_samples_per_token(I.codec);
+    // the output rate is checked here, with the models: a rate the resampler refuses leaves the
+    // instance not ready; the codec's own rate (or 0) takes the epilogue as it was
+    I.out_rate = config_.output_sample_rate > 0 ? config_.output_sample_rate : I.sample_rate;
+    if (config_.output_sample_rate < 0 ||
+        (I.out_rate != I.sample_rate &&
+         mio_hip_resampler_create(I.dev, I.sample_rate, I.out_rate, &I.rs) != MIO_OK)) {
+        fprintf(stderr, "TestToSpeech: output sample rate %d: %s\n", config_.output_sample_rate,
+                config_.output_sample_rate < 0 ? "not a rate" : mio_hip_last_error());
+        miocodec_free(I.codec);
+        I.codec = nullptr;
+        return;
+    }
     // device memory for utterances of up to max_tokens codes, allocated with the models (as
     // llama_init_from_model / miocodec_load reserve theirs): codec workspace and prenet cache,
     // the PCM and PCM16 buffers; a synthesis then allocates nothing on the device
@@ -406,7 +491,7 @@ TestToSpeech::TestToSpeech(const Config &config) : config_(config), impl_(std::m
 TestToSpeech::~TestToSpeech() = default;
 
 bool TestToSpeech::is_ready() const { return impl_ && impl_->codec != nullptr; }
-int TestToSpeech::sample_rate() const { return impl_ ? impl_->sample_rate : 0; }
+int TestToSpeech::sample_rate() const { return impl_ ? impl_->out_rate : 0; }
 
 bool TestToSpeech::generate_token_text(const std::string &text, const Options &options, std::string &out) {
     out.clear();
@@ -483,16 +568,10 @@ bool TestToSpeech::synthesize_to_file(const VoiceModel &voice, const std::string
     }
     Impl &I = *impl_;
     int len = 0;
+    std::vector<int16_t> pcm16;
     if (!I.decode_codes_dev(voice, codes, &len, nullptr, nullptr) ||
-        !I.ensure(I.d_pcm16, I.pcm16_cap, (size_t)len * 2 + 64))
+        !I.finish_pcm16((const float *)I.d_pcm, len, options.apply_peak_normalization, pcm16))
         return false;
-    std::vector<int16_t> pcm16(len);
-    if (mio_hip_pcm_finish(I.dev, (const float *)I.d_pcm, len, options.apply_peak_normalization ? 1 : 0,
-                           (int16_t *)I.d_pcm16, nullptr, nullptr) != MIO_OK ||
-        (len && mio_hip_memcpy_d2h(I.dev, pcm16.data(), I.d_pcm16, (size_t)len * 2) != MIO_OK)) {
-        fprintf(stderr, "TestToSpeech: PCM epilogue failed: %s\n", mio_hip_last_error());
-        return false;
-    }
     return mio::wav_write_pcm16(output_path, pcm16.data(), pcm16.size(), sample_rate());
 }
 
@@ -616,14 +695,8 @@ bool TestToSpeech::batch_to_files(const VoiceModel *voices, bool per_utterance, 
             return false;
         }
         for (int b = 0; b < B; ++b) {
-            std::vector<int16_t> pcm16((size_t)len[b]);
-            if (!I.ensure(I.d_pcm16, I.pcm16_cap, (size_t)len[b] * 2 + 64) ||
-                mio_hip_pcm_finish(I.dev, op[b], len[b], options.apply_peak_normalization ? 1 : 0,
-                                   (int16_t *)I.d_pcm16, nullptr, nullptr) != MIO_OK ||
-                (len[b] && mio_hip_memcpy_d2h(I.dev, pcm16.data(), I.d_pcm16, (size_t)len[b] * 2) != MIO_OK)) {
-                fprintf(stderr, "TestToSpeech: PCM epilogue failed: %s\n", mio_hip_last_error());
-                return false;
-            }
+            std::vector<int16_t> pcm16;
+            if (!I.finish_pcm16(op[b], len[b], options.apply_peak_normalization, pcm16)) return false;
             if (!mio::wav_write_pcm16(output_paths[g0 + b], pcm16.data(), pcm16.size(), sample_rate())) return false;
         }
     }
@@ -657,12 +730,29 @@ bool TestToSpeech::synthesize_stream_profiled(const VoiceModel &voice, const std
     Impl &I = *impl_;
     const int sr = I.sample_rate;
     const size_t xfade = std::min<size_t>((size_t)(sr * 3 / 100), 4096);
-    std::vector<float> tail;
+    std::vector<float> tail, resampled;
+    // an output rate other than the codec's: every chunk, cut and crossfaded at the codec's
+    // rate as ever, passes through the one stateful resampler before the callback sees it
+    if (I.rs) {
+        int info[5];
+        mio_hip_resampler_reset(I.rs);
+        mio_hip_resampler_info(I.rs, info);
+        if (!I.ensure(I.d_rs_in, I.rs_in_cap, chunk_samples * sizeof(float) + 64) ||
+            !I.ensure(I.d_rs_out, I.rs_out_cap, (I.out_samples(chunk_samples + (size_t)info[3]) + 1) * sizeof(float)))
+            return false;
+    }
 
+    // emitted_samples counts what the callback received, at the rate it received it
     auto call = [&](const float *p, size_t n, bool last) {
+        if (I.rs) {
+            if (!I.resample_chunk(p, n, last, resampled)) return false;
+            if (resampled.empty() && !last) return true;
+            p = resampled.empty() ? nullptr : resampled.data(), n = resampled.size();
+        }
         const auto a = clk::now();
-        const bool ok = callback(p, n, sr, last);
+        const bool ok = callback(p, n, I.out_rate, last);
         profile.callback_sec += secs(a, clk::now());
+        if (ok) profile.emitted_samples += n;
         return ok;
     };
     auto emit = [&](const std::vector<float> &audio, size_t begin, size_t end, bool final_) -> bool {
@@ -682,7 +772,6 @@ bool TestToSpeech::synthesize_stream_profiled(const VoiceModel &voice, const std
             else
                 tail = chunk;
             if (!call(chunk.data(), n, final_ && i + n >= end)) return false;
-            profile.emitted_samples += n;
             i += n;
         }
         return true;
@@ -691,7 +780,9 @@ bool TestToSpeech::synthesize_stream_profiled(const VoiceModel &voice, const std
     if (options.skip_llm) {
         const std::vector<int> codes = parse_speech_tokens(text);
         std::vector<float> audio;
-        if (codes.empty() || !I.decode_codes(voice, codes, audio, &profile.codec_sec, &profile.istft_sec)) {
+        // at the codec's rate: the chunks are resampled on their way out, like any stream's
+        if (codes.empty() || !I.decode_codes(voice, codes, audio, &profile.codec_sec, &profile.istft_sec, false, false,
+                                             nullptr, true)) {
             if (codes.empty()) fprintf(stderr, "TestToSpeech: no speech codes parsed from text\n");
             return false;
         }
@@ -881,6 +972,26 @@ MIO_V1 mio_v1_synthesize_stream_profiled(TestToSpeech *t, const VoiceModel &v, c
                                          TestToSpeech::StreamProfile &p) {
     return t->synthesize_stream_profiled(v, text, cb, chunk, widen(o), p);
 }
+
+// Before Config::output_sample_rate, Config ended in four bytes of padding that no caller wrote
+// and the constructor had this untagged name (complete- and base-object variants). A program
+// compiled against that header still constructs through it: everything but the rate is read
+// as given, the rate is the codec's own.
+static_assert(sizeof(TestToSpeech::Config) == 2 * sizeof(std::string) + 6 * sizeof(int),
+              "output_sample_rate fills the earlier Config's tail padding: no other field, no growth");
+static void construct_v1(TestToSpeech *t, const TestToSpeech::Config &c) {
+    TestToSpeech::Config n = c;
+    n.output_sample_rate = 0;
+    new (t) TestToSpeech(n);
+}
+extern "C" __attribute__((visibility("default"))) void mio_v1_construct_c1(TestToSpeech *t,
+                                                                           const TestToSpeech::Config &c)
+    asm("_ZN12TestToSpeechC1ERKNS_6ConfigE");
+void mio_v1_construct_c1(TestToSpeech *t, const TestToSpeech::Config &c) { construct_v1(t, c); }
+extern "C" __attribute__((visibility("default"))) void mio_v1_construct_c2(TestToSpeech *t,
+                                                                           const TestToSpeech::Config &c)
+    asm("_ZN12TestToSpeechC2ERKNS_6ConfigE");
+void mio_v1_construct_c2(TestToSpeech *t, const TestToSpeech::Config &c) { construct_v1(t, c); }
 
 #undef MIO_V1
 #undef MIO_STR

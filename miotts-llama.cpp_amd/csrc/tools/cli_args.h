@@ -21,6 +21,7 @@ struct CliArgs {
     int gpus = 1;            // miotts --gpus: MI355Xs the batch is sharded over
     float temperature = 0.8f;
     int max_tokens = 700, n_threads = 4, n_gpu_layers = 0, device = -1;
+    int sample_rate = 0;  // --sample-rate: TestToSpeech::Config::output_sample_rate (0 = the codec's)
     size_t chunk_samples = 4096;
     bool skip_llm = false, dump_tensors = false, speech_only = false, ignore_eos = false;
     // the on-device sampler chain (TestToSpeech::Options; neutral by default)
@@ -69,6 +70,9 @@ inline std::vector<CliFlag> cli_common_flags() {
          [](CliArgs &a, const std::string &v) { a.n_gpu_layers = std::stoi(v); }},
         {{"--device"}, true, "MI355X index (default: MIO_DEVICE, else LOCAL_RANK, else 0)",
          [](CliArgs &a, const std::string &v) { a.device = std::stoi(v); }},
+        {{"--sample-rate"}, true,
+         "Output rate in Hz: 8000, 16000, 22050, 24000, 32000 or 48000 (default: the codec's own, 44100)",
+         [](CliArgs &a, const std::string &v) { a.sample_rate = cli_int(v); }},
         {{"--skip-llm"}, false, "Treat --prompt as raw <|s_N|> token text",
          [](CliArgs &a, const std::string &) { a.skip_llm = true; }},
         {{"--speech-only"}, false, "Benchmark harness: sample only the <|s_N|> speech ids",
@@ -143,6 +147,7 @@ inline std::string cli_check(const CliArgs &a, bool path_words = false) {
     for (float v : {a.top_p, a.min_p, a.repeat_penalty, a.frequency_penalty, a.presence_penalty})
         if (v != v) return "a sampling option is NaN";
     if (!(a.repeat_penalty > 0.0f)) return "--repeat-penalty must be > 0";
+    if (a.sample_rate < 0) return "--sample-rate must be a rate in Hz";
     if (a.repeat_last_n < 0 || a.repeat_last_n > 256) return "--repeat-last-n must be in 0..256";
     return "";
 }
@@ -156,6 +161,7 @@ inline TestToSpeech::Config cli_config(const CliArgs &a) {
     c.temperature = a.temperature;
     c.max_tokens = a.max_tokens;
     c.device = a.device;
+    c.output_sample_rate = a.sample_rate;
     return c;
 }
 

@@ -109,6 +109,15 @@ def _declare(L: ctypes.CDLL) -> None:
         "mio_hip_timer_elapsed": (c_int, [_vp, c_int, c_int, _f32p]),
         "mio_hip_pcm_finish": (c_int, [_vp, _vp, ctypes.c_int64, c_int, _vp, _f32p, _vp]),
         "mio_hip_pcm_normalize": (c_int, [_vp, _vp, ctypes.c_int64, _vp, _f32p, _vp]),
+        "mio_hip_resampler_create": (c_int, [_vp, c_int, c_int, ctypes.POINTER(_vp)]),
+        "mio_hip_resampler_destroy": (None, [_vp]),
+        "mio_hip_resampler_info": (c_int, [_vp, _i32p]),
+        "mio_hip_resampler_coeffs": (c_int, [_vp, _vp, c_int]),
+        "mio_hip_resampler_reset": (c_int, [_vp]),
+        "mio_hip_resample": (c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_float, _vp, _vp, ctypes.c_int64,
+                                     ctypes.POINTER(ctypes.c_int64), c_int, _vp]),
+        "mio_hip_pcm_finish_rate": (c_int, [_vp, _vp, ctypes.c_int64, c_int, _vp, _vp, ctypes.c_int64,
+                                            ctypes.POINTER(ctypes.c_int64), _f32p, _vp]),
         "mio_hip_istft_create": (c_int, [_vp, c_int, c_int, ctypes.POINTER(_vp)]),
         "mio_hip_istft_destroy": (None, [_vp]),
         "mio_hip_istft_out_len": (c_int, [_vp, c_int, c_int, ctypes.POINTER(c_int)]),
@@ -342,6 +351,67 @@ def pcm_finish(dev: "Device", samples: "DeviceArray", n: int, normalize: bool,
     check(lib().mio_hip_pcm_finish(dev.h, samples.ptr if n else None, n, 1 if normalize else 0,
                                    out.ptr if n else None, ctypes.byref(peak), None))
     return out.numpy()[:n], peak.value
+
+
+class Resampler:
+    """Output-rate resampler (mio_hip_resampler, include/mio_hip.h "output rate"). dev None: the
+    filter design alone (L, M, P, coeffs()); nothing runs."""
+
+    def __init__(self, dev: Optional["Device"], f_in: int, f_out: int):
+        self.dev = dev
+        h = _vp()
+        check(lib().mio_hip_resampler_create(dev.h if dev is not None else None, f_in, f_out, ctypes.byref(h)))
+        self.h = h
+        info = np.zeros(5, np.int32)
+        check(lib().mio_hip_resampler_info(h, info.ctypes.data_as(_i32p)))
+        self.L, self.M, self.P, self.delay, self.tile = [int(x) for x in info]
+
+    def close(self):
+        if self.h:
+            lib().mio_hip_resampler_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def coeffs(self) -> np.ndarray:
+        """The phase table c[L][P] (float32)."""
+        c = np.empty((self.L, self.P), np.float32)
+        check(lib().mio_hip_resampler_coeffs(self.h, _ptr(c), c.size))
+        return c
+
+    def out_len(self, n: int) -> int:
+        """Samples out for n in: ceil(n L / M)."""
+        return -(-n * self.L // self.M)
+
+    def reset(self) -> None:
+        check(lib().mio_hip_resampler_reset(self.h))
+
+    def __call__(self, x: np.ndarray, gain: float = 1.0, flush: bool = False, pcm16: bool = False) -> np.ndarray:
+        """The next samples of the stream (host float32) through mio_hip_resample: the outputs
+        they complete (flush: and the rest of the stream), float32 or, with pcm16, int16."""
+        x = np.ascontiguousarray(x, np.float32)
+        cap = self.out_len(x.size + self.delay) + 1
+        d_in = self.dev.upload(x if x.size else np.zeros(1, np.float32))
+        d_out = self.dev.empty((cap,), np.int16 if pcm16 else np.float32)
+        n = ctypes.c_int64(0)
+        check(lib().mio_hip_resample(self.h, d_in.ptr, x.size, gain, None if pcm16 else d_out.ptr,
+                                     d_out.ptr if pcm16 else None, cap, ctypes.byref(n), int(flush), None))
+        return d_out.numpy()[: n.value]
+
+    def finish(self, samples: "DeviceArray", n: int, normalize: bool, pcm16: bool = True):
+        """mio_hip_pcm_finish_rate on a whole utterance of n device floats: (its ceil(n L / M)
+        samples at the output rate on the host, the native-rate peak or 0.0 when not normalizing)."""
+        cap = max(self.out_len(n), 1)
+        out = self.dev.empty((cap,), np.int16 if pcm16 else np.float32)
+        got, peak = ctypes.c_int64(0), ctypes.c_float(0)
+        check(lib().mio_hip_pcm_finish_rate(self.h, samples.ptr if n else None, n, int(normalize),
+                                            None if pcm16 else out.ptr, out.ptr if pcm16 else None, cap,
+                                            ctypes.byref(got), ctypes.byref(peak), None))
+        return out.numpy()[: got.value], peak.value
 
 
 class Istft:
