@@ -209,8 +209,28 @@ int mio_hip_codec_decode_stage(mio_hip_codec *c, const int32_t *codes, int n_cod
  * Q3_K (IQ4_XS) token_embd.weight loads in a file whose layer 0 is Q3_K (IQ4_XS),
  * F16 KV cache of n_ctx positions (0 -> 2048, :104). A file whose matrices are all BF16 (lfm2
  * short-conv layers included) runs on every path; BF16 matrices beside quantized ones load and
- * decode single-stream, with the prompt as forced decode steps and no batched decode. */
+ * decode single-stream, with the prompt as forced decode steps and no batched decode.
+ * The cache type follows the policy switch MIO_KV_TYPE (f16, the default, or q8_0: see
+ * mio_hip_llm_load_kv; any other value is MIO_ERR_UNSUPPORTED). */
 int mio_hip_llm_load(mio_hip_device *d, const char *gguf_path, int n_ctx, mio_hip_llm **out);
+/* mio_hip_llm_load with the KV cache type given (llama.cpp's -ctk / -ctv, one type for both):
+ * kv_type 1 (GGML_F16, what mio_hip_llm_load makes by default) or 8 (GGML_Q8_0); anything else is
+ * MIO_ERR_UNSUPPORTED with the type named. The choice is independent of the weight types.
+ * Q8_0: per layer and kv head, codes int8 [n_kv][n_ctx][head_dim] and scales f16 [n_kv][n_ctx]
+ * [head_dim / 32]: 34 bytes per 32 values instead of 64 (0.53 x the cache's memory and of the
+ * bytes every attention launch reads). A row is ggml's quantize_row_q8_0_ref of the f16-exact k / v
+ * values the F16 cache would store: per 32 values d = amax / 127 in f32, id = d ? 1 / d : 0,
+ * q = roundf(x * id) (half away from zero), d stored as f16 (round to nearest even). Attention
+ * consumes f16(float(d_f16) * q), rounded to nearest even, for every row including the one the
+ * running step appends: this rounding of the cached rows is the one place where the two cache
+ * types differ numerically (everything after it, the matrix-core attention and the merge, is the
+ * same code). Prefill, single-stream decode and batched decode stay equal to each other bit for
+ * bit on either type. What it costs: the single-stream step runs its attention block as three
+ * launches (kinds 0, 1, 2 of mio_hip_llm_step_kinds) whatever MIO_ATT_FUSE_O / MIO_LAYER_ATT say,
+ * since the fused launches read the F16 cache only; DESIGN 4 has the measurements. */
+int mio_hip_llm_load_kv(mio_hip_device *d, const char *gguf_path, int n_ctx, int kv_type, mio_hip_llm **out);
+/* *type = the handle's KV cache type: 1 (GGML_F16) or 8 (GGML_Q8_0). */
+int mio_hip_llm_kv_type(const mio_hip_llm *m, int *type);
 void mio_hip_llm_free(mio_hip_llm *m);
 /* info[8] = {n_vocab, n_embd, n_layer, n_head, n_head_kv, head_dim, n_ff, n_ctx} */
 int mio_hip_llm_info(const mio_hip_llm *m, int *info);

@@ -74,6 +74,17 @@ int mio_hip_debug_mmq(mio_hip_device *d, uint32_t type, const void *gguf_rows, i
  * The inverse of mio_hip_llm_kv_rows: f16 bit patterns k, v [n_kv][n_pos][head_dim] are written to
  * cache positions [p0, p0 + n_pos) of layer il. */
 int mio_hip_llm_set_kv_rows(mio_hip_llm *m, int il, int p0, int n_pos, const uint16_t *k, const uint16_t *v);
+/* The same for a handle with a Q8_0 KV cache (mio_hip_llm_load_kv, kv_type 8): codes kq, vq
+ * [n_kv][n_pos][head_dim] and f16 scale bit patterns ks, vs [n_kv][n_pos][head_dim / 32] of layer
+ * il's rows [0, n_pos) read back, or written to rows [p0, p0 + n_pos). slot -1: the handle's own
+ * cache; 0..: that slot of the batch caches (MIO_ERR_INVALID before the batch state exists, as for a
+ * short-conv layer or a range outside the cache). MIO_ERR_UNSUPPORTED on an F16 handle; on a Q8_0
+ * handle mio_hip_llm_kv_rows, mio_hip_llm_set_kv_rows and their batch forms are MIO_ERR_UNSUPPORTED,
+ * and mio_hip_llm_debug_attention (which 1) / _debug_attention_multi run the Q8_0 launches. */
+int mio_hip_llm_kv_rows_q8(mio_hip_llm *m, int slot, int il, int n_pos, int8_t *kq, uint16_t *ks, int8_t *vq,
+                           uint16_t *vs);
+int mio_hip_llm_set_kv_rows_q8(mio_hip_llm *m, int slot, int il, int p0, int n_pos, const int8_t *kq,
+                               const uint16_t *ks, const int8_t *vq, const uint16_t *vs);
 /* One attention launch of layer il at position pos on the raw q|k|v row qkv[(H + 2 Hkv) * hd]
  * (the projections' output: bias, q/k norm, RoPE and the f16 rounding are the launch's own):
  * which = 1 the attention launch, 10 the attention + O launch (MIO_ERR_UNSUPPORTED where the

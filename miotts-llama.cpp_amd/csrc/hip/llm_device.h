@@ -2334,6 +2334,29 @@ __device__ __forceinline__ void attn_merge_owner(const float *part, uint32_t hea
     attn_merge_store<HD, G>(part, head0, g_stride, nch, out, -1, {}, 0, rdy, tl);
 }
 
+// The multi-token launches (llm_prefill.hip; llm_attention_q8.hip on the Q8_0 cache):
+// attend_chunk_mfma + attn_merge_last of token t's (kv head, chunk): records in pb.part
+// [t][H][max_splits][REC], tickets pb.att_cnt[t][Hkv], outputs pb.att[t][H * hd].
+// att_q >= 0: the merger also writes token t's O-matvec activation record (attn_merge_last).
+template <int HD, int G>
+__device__ __forceinline__ void merge_token(const LlmDims &d, int pos, int t, int kvh, const PrefillBuffers &pb,
+                                            int att_q, float *part, uint32_t head0, uint32_t gs) {
+    const int KO = d.n_head * HD;
+    attn_merge_last<HD, G>(part, head0, gs, pos / ATT_CHUNK + 1, pb.att_cnt + (size_t)t * d.n_kv + kvh,
+                           pb.att + (size_t)t * KO + (size_t)kvh * G * HD, att_q, carve_t(pb.act, KO, t).a,
+                           att_q == 1 ? kvh * G * HD / 256 : kvh * G * HD / 32);
+}
+template <int HD, int G>
+__device__ __forceinline__ void attend_and_merge(const LlmDims &d, const _Float16 (*qh)[HD], const char *img, int t0,
+                                                 int pos, int ch, int t, int kvh, const PrefillBuffers &pb, int att_q) {
+    using C = AttCfg<HD>;
+    const uint32_t gs = (uint32_t)(d.max_splits * C::REC);
+    float *part = pb.part + (size_t)t * d.n_head * gs;  // token t's records (wave-uniform)
+    const uint32_t head0 = (uint32_t)(kvh * G) * gs;
+    attend_chunk_mfma<HD, G>(qh, img, img + AttM<HD>::IMG, t0, pos, d.scale, part + head0 + (uint32_t)ch * C::REC, gs);
+    merge_token<HD, G>(d, pos, t, kvh, pb, att_q, part, head0, gs);
+}
+
 // ------------------------------------------------------------------ host-side dispatch
 // Calls f.template operator()<SU>() for the instantiated single-group sizes of NP.
 template <int NP, class F>

@@ -77,6 +77,24 @@ constexpr int kChainHistMax = 256;
 constexpr int kConvL = 3;
 constexpr int kConvSlots = 4;
 
+// The opt-in Q8_0 K/V cache (mio_hip_llm_load_kv, kv type GGML_Q8_0) in the split style of the
+// weight planes, per sequence: codes int8 [n_layer][n_kv][n_ctx][hd] and scales f16 [n_layer][n_kv]
+// [n_ctx][hd / 32] for K and for V. A row is ggml's quantize_row_q8_0_ref of the f16-exact k / v
+// values the F16 cache would store, and attention consumes f16(float(d) * q) (csrc/hip/llm_kv_q8.h).
+// All pointers null: the F16 cache. The kernels that read it (csrc/hip/llm_attention_q8.hip) get the
+// four planes as arguments of their own, so no launch of the F16 cache changes.
+struct KvQ8 {
+    int8_t *kq, *vq;
+    _Float16 *ks, *vs;
+    explicit operator bool() const { return kq != nullptr; }
+    // the planes `rows` cache rows of head dim hd further on (a layer, a sequence)
+    KvQ8 at(size_t rows, int hd) const {
+        return *this ? KvQ8{kq + rows * hd, vq + rows * hd, ks + rows * (hd / 32), vs + rows * (hd / 32)} : *this;
+    }
+};
+// bytes of one cache row of one kv head, K or V: hd codes + hd / 32 f16 scales (F16: 2 hd)
+constexpr size_t kv_q8_row_bytes(int hd) { return (size_t)hd + (size_t)(hd / 32) * 2; }
+
 struct LayerW {
     const float *attn_norm, *q_norm, *k_norm, *ffn_norm;
     const float *bqkv;  // [(H + 2 Hkv) hd] q|k|v biases (qwen2 attn_{q,k,v}.bias), or null
@@ -161,9 +179,10 @@ int prefill_rec_k(int K, int type);
 // One chunk of nt <= kPrefillB tokens (ids at tokens[p0 + t], positions/sequences from
 // pb.pos / pb.seq) through every layer: embedding, K/V rows, residual streams in pb.x.
 // n_chunks = attention chunks to sweep (>= max position / kAttChunk + 1).
+// q8 (here and below): the Q8_0 cache of the same sequences; kcache / vcache are then unused.
 void launch_prefill_chunk(const LlmDims &d, const LayerW *layers, int n_layer, _Float16 *kcache,
                           _Float16 *vcache, const QMat &tok_embd, const PrefillBuffers &pb, int p0, int nt,
-                          int n_chunks, hipStream_t s);
+                          int n_chunks, hipStream_t s, const KvQ8 &q8 = {});
 
 // Batched decode of B <= kBatchMax streams: per stream b, state st[b], sampling cfg[b]
 // (cfg[b].out_tokens[step] = where the token of that step goes: the output region of the utterance
@@ -180,7 +199,7 @@ struct BatchBuffers {
 // embedding + state advance.
 void launch_batch_step(const LlmDims &d, const LayerW *layers, int n_layer, _Float16 *kcache, _Float16 *vcache,
                        const float *out_norm, const QMat &lm, const QMat &tok_embd, const PrefillBuffers &pb,
-                       const BatchBuffers &bb, int B, bool chain, hipStream_t s);
+                       const BatchBuffers &bb, int B, bool chain, hipStream_t s, const KvQ8 &q8 = {});
 // B streams fit one batched step (B <= kBatchMax and the lm_head's LDS for its weight type)
 bool batch_supported(const LlmDims &d, int B, int lm_type);
 // How a batched step of B streams would run, with nothing launched: per layer four codes (q|k|v or
@@ -250,6 +269,7 @@ struct StepCtx {
     _Float16 *kc, *vc;
     const float *out_norm;
     QMat lm, tok;
+    KvQ8 q8;  // the Q8_0 cache (then kc / vc are null and kAttention is k_attention_q8)
 };
 // The sampler chain launch: stream t (one workgroup each, B of them) reads logits + t * stride,
 // st[t], cfg[t] and rewrites its nblk sampling partials smp + t * nblk * 2. dbg (parity entry,
@@ -341,6 +361,13 @@ void launch_debug_mmq(const QMat &W, const QMat &up, int mode, const float *x, i
 // cache; decode: k_bt_attention, else k_pf_rope + k_pf_attention; att_q as merger_records gives it.
 void launch_debug_attention_multi(const LlmDims &d, const LayerW &L, _Float16 *kc, _Float16 *vc,
                                   const PrefillBuffers &pb, int nt, int n_chunks, bool decode, int att_q,
-                                  hipStream_t s);
+                                  hipStream_t s, const KvQ8 &q8 = {});
+// The Q8_0 cache's attention launches (csrc/hip/llm_attention_q8.hip), kv = the layer's planes of
+// sequence 0: the decode step's k_attention_q8 (grid (max_splits, n_kv), as k_attention), and the
+// multi-token layers' (decode: k_bt_attention_q8, else k_pf_rope_q8 + k_pf_attention_q8; the
+// sequence offset is pb.seq_kv rows' worth of each plane).
+void launch_attention_q8(const LlmDims &d, const LayerW &L, const KvQ8 &kv, const LlmBuffers &b, hipStream_t s);
+void launch_mt_attention_q8(const LlmDims &d, const LayerW &L, const KvQ8 &kv, const PrefillBuffers &pb, int nt,
+                            int n_chunks, bool decode, int att_q, hipStream_t s);
 
 }  // namespace mio

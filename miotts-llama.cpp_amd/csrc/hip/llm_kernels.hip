@@ -635,7 +635,9 @@ void launch_step_kernel(StepKind which, const StepCtx &c, int il, const LlmBuffe
         case kAttention: {
             const LayerW &L = layers[il];
             const dim3 grid(d.max_splits, d.n_kv);
-            if (d.hd == 128)
+            if (c.q8) {  // the Q8_0 cache: k_attention_q8 (llm_attention_q8.hip)
+                launch_attention_q8(d, L, c.q8.at(il * layer_kv / d.hd, d.hd), b, s);
+            } else if (d.hd == 128)
                 launch_attention<128, DG>(G, grid, s, d, L, kcache + il * layer_kv, vcache + il * layer_kv, b);
             else
                 launch_attention<64, DG>(G, grid, s, d, L, kcache + il * layer_kv, vcache + il * layer_kv, b);

@@ -596,28 +596,7 @@ __global__ __launch_bounds__(64) void k_pf_rope(LlmDims d, const float *q_norm, 
     }
 }
 
-// attend_chunk_mfma + attn_merge_last of token t's (kv head, chunk): records in pb.part
-// [t][H][max_splits][REC], tickets pb.att_cnt[t][Hkv], outputs pb.att[t][H * hd].
-// att_q >= 0: the merger also writes token t's O-matvec activation record (attn_merge_last).
-template <int HD, int G>
-__device__ __forceinline__ void merge_token(const LlmDims &d, int pos, int t, int kvh, const PrefillBuffers &pb,
-                                            int att_q, float *part, uint32_t head0, uint32_t gs) {
-    const int KO = d.n_head * HD;
-    attn_merge_last<HD, G>(part, head0, gs, pos / ATT_CHUNK + 1, pb.att_cnt + (size_t)t * d.n_kv + kvh,
-                           pb.att + (size_t)t * KO + (size_t)kvh * G * HD, att_q, carve_t(pb.act, KO, t).a,
-                           att_q == 1 ? kvh * G * HD / 256 : kvh * G * HD / 32);
-}
-template <int HD, int G>
-__device__ __forceinline__ void attend_and_merge(const LlmDims &d, const _Float16 (*qh)[HD], const char *img, int t0,
-                                                 int pos, int ch, int t, int kvh, const PrefillBuffers &pb, int att_q) {
-    using C = AttCfg<HD>;
-    const uint32_t gs = (uint32_t)(d.max_splits * C::REC);
-    float *part = pb.part + (size_t)t * d.n_head * gs;  // token t's records (wave-uniform)
-    const uint32_t head0 = (uint32_t)(kvh * G) * gs;
-    attend_chunk_mfma<HD, G>(qh, img, img + AttM<HD>::IMG, t0, pos, d.scale, part + head0 + (uint32_t)ch * C::REC, gs);
-    merge_token<HD, G>(d, pos, t, kvh, pb, att_q, part, head0, gs);
-}
-
+// (merge_token / attend_and_merge: llm_device.h, shared with the Q8_0 cache's launches)
 // One workgroup per (ATT_CHUNK-position chunk, kv head, token): causal softmax over the
 // chunk's positions <= the token's position in the token's own sequence, all rows read from
 // the cache (this launch's own rows were written by k_pf_rope); the attention and
@@ -1416,8 +1395,10 @@ struct LayerRun {
 
     // RoPE + K/V rows + attention of nt tokens; the merger writes pb.att and, with att_q >= 0,
     // the O matvec's act records. decode: all inside k_bt_attention, per token.
-    void attention(const LayerW &L, _Float16 *kc, _Float16 *vc, int n_chunks, int att_q) const {
+    // q8: the layer's planes of the Q8_0 cache (llm_attention_q8.hip has the launches).
+    void attention(const LayerW &L, _Float16 *kc, _Float16 *vc, int n_chunks, int att_q, const KvQ8 &q8 = {}) const {
         if (report) return;
+        if (q8) return launch_mt_attention_q8(d, L, q8, pb, nt, n_chunks, decode, att_q, s);
         const int G = d.n_head / d.n_kv;
         const dim3 grid(d.n_kv * nt, n_chunks);
         dispatch_hd(d.hd, [&]<int HD>() {
@@ -1444,7 +1425,7 @@ struct LayerRun {
 // site (sub-launches only where a token range does not fit LDS).
 void launch_layers(const LlmDims &d, const LayerW *layers, int n_layer, _Float16 *kcache, _Float16 *vcache,
                    const PrefillBuffers &pb, int nt, int n_chunks, bool decode, hipStream_t s,
-                   std::vector<int> *report = nullptr) {
+                   std::vector<int> *report = nullptr, const KvQ8 &q8 = {}) {
     LayerRun r{d, pb, nt, decode, s};
     r.report = report;
     const size_t layer_kv = (size_t)d.n_kv * d.n_ctx * d.hd;
@@ -1460,7 +1441,8 @@ void launch_layers(const LlmDims &d, const LayerW *layers, int n_layer, _Float16
         } else {
             const int att_q = merger_records(r.sw, L.wo.type, d.n_head / d.n_kv * d.hd);
             r.run({kSiteQkv, {L.wq, L.wk, L.wv}, 3, {}, n, kInNorm, pb.x, L.attn_norm, MMQ_STORE, pb.qkv, QD, QD});
-            r.attention(L, kcache + il * layer_kv, vcache + il * layer_kv, n_chunks, att_q);
+            r.attention(L, kcache + il * layer_kv, vcache + il * layer_kv, n_chunks, att_q,
+                        q8.at(il * layer_kv / d.hd, d.hd));
             r.run({kSiteO, {L.wo}, 1, {}, L.wo.k, att_q < 0 ? kInPlain : kInRecords, pb.att, nullptr, MMQ_RESID, pb.x, n,
                    QD});
         }
@@ -1473,11 +1455,11 @@ void launch_layers(const LlmDims &d, const LayerW *layers, int n_layer, _Float16
 
 void launch_prefill_chunk(const LlmDims &d, const LayerW *layers, int n_layer, _Float16 *kcache,
                           _Float16 *vcache, const QMat &tok_embd, const PrefillBuffers &pb, int p0, int nt,
-                          int n_chunks, hipStream_t s) {
+                          int n_chunks, hipStream_t s, const KvQ8 &q8) {
     if (nt <= 0) return;
     hipLaunchKernelGGL(for_table_te(tok_embd, []<int TE>() { return k_pf_embed<TE>; }), dim3(nt), dim3(ST), 0, s, d, tok_embd,
                        pb, p0);
-    launch_layers(d, layers, n_layer, kcache, vcache, pb, nt, n_chunks, false, s);
+    launch_layers(d, layers, n_layer, kcache, vcache, pb, nt, n_chunks, false, s, nullptr, q8);
 }
 
 size_t prefill_act_bytes(int k_max) { return act_bytes(k_max) * kPrefillB; }
@@ -1499,9 +1481,9 @@ void launch_debug_mmq(const QMat &W, const QMat &up, int mode, const float *x, i
 // parity entry (mio_hip_llm_debug_attention_multi): LayerRun::attention of one layer, alone
 void launch_debug_attention_multi(const LlmDims &d, const LayerW &L, _Float16 *kc, _Float16 *vc,
                                   const PrefillBuffers &pb, int nt, int n_chunks, bool decode, int att_q,
-                                  hipStream_t s) {
+                                  hipStream_t s, const KvQ8 &q8) {
     const LayerRun r{d, pb, nt, decode, s};
-    r.attention(L, kc, vc, n_chunks, att_q);
+    r.attention(L, kc, vc, n_chunks, att_q, q8);
 }
 
 size_t batch_lm_head_lds(const LlmDims &d, int B, int type) {
@@ -1529,8 +1511,8 @@ void batch_step_plan(const LlmDims &d, const LayerW *layers, int n_layer, const 
 
 void launch_batch_step(const LlmDims &d, const LayerW *layers, int n_layer, _Float16 *kcache, _Float16 *vcache,
                        const float *out_norm, const QMat &lm, const QMat &tok_embd, const PrefillBuffers &pb,
-                       const BatchBuffers &bb, int B, bool chain, hipStream_t s) {
-    launch_layers(d, layers, n_layer, kcache, vcache, pb, B, d.max_splits, true, s);
+                       const BatchBuffers &bb, int B, bool chain, hipStream_t s, const KvQ8 &q8) {
+    launch_layers(d, layers, n_layer, kcache, vcache, pb, B, d.max_splits, true, s, nullptr, q8);
     LayerRun r{d, pb, B, true, s};
     const Site head = lm_head_site(d, lm, out_norm, pb, bb.logits);
     const int nblk = matvec_grid(d, d.n_vocab);  // the batched lm_head keeps one workgroup per CU

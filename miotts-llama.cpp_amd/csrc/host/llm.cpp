@@ -25,9 +25,10 @@ bool no_graph() {
 
 // MIO_ATT_FUSE_O (default 1): attention + O as one launch (k_att_o, kAttO) where the head
 // shape has it; 0 keeps the two launches (A/B).
+// A Q8_0 cache has the three launches only (k_attention_q8), whatever the switches say.
 bool fuse_att_o(const mio_hip_llm *m) {
     static const bool env = env_flag("MIO_ATT_FUSE_O", true);
-    return env && m->dims.n_kv <= mio::kRdyOff && mio::att_o_supported(m->dims.hd, m->dims.n_head / m->dims.n_kv);
+    return env && m->kv_type == mio::GGML_F16 && m->dims.n_kv <= mio::kRdyOff && mio::att_o_supported(m->dims.hd, m->dims.n_head / m->dims.n_kv);
 }
 
 // MIO_LAYER_ATT (default 1): layers >= 1 run their whole attention block as one launch
@@ -271,7 +272,7 @@ int prefill_issue(mio_hip_llm *m, int n) {
         pb.seq = m->d_iota, pb.seq_stride = 0;       // one sequence: the model's own cache
         pb.seq_kv = 0;
         mio::launch_prefill_chunk(m->dims, m->layers.data(), m->n_layer, m->kc, m->vc, m->tok, pb, p0, nt,
-                                  (p0 + nt - 1) / mio::kAttChunk + 1, m->d->stream);
+                                  (p0 + nt - 1) / mio::kAttChunk + 1, m->d->stream, m->q8);
         MIO_HIP_CHECK(hipGetLastError());
     }
     return MIO_OK;

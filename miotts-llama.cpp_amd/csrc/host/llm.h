@@ -46,6 +46,11 @@ uint64_t llm_step_weight_bytes(const mio_hip_llm *m);
 // F16 rows k, v [n_kv][n_pos][head_dim] into cache positions [p0, p0 + n_pos) of layer il (the
 // inverse of mio_hip_llm_kv_rows).
 int llm_set_kv_rows(mio_hip_llm *m, int il, int p0, int n_pos, const uint16_t *k, const uint16_t *v);
+// The same for a Q8_0 cache, both directions (set: write): codes kq, vq [n_kv][n_pos][head_dim] and
+// scale bit patterns ks, vs [n_kv][n_pos][head_dim / 32] of rows [p0, p0 + n_pos) of layer il;
+// slot -1 the handle's own cache, else a slot of the batch caches.
+int llm_kv_rows_q8(mio_hip_llm *m, bool set, int slot, int il, int p0, int n_pos, int8_t *kq, uint16_t *ks, int8_t *vq,
+                   uint16_t *vs);
 // One attention launch of layer il at position pos on the raw q|k|v row qkv[(H + 2 Hkv) hd]:
 // which = 1 (k_attention) or 10 (k_att_o); att[H hd] receives LlmBuffers.att. Leaves the decode
 // state at pos and cache row pos written.

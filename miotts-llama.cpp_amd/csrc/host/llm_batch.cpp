@@ -34,8 +34,16 @@ int batch_ensure(mio_hip_llm *m, int B) {
         hipMemsetAsync(p, 0, bytes + 256, m->d->stream);
         return p;
     };
-    bt.kc = (_Float16 *)al((size_t)B * seq_kv * 2);
-    bt.vc = (_Float16 *)al((size_t)B * seq_kv * 2);
+    const bool q8 = m->kv_type == mio::GGML_Q8_0;
+    bt.kc = bt.vc = nullptr, bt.q8 = {};
+    if (q8) {
+        bt.q8 = mio::KvQ8{(int8_t *)al((size_t)B * seq_kv), (int8_t *)al((size_t)B * seq_kv),
+                          (_Float16 *)al((size_t)B * seq_kv / 32 * 2), (_Float16 *)al((size_t)B * seq_kv / 32 * 2)};
+    } else {
+        bt.kc = (_Float16 *)al((size_t)B * seq_kv * 2);
+        bt.vc = (_Float16 *)al((size_t)B * seq_kv * 2);
+    }
+    const bool kv_ok = q8 ? bt.q8.kq && bt.q8.vq && bt.q8.ks && bt.q8.vs : bt.kc && bt.vc;
     bt.st = (mio::StepState *)al((size_t)B * sizeof(mio::StepState));
     bt.cfg = (mio::SampleCfg *)al((size_t)B * sizeof(mio::SampleCfg));
     bt.logits = (float *)al((size_t)B * D.n_vocab * 4);
@@ -44,7 +52,7 @@ int batch_ensure(mio_hip_llm *m, int B) {
     bt.pseq = (int *)al((size_t)B * D.n_ctx * 4);
     bt.ptok = (int *)al((size_t)B * D.n_ctx * 4);
     bt.ring = m->buf.ring ? (float *)al(B * batch_seq_ring(m) * 4) : nullptr;
-    if (!bt.kc || !bt.vc || !bt.st || !bt.cfg || !bt.logits || !bt.smp || !bt.ppos || !bt.pseq || !bt.ptok ||
+    if (!kv_ok || !bt.st || !bt.cfg || !bt.logits || !bt.smp || !bt.ppos || !bt.pseq || !bt.ptok ||
         (m->buf.ring && !bt.ring)) {
         for (void *p : bt.allocs) hipFree(p);
         bt.allocs.clear();
@@ -79,7 +87,7 @@ mio::BatchBuffers batch_bb(mio_hip_llm *m) { return mio::BatchBuffers{m->bt.st, 
 int issue_batch_steps(mio_hip_llm *m, int n, bool chain) {
     for (int i = 0; i < n; ++i)
         mio::launch_batch_step(m->dims, m->layers.data(), m->n_layer, m->bt.kc, m->bt.vc, m->out_norm, m->lm, m->tok,
-                               step_pb(m), batch_bb(m), m->bt.B, chain, m->d->stream);
+                               step_pb(m), batch_bb(m), m->bt.B, chain, m->d->stream, m->bt.q8);
     return MIO_OK;
 }
 
@@ -195,7 +203,7 @@ int queue_run(const char *who, mio_hip_llm *m, const int32_t *prompts, const int
                 mio::PrefillBuffers pb = batch_pb(m, bt.ppos + c0, 1, bt.pseq + c0);
                 pb.tokens = bt.ptok;
                 mio::launch_prefill_chunk(D, m->layers.data(), m->n_layer, bt.kc, bt.vc, m->tok, pb, c0, nt,
-                                          pmax / mio::kAttChunk + 1, s);
+                                          pmax / mio::kAttChunk + 1, s, bt.q8);
             }
             mio::launch_queue_admit(D, m->tok, step_pb(m), batch_bb(m), bt.cfg, base, qb, r, S, s);
             MIO_HIP_CHECK(hipGetLastError());

@@ -77,6 +77,8 @@ extern "C" int mio_hip_llm_eval_layers(mio_hip_llm *m, int32_t token, int pos, f
 extern "C" int mio_hip_llm_kv_rows(mio_hip_llm *m, int il, int n_pos, uint16_t *k, uint16_t *v) {
     MIO_REQUIRE(m && k && v && il >= 0 && il < m->n_layer && n_pos >= 0 && n_pos <= m->dims.n_ctx, MIO_ERR_INVALID,
                 "llm_kv_rows: bad args");
+    MIO_REQUIRE(m->kv_type == mio::GGML_F16, MIO_ERR_UNSUPPORTED,
+                "%s: the handle's KV cache is q8_0 (mio_hip_llm_kv_rows_q8 / _set_kv_rows_q8)", "llm_kv_rows");
     int rc = mio::bind(m->d);
     if (rc) return rc;
     const mio::LlmDims &D = m->dims;
@@ -96,6 +98,8 @@ int mio::llm_set_kv_rows(mio_hip_llm *m, int il, int p0, int n_pos, const uint16
     MIO_REQUIRE(m && k && v && il >= 0 && il < m->n_layer && p0 >= 0 && n_pos >= 0 && p0 <= m->dims.n_ctx &&
                     n_pos <= m->dims.n_ctx - p0,
                 MIO_ERR_INVALID, "llm_set_kv_rows: bad args");
+    MIO_REQUIRE(m->kv_type == mio::GGML_F16, MIO_ERR_UNSUPPORTED,
+                "%s: the handle's KV cache is q8_0 (mio_hip_llm_kv_rows_q8 / _set_kv_rows_q8)", "llm_set_kv_rows");
     int rc = mio::bind(m->d);
     if (rc) return rc;
     const mio::LlmDims &D = m->dims;
@@ -104,6 +108,39 @@ int mio::llm_set_kv_rows(mio_hip_llm *m, int il, int p0, int n_pos, const uint16
         const size_t dst = (((size_t)il * D.n_kv + h) * D.n_ctx + p0) * D.hd, src = (size_t)h * n_pos * D.hd;
         MIO_HIP_CHECK(hipMemcpyAsync(m->kc + dst, k + src, (size_t)n_pos * D.hd * 2, hipMemcpyHostToDevice, s));
         MIO_HIP_CHECK(hipMemcpyAsync(m->vc + dst, v + src, (size_t)n_pos * D.hd * 2, hipMemcpyHostToDevice, s));
+    }
+    MIO_HIP_CHECK(hipStreamSynchronize(s));
+    return MIO_OK;
+}
+
+// Rows [p0, p0 + n_pos) of layer il of a Q8_0 cache (parity tests), read (set = false) or written:
+// codes kq, vq [n_kv][n_pos][head_dim], scale bit patterns ks, vs [n_kv][n_pos][head_dim / 32].
+// slot -1: the handle's own cache; else slot `slot` of the batch caches.
+int mio::llm_kv_rows_q8(mio_hip_llm *m, bool set, int slot, int il, int p0, int n_pos, int8_t *kq, uint16_t *ks,
+                        int8_t *vq, uint16_t *vs) {
+    MIO_REQUIRE(m && kq && ks && vq && vs, MIO_ERR_INVALID, "llm_kv_rows_q8: null argument");
+    MIO_REQUIRE(m->kv_type == mio::GGML_Q8_0, MIO_ERR_UNSUPPORTED,
+                "llm_kv_rows_q8: the handle's KV cache is f16 (mio_hip_llm_kv_rows / _set_kv_rows)");
+    MIO_REQUIRE(slot >= -1 && slot < m->bt.B && il >= 0 && il < m->n_layer && p0 >= 0 && n_pos >= 0 &&
+                    p0 <= m->dims.n_ctx && n_pos <= m->dims.n_ctx - p0,
+                MIO_ERR_INVALID, "llm_kv_rows_q8: slot %d / layer %d / rows [%d, +%d) out of range", slot, il, p0, n_pos);
+    MIO_REQUIRE(!m->layers[il].conv, MIO_ERR_INVALID, "llm_kv_rows_q8: layer %d is a short-conv layer", il);
+    int rc = mio::bind(m->d);
+    if (rc) return rc;
+    const mio::LlmDims &D = m->dims;
+    hipStream_t s = m->d->stream;
+    const size_t seq_rows = (size_t)m->n_layer * D.n_kv * D.n_ctx, nb = D.hd / 32;
+    const mio::KvQ8 c = slot < 0 ? m->q8 : m->bt.q8.at((size_t)slot * seq_rows, D.hd);
+    const hipMemcpyKind kind = set ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
+    auto copy = [&](void *host, void *dev, size_t bytes) {
+        return set ? hipMemcpyAsync(dev, host, bytes, kind, s) : hipMemcpyAsync(host, dev, bytes, kind, s);
+    };
+    for (int h = 0; h < D.n_kv && n_pos > 0; ++h) {
+        const size_t dr = ((size_t)il * D.n_kv + h) * D.n_ctx + p0, hr = (size_t)h * n_pos;
+        MIO_HIP_CHECK(copy(kq + hr * D.hd, c.kq + dr * D.hd, (size_t)n_pos * D.hd));
+        MIO_HIP_CHECK(copy(vq + hr * D.hd, c.vq + dr * D.hd, (size_t)n_pos * D.hd));
+        MIO_HIP_CHECK(copy(ks + hr * nb, c.ks + dr * nb, (size_t)n_pos * nb * 2));
+        MIO_HIP_CHECK(copy(vs + hr * nb, c.vs + dr * nb, (size_t)n_pos * nb * 2));
     }
     MIO_HIP_CHECK(hipStreamSynchronize(s));
     return MIO_OK;
@@ -141,6 +178,8 @@ int mio::llm_debug_attention(mio_hip_llm *m, int il, int pos, int which, const f
     MIO_REQUIRE(which == kAttention || (D.n_kv <= mio::kRdyOff && mio::att_o_supported(D.hd, D.n_head / D.n_kv) &&
                                         m->layers[il].wo.k <= 2048),  // k_att_o: one 2048-weight pass of W_o
                 MIO_ERR_UNSUPPORTED, "llm_debug_attention: no attention + O launch for this shape");
+    MIO_REQUIRE(which == kAttention || m->kv_type == mio::GGML_F16, MIO_ERR_UNSUPPORTED,
+                "llm_debug_attention: a q8_0 KV cache has no attention + O launch");
     int rc = mio::bind(m->d);
     if (rc) return rc;
     hipStream_t s = m->d->stream;
@@ -251,6 +290,8 @@ int mio::llm_batch_logits(mio_hip_llm *m, float *logits) {
 int mio::llm_batch_kv_rows(mio_hip_llm *m, int slot, int il, int n_pos, uint16_t *k, uint16_t *v) {
     MIO_REQUIRE(m && k && v, MIO_ERR_INVALID, "llm_batch_kv_rows: null argument");
     MIO_REQUIRE(m->bt.B > 0, MIO_ERR_INVALID, "llm_batch_kv_rows: no batched call has run on this handle");
+    MIO_REQUIRE(m->kv_type == mio::GGML_F16, MIO_ERR_UNSUPPORTED,
+                "%s: the handle's KV cache is q8_0 (mio_hip_llm_kv_rows_q8 / _set_kv_rows_q8)", "llm_batch_kv_rows");
     MIO_REQUIRE(slot >= 0 && slot < m->bt.B && il >= 0 && il < m->n_layer && n_pos >= 0 && n_pos <= m->dims.n_ctx,
                 MIO_ERR_INVALID, "llm_batch_kv_rows: slot %d / layer %d / %d rows out of range", slot, il, n_pos);
     MIO_REQUIRE(!m->layers[il].conv, MIO_ERR_INVALID, "llm_batch_kv_rows: layer %d is a short-conv layer", il);
@@ -275,6 +316,8 @@ int mio::llm_batch_set_kv_rows(mio_hip_llm *m, int slot, int il, int p0, int n_p
                                const uint16_t *v) {
     MIO_REQUIRE(m && k && v, MIO_ERR_INVALID, "llm_batch_set_kv_rows: null argument");
     MIO_REQUIRE(m->bt.B > 0, MIO_ERR_INVALID, "llm_batch_set_kv_rows: this handle has no batch state yet");
+    MIO_REQUIRE(m->kv_type == mio::GGML_F16, MIO_ERR_UNSUPPORTED,
+                "%s: the handle's KV cache is q8_0 (mio_hip_llm_kv_rows_q8 / _set_kv_rows_q8)", "llm_batch_set_kv_rows");
     MIO_REQUIRE(slot >= 0 && slot < m->bt.B && il >= 0 && il < m->n_layer && p0 >= 0 && n_pos >= 0 &&
                     p0 <= m->dims.n_ctx && n_pos <= m->dims.n_ctx - p0,
                 MIO_ERR_INVALID, "llm_batch_set_kv_rows: slot %d / layer %d / rows [%d, +%d) out of range", slot, il, p0,
@@ -367,7 +410,8 @@ int mio::llm_debug_attention_multi(mio_hip_llm *m, int il, int mode, int slots, 
     }
     const size_t layer_kv = (size_t)D.n_kv * D.n_ctx * D.hd;
     mio::launch_debug_attention_multi(D, m->layers[il], (slots ? m->bt.kc : m->kc) + il * layer_kv,
-                                      (slots ? m->bt.vc : m->vc) + il * layer_kv, pb, nt, n_chunks, mode == 1, att_q, s);
+                                      (slots ? m->bt.vc : m->vc) + il * layer_kv, pb, nt, n_chunks, mode == 1, att_q, s,
+                                      (slots ? m->bt.q8 : m->q8).at(il * layer_kv / D.hd, D.hd));
     MIO_HIP_CHECK(hipGetLastError());
     MIO_HIP_CHECK(hipMemcpyAsync(rows.data(), m->pf.att, rows.size() * 4, hipMemcpyDeviceToHost, s));
     if (rec) MIO_HIP_CHECK(hipMemcpyAsync(rec, m->pf.act, (size_t)nt * rec_bytes, hipMemcpyDeviceToHost, s));
@@ -480,10 +524,12 @@ uint64_t kind_bytes(const mio_hip_llm *m, mio::StepKind kind, const mio::LayerW 
     const uint64_t part = 4ull * D.n_head * nch * (D.hd + 2);
     // x in + the q|k|v weights; q|k|v out only where another launch reads it
     const uint64_t attn_in_bytes = qbytes(L.wq) + qbytes(L.wk) + qbytes(L.wv) + 4ull * D.n_embd;
-    // attention: F16 K and V rows of positions 0..pos (the row at pos is written, the rest
-    // read) + q|k|v in + RoPE pair + partial records out and back + outputs
+    // attention: K and V rows of positions 0..pos (the row at pos is written, the rest read; F16
+    // rows of 2 hd bytes, Q8_0 rows of hd codes + hd / 32 f16 scales) + q|k|v in + RoPE pair +
+    // partial records out and back + outputs
+    const uint64_t row = m->kv_type == mio::GGML_Q8_0 ? mio::kv_q8_row_bytes(D.hd) : 2ull * D.hd;
     const uint64_t att_bytes =
-        2ull * 2 * D.n_kv * D.hd * (pos + 1) + 4ull * qkv + 8ull * (D.hd / 2) + 2 * part + 4ull * D.n_head * D.hd;
+        2ull * row * D.n_kv * (pos + 1) + 4ull * qkv + 8ull * (D.hd / 2) + 2 * part + 4ull * D.n_head * D.hd;
     const uint64_t o_bytes = qbytes(L.wo) + 4ull * D.n_head * D.hd + 4ull * D.n_embd * 2;
     const uint64_t ffn_in_bytes = qbytes(L.gate) + qbytes(L.up) + 4ull * (D.n_embd * 2 + D.n_ff);
     const uint64_t ffn_down_bytes = qbytes(L.down) + 4ull * (D.n_ff + 2 * D.n_embd);

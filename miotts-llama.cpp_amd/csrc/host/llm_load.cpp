@@ -355,8 +355,14 @@ int carve_buffers(const Load &ld, mio_hip_llm *m, float2 **rope) {
     // q|k|v rows, or an lfm2 short-conv layer's B | C | X rows
     const int qkv_rows = std::max(qkv, m->has_conv ? 3 * D.n_embd : 0);
     const size_t kv = (size_t)m->n_layer * D.n_kv * n_ctx * D.hd;
-    m->kc = dalloc<_Float16>(m, kv);
-    m->vc = dalloc<_Float16>(m, kv);
+    if (m->kv_type == mio::GGML_Q8_0) {
+        m->q8 = mio::KvQ8{dalloc<int8_t>(m, kv), dalloc<int8_t>(m, kv), dalloc<_Float16>(m, kv / 32),
+                          dalloc<_Float16>(m, kv / 32)};
+    } else {
+        m->kc = dalloc<_Float16>(m, kv);
+        m->vc = dalloc<_Float16>(m, kv);
+    }
+    const bool kv_ok = m->kv_type == mio::GGML_Q8_0 ? m->q8.kq && m->q8.vq && m->q8.ks && m->q8.vs : m->kc && m->vc;
     std::vector<std::pair<void **, size_t>> carve;
     auto want = [&](auto *&ptr, size_t count) {
         carve.push_back({reinterpret_cast<void **>(&ptr), count * sizeof(*ptr)});
@@ -403,7 +409,7 @@ int carve_buffers(const Load &ld, mio_hip_llm *m, float2 **rope) {
     for (auto &c : carve) io_bytes += (c.second + 255) & ~(size_t)255;
     uint8_t *io = dalloc<uint8_t>(m, (io_bytes + (2u << 20) - 1) & ~(size_t)((2u << 20) - 1));
     // a failed allocation leaves every carved pointer null
-    MIO_REQUIRE(m->kc && m->vc && io, MIO_ERR_OOM, "llm_load: device allocation failed");
+    MIO_REQUIRE(kv_ok && io, MIO_ERR_OOM, "llm_load: device allocation failed");
     size_t off = 0;
     for (auto &c : carve) {
         *c.first = io + off;
@@ -440,8 +446,26 @@ void upload_tables(const Load &ld, mio_hip_llm *m, float2 *dr) {
 
 }  // namespace
 
+// MIO_KV_TYPE (policy switch of mio_hip_llm_load): f16 (default) or q8_0.
 extern "C" int mio_hip_llm_load(mio_hip_device *d, const char *path, int n_ctx, mio_hip_llm **out) {
+    const char *e = getenv("MIO_KV_TYPE");
+    const std::string t = e ? e : "f16";
+    MIO_REQUIRE(t == "f16" || t == "q8_0", MIO_ERR_UNSUPPORTED, "llm_load: MIO_KV_TYPE '%s' not supported (f16, q8_0)",
+                t.c_str());
+    return mio_hip_llm_load_kv(d, path, n_ctx, t == "q8_0" ? mio::GGML_Q8_0 : mio::GGML_F16, out);
+}
+
+extern "C" int mio_hip_llm_kv_type(const mio_hip_llm *m, int *type) {
+    MIO_REQUIRE(m && type, MIO_ERR_INVALID, "llm_kv_type: null");
+    *type = m->kv_type;
+    return MIO_OK;
+}
+
+extern "C" int mio_hip_llm_load_kv(mio_hip_device *d, const char *path, int n_ctx, int kv_type, mio_hip_llm **out) {
     MIO_REQUIRE(d && path && out, MIO_ERR_INVALID, "llm_load: null argument");
+    MIO_REQUIRE(kv_type == mio::GGML_F16 || kv_type == mio::GGML_Q8_0, MIO_ERR_UNSUPPORTED,
+                "llm_load: KV cache type %d (%s) not supported (1 f16, 8 q8_0)", kv_type,
+                mio::ggml_type_name((uint32_t)kv_type));
     if (n_ctx <= 0) n_ctx = 2048;  // test-to-speech.cpp:104
     int rc = mio::bind(d);
     if (rc) return rc;
@@ -467,6 +491,7 @@ extern "C" int mio_hip_llm_load(mio_hip_device *d, const char *path, int n_ctx, 
     // owned from here on: every return below releases the model and what it has allocated
     auto m = std::make_unique<mio_hip_llm>();
     m->d = d;
+    m->kv_type = kv_type;
     m->stager = std::make_unique<Stager>();
     MIO_REQUIRE(m->stager->init(), MIO_ERR_HIP, "llm_load: staging stream failed");
     if ((rc = read_dims(ld, m.get())) || (rc = plan_arena(ld, m.get())) || (rc = upload_globals(ld, m.get())))
@@ -481,7 +506,7 @@ extern "C" int mio_hip_llm_load(mio_hip_device *d, const char *path, int n_ctx, 
     MIO_REQUIRE(m->stager->finish() && hipDeviceSynchronize() == hipSuccess, MIO_ERR_HIP,
                 "llm_load: device synchronize failed");
     m->stager.reset();
-    m->step = mio::StepCtx{m->dims, m->layers.data(), m->kc, m->vc, m->out_norm, m->lm, m->tok};
+    m->step = mio::StepCtx{m->dims, m->layers.data(), m->kc, m->vc, m->out_norm, m->lm, m->tok, m->q8};
     // the decode-step graphs are captured here, as llama_init_from_model reserves its compute
     // graphs at context creation: the first generate replays them instead of capturing
     if ((rc = ensure_graph(m.get()))) return rc;

@@ -44,6 +44,10 @@ struct mio_hip_llm {
     mio::QMat tok{}, lm{};
     float *out_norm = nullptr;
     _Float16 *kc = nullptr, *vc = nullptr;
+    // the cache type (GGML_F16, or GGML_Q8_0: mio_hip_llm_load_kv) and, for Q8_0, the planes that
+    // stand in for kc / vc (which stay null): this handle's, and the batch engine's below
+    int kv_type = mio::GGML_F16;
+    mio::KvQ8 q8{};
     // what every launch_step_kernel of this model gets (built once, at the end of the load)
     mio::StepCtx step{};
     const mio::StepCtx &ctx() const { return step; }
@@ -55,6 +59,7 @@ struct mio_hip_llm {
     struct Batch {
         int B = 0;
         _Float16 *kc = nullptr, *vc = nullptr;  // [B][layer][kv head][n_ctx][hd]
+        mio::KvQ8 q8{};                         // the same rows of a Q8_0 cache
         mio::StepState *st = nullptr;
         mio::SampleCfg *cfg = nullptr;
         float *logits = nullptr, *smp = nullptr;

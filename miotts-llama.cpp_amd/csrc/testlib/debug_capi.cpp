@@ -195,6 +195,17 @@ extern "C" int mio_hip_llm_set_kv_rows(mio_hip_llm *m, int il, int p0, int n_pos
     return mio::llm_set_kv_rows(m, il, p0, n_pos, k, v);
 }
 
+extern "C" int mio_hip_llm_kv_rows_q8(mio_hip_llm *m, int slot, int il, int n_pos, int8_t *kq, uint16_t *ks,
+                                      int8_t *vq, uint16_t *vs) {
+    return mio::llm_kv_rows_q8(m, false, slot, il, 0, n_pos, kq, ks, vq, vs);
+}
+
+extern "C" int mio_hip_llm_set_kv_rows_q8(mio_hip_llm *m, int slot, int il, int p0, int n_pos, const int8_t *kq,
+                                          const uint16_t *ks, const int8_t *vq, const uint16_t *vs) {
+    return mio::llm_kv_rows_q8(m, true, slot, il, p0, n_pos, const_cast<int8_t *>(kq), const_cast<uint16_t *>(ks),
+                               const_cast<int8_t *>(vq), const_cast<uint16_t *>(vs));
+}
+
 extern "C" int mio_hip_llm_debug_attention(mio_hip_llm *m, int il, int pos, int which, const float *qkv,
                                            float *att) {
     return mio::llm_debug_attention(m, il, pos, which, qkv, att);

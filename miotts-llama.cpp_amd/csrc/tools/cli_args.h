@@ -27,6 +27,8 @@ struct CliArgs {
     // the on-device sampler chain (TestToSpeech::Options; neutral by default)
     int top_k = 0, repeat_last_n = 64;
     float top_p = 1.0f, min_p = 0.0f, repeat_penalty = 1.0f, frequency_penalty = 0.0f, presence_penalty = 0.0f;
+    // llama.cpp's -ctk / -ctv: the LLM's KV cache type, f16 or q8_0, one type for both (empty: not given)
+    std::string cache_type_k, cache_type_v;
 };
 
 // The whole of v as a number (std::stof / std::stoi alone accept "0.9x"); throws as they do.
@@ -93,6 +95,10 @@ inline std::vector<CliFlag> cli_common_flags() {
          [](CliArgs &a, const std::string &v) { a.frequency_penalty = cli_float(v); }},
         {{"--presence-penalty"}, true, "Subtracted once from a recently sampled id (default: 0 = off)",
          [](CliArgs &a, const std::string &v) { a.presence_penalty = cli_float(v); }},
+        {{"-ctk", "--cache-type-k"}, true, "KV cache type for K: f16 or q8_0 (default: f16; -ctv must match)",
+         [](CliArgs &a, const std::string &v) { a.cache_type_k = v; }},
+        {{"-ctv", "--cache-type-v"}, true, "KV cache type for V: f16 or q8_0 (default: f16; -ctk must match)",
+         [](CliArgs &a, const std::string &v) { a.cache_type_v = v; }},
     };
 }
 
@@ -149,10 +155,18 @@ inline std::string cli_check(const CliArgs &a, bool path_words = false) {
     if (!(a.repeat_penalty > 0.0f)) return "--repeat-penalty must be > 0";
     if (a.sample_rate < 0) return "--sample-rate must be a rate in Hz";
     if (a.repeat_last_n < 0 || a.repeat_last_n > 256) return "--repeat-last-n must be in 0..256";
+    for (const std::string &t : {a.cache_type_k, a.cache_type_v})
+        if (!t.empty() && t != "f16" && t != "q8_0") return "cache type '" + t + "' is not supported (f16, q8_0)";
+    if (!a.cache_type_k.empty() && !a.cache_type_v.empty() && a.cache_type_k != a.cache_type_v)
+        return "--cache-type-k and --cache-type-v must be equal";
     return "";
 }
 
+// Also sets the runner's policy switch MIO_KV_TYPE from -ctk / -ctv (TestToSpeech::Config has no
+// field for it: its size is ABI), so every CLI has it set before it constructs its TestToSpeech.
 inline TestToSpeech::Config cli_config(const CliArgs &a) {
+    const std::string &kv = a.cache_type_k.empty() ? a.cache_type_v : a.cache_type_k;
+    if (!kv.empty()) setenv("MIO_KV_TYPE", kv.c_str(), 1);
     TestToSpeech::Config c;
     c.model_path = a.model_path;
     c.codec_path = a.codec_path;

@@ -141,6 +141,8 @@ def _declare(L: ctypes.CDLL) -> None:
         "mio_synth_llm_gguf_shape": (c_int, [ctypes.c_char_p, c_int, c_int, ctypes.c_uint64, c_int, c_int, c_int,
                                              c_int, c_int]),
         "mio_hip_llm_load": (c_int, [_vp, ctypes.c_char_p, c_int, ctypes.POINTER(_vp)]),
+        "mio_hip_llm_load_kv": (c_int, [_vp, ctypes.c_char_p, c_int, c_int, ctypes.POINTER(_vp)]),
+        "mio_hip_llm_kv_type": (c_int, [_vp, ctypes.POINTER(c_int)]),
         "mio_hip_llm_free": (None, [_vp]),
         "mio_normalize_tts_text": (c_int, [ctypes.c_char_p, _vp, c_int, ctypes.POINTER(c_int)]),
         "mio_parse_speech_tokens": (c_int, [ctypes.c_char_p, _vp, c_int, ctypes.POINTER(c_int)]),
@@ -167,6 +169,8 @@ def _declare(L: ctypes.CDLL) -> None:
         "mio_hip_llm_eval_layers": (c_int, [_vp, ctypes.c_int32, c_int, _vp, _vp]),
         "mio_hip_llm_kv_rows": (c_int, [_vp, c_int, c_int, _vp, _vp]),
         "mio_hip_llm_set_kv_rows": (c_int, [_vp, c_int, c_int, c_int, _vp, _vp]),
+        "mio_hip_llm_kv_rows_q8": (c_int, [_vp, c_int, c_int, c_int, _vp, _vp, _vp, _vp]),
+        "mio_hip_llm_set_kv_rows_q8": (c_int, [_vp, c_int, c_int, c_int, c_int, _vp, _vp, _vp, _vp]),
         "mio_hip_llm_debug_attention": (c_int, [_vp, c_int, c_int, c_int, _vp, _vp]),
         "mio_hip_llm_handoff_words": (c_int, [_vp, c_int, _vp]),
         "mio_hip_llm_batch_state": (c_int, [_vp, ctypes.POINTER(c_int), _vp, _vp, _vp, _vp]),
@@ -683,10 +687,15 @@ def synth_llm_shape(path: str, preset: int, qtype: int, seed: int = 1, n_embd: i
 class Llm:
     """HIP LLM decode (mirror of the llama.cpp calls in test-to-speech.cpp:44-196)."""
 
-    def __init__(self, dev: Device, path: str, n_ctx: int = 2048):
+    def __init__(self, dev: Device, path: str, n_ctx: int = 2048, kv_type: int = None):
+        """kv_type: the KV cache type, 1 (F16) or 8 (Q8_0: mio_hip_llm_load_kv); None follows the
+        policy switch MIO_KV_TYPE (f16 by default)."""
         self.dev = dev
         h = _vp()
-        check(lib().mio_hip_llm_load(dev.h, path.encode(), n_ctx, ctypes.byref(h)))
+        if kv_type is None:
+            check(lib().mio_hip_llm_load(dev.h, path.encode(), n_ctx, ctypes.byref(h)))
+        else:
+            check(lib().mio_hip_llm_load_kv(dev.h, path.encode(), n_ctx, kv_type, ctypes.byref(h)))
         self.h = h
         info = np.zeros(8, np.int32)
         check(lib().mio_hip_llm_info(h, info.ctypes.data_as(_i32p)))
@@ -703,6 +712,12 @@ class Llm:
             self.close()
         except Exception:
             pass
+
+    def kv_type(self) -> int:
+        """The handle's KV cache type: 1 (F16) or 8 (Q8_0)."""
+        v = ctypes.c_int(0)
+        check(lib().mio_hip_llm_kv_type(self.h, ctypes.byref(v)))
+        return v.value
 
     def weight_bytes(self) -> int:
         b = ctypes.c_uint64(0)
@@ -799,6 +814,25 @@ class Llm:
         v = np.ascontiguousarray(v, np.float16)
         assert k.shape == v.shape and k.ndim == 3 and k.shape[0] == self.n_kv and k.shape[2] == self.head_dim, k.shape
         check(lib().mio_hip_llm_set_kv_rows(self.h, il, p0, k.shape[1], _ptr(k), _ptr(v)))
+
+    def kv_rows_q8(self, il: int, n_pos: int, slot: int = -1):
+        """Rows [0, n_pos) of layer il of a Q8_0 cache (slot -1: the handle's own, else a batch
+        slot's): (K codes, K scales, V codes, V scales), codes int8 [n_kv, n_pos, head_dim], scales
+        float16 [n_kv, n_pos, head_dim / 32] (test-support library)."""
+        kq = np.empty((self.n_kv, n_pos, self.head_dim), np.int8)
+        ks = np.empty((self.n_kv, n_pos, self.head_dim // 32), np.float16)
+        vq, vs = np.empty_like(kq), np.empty_like(ks)
+        check(lib().mio_hip_llm_kv_rows_q8(self.h, slot, il, n_pos, _ptr(kq), _ptr(ks), _ptr(vq), _ptr(vs)))
+        return kq, ks, vq, vs
+
+    def set_kv_rows_q8(self, il: int, p0: int, kq, ks, vq, vs, slot: int = -1) -> None:
+        """The inverse of kv_rows_q8: rows [p0, p0 + n_pos) of layer il."""
+        kq, vq = np.ascontiguousarray(kq, np.int8), np.ascontiguousarray(vq, np.int8)
+        ks, vs = np.ascontiguousarray(ks, np.float16), np.ascontiguousarray(vs, np.float16)
+        assert kq.shape == vq.shape == (self.n_kv, kq.shape[1], self.head_dim), kq.shape
+        assert ks.shape == vs.shape == (self.n_kv, kq.shape[1], self.head_dim // 32), ks.shape
+        check(lib().mio_hip_llm_set_kv_rows_q8(self.h, slot, il, p0, kq.shape[1], _ptr(kq), _ptr(ks), _ptr(vq),
+                                               _ptr(vs)))
 
     def debug_attention(self, il: int, pos: int, which: int, qkv: np.ndarray) -> np.ndarray:
         """One attention launch (which 1: attention, 10: attention + O) of layer il at position
@@ -1022,6 +1056,20 @@ def dequantize_rows(qtype: int, rows_bytes: np.ndarray, k: int) -> np.ndarray:
     out = np.empty((rows_bytes.shape[0], k), np.float32)
     check(lib().mio_dequantize_rows(qtype, _ptr(rows_bytes), rows_bytes.shape[0], k, _ptr(out)))
     return out
+
+
+def kv_q8_0(x: np.ndarray):
+    """K / V rows x [..., k] (k a multiple of 32; f16-exact values) as a Q8_0 KV cache holds them, by
+    the host's Q8_0 row quantizer (ggml's quantize_row_q8_0_ref): (codes int8 [..., k], scales
+    float16 [..., k / 32], the float16 values [..., k] attention consumes: f16(float(d) * q), round
+    to nearest even)."""
+    x = np.ascontiguousarray(x, np.float32)
+    k = x.shape[-1]
+    raw = quantize_rows(8, x.reshape(-1, k)).reshape(-1, k // 32, 34)
+    scales = np.ascontiguousarray(raw[:, :, :2]).view(np.float16).reshape(x.shape[:-1] + (k // 32,))
+    codes = np.ascontiguousarray(raw[:, :, 2:]).view(np.int8).reshape(x.shape)
+    deq = dequantize_rows(8, raw.reshape(-1, k // 32 * 34), k).astype(np.float16).reshape(x.shape)
+    return codes, scales, deq
 
 
 def to_split(qtype: int, rows_bytes: np.ndarray, k: int):
