@@ -129,6 +129,36 @@ int mio_hip_pcm_finish_rate(mio_hip_resampler *h, const float *samples, int64_t 
                             float *out_f32, int16_t *out_pcm16, int64_t out_cap, int64_t *n_out,
                             float *peak, void *stream);
 
+/* ---------------- speaking rate: WSOLA time-scale modification ----------------
+ * The same voice and pitch, faster or slower, on f32 PCM x[0 .. n) (x = 0 outside), before peak
+ * normalisation and the output rate. speed s in [0.5, 2.0]; N = 1024, Hs = 512, D = 512; the window
+ * is the periodic Hann w[i] = 0.5 - 0.5 cos(2 pi i / N), designed in float64 and rounded to f32
+ * (w[i] + w[i + Hs] = 1).
+ *   n_out = ceil(n / (double)s), F = ceil(n_out / Hs) + 1 frames; frame m covers outputs
+ *   [(m - 1) Hs, (m + 1) Hs) and nominally starts at input p_m = floor((m - 1) Hs (double)s + 0.5).
+ *   offsets: d_0 = 0, a_m = p_m + d_m. For m >= 1 the template is the natural continuation of the
+ *   previous frame, t[i] = x[a_{m-1} + Hs + i], and the score of a lag d in [-D, D) is
+ *     c(d) = sum_{i < N} t[i] x[p_m + d + i] / sqrt(sum_{i < N} x[p_m + d + i]^2 + 1e-12),
+ *   both sums accumulated in f32 in the order i = 0 .. N - 1. d_m is the lag of the largest score;
+ *   of equal scores the smallest |d|, then the smaller d (all-zero audio: 0).
+ *   output: y[j] = sum_m w[j - (m - 1) Hs] x[a_m + j - (m - 1) Hs], 0 <= j < n_out; exactly two
+ *   frames (q = j / Hs and q + 1, r = j mod Hs) reach each sample, and the kernel forms it as
+ *   fma(w[r + Hs], x1 - x2, x2) with x1 = x[a_q + Hs + r], x2 = x[a_{q+1} + r].
+ * At s = 1, by Cauchy-Schwarz, every d_m = 0 and y = x bit for bit.
+ * in[b], out[b] (room for out_cap[b] floats) and offsets[b] (room for F int32; offsets, or an entry
+ * of it, may be NULL) are device pointers, 1 <= B <= 16 utterances of n[b] <= 2^30 samples in one
+ * call: one persistent workgroup per utterance walks its frames, then one overlap-add launch covers
+ * the batch. n_out[b] (host) receives each length. A speed outside [0.5, 2] or a NaN is
+ * MIO_ERR_UNSUPPORTED with the value in the message; out_cap[b] < n_out[b] is MIO_ERR_INVALID,
+ * before anything runs. Queued on `stream`; does not wait. The workspace (the window and 16 rows of
+ * offsets) belongs to the device and is allocated by the first call or by
+ * mio_hip_pcm_speed_reserve (for utterances of up to n_max samples at any speed); a call inside
+ * that size allocates nothing. A device's calls go to one stream. */
+int mio_hip_pcm_speed_reserve(mio_hip_device *d, int64_t n_max);
+int mio_hip_pcm_speed(mio_hip_device *d, const float *const *in, const int64_t *n, int B, float speed,
+                      float *const *out, const int64_t *out_cap, int64_t *n_out,
+                      int32_t *const *offsets, void *stream);
+
 /* ---------------- iSTFT ----------------
  * Replaces istft_cache(n_fft, win_length) (istft.h:6-30, istft.cpp:7-32) and
  * istft(spec, n_frames, hop, cache) (istft.h:38-42, istft.cpp:68-108).

@@ -108,6 +108,15 @@ public:
     bool is_ready() const;
     int sample_rate() const;
 
+    // (extension) speaking rate: the same voice and pitch, `speed` times as fast (0.5 .. 2.0;
+    // default 1 = as generated), by WSOLA time-scale modification on the device between the iSTFT
+    // and peak normalisation (mio_hip.h "speaking rate"). Applies to synthesize_to_file,
+    // synthesize_to_vector and synthesize_batch_to_files from the next call on; the streaming
+    // entry points refuse to run while the speed is not 1. false (and no change) for a value
+    // outside the range, a NaN, or an instance without a device.
+    bool set_speed(float speed);
+    float speed() const;
+
     bool synthesize_to_file(const VoiceModel & voice,
                             const std::string & text,
                             const std::string & output_path,

@@ -76,6 +76,7 @@ extern "C" void mio_hip_device_close(mio_hip_device *d) {
         hipStreamSynchronize(d->stream);
         hipStreamDestroy(d->stream);
     }
+    if (d->speed_ws) hipFree(d->speed_ws);
     delete d;
 }
 

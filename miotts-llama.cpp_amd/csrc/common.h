@@ -54,6 +54,10 @@ struct mio_hip_device {
     int dev = 0;
     hipStream_t stream = nullptr;
     int n_cu = 0;
+    // mio_hip_pcm_speed's workspace (csrc/capi/speed_capi.cpp): the window, then 16 rows of
+    // speed_frames offsets; allocated by the first call or mio_hip_pcm_speed_reserve
+    void *speed_ws = nullptr;
+    long long speed_frames = 0;
 };
 
 namespace mio {

@@ -234,6 +234,13 @@ struct TestToSpeech::Impl {
     int out_rate = 0;
     void *d_rs_in = nullptr, *d_rs_out = nullptr;
     size_t rs_in_cap = 0, rs_out_cap = 0;
+    // set_speed: the speaking rate (1 = nothing is launched) and the buffers the time-scaled
+    // floats go to: one for a single utterance, one per utterance of a batch group
+    float speed = 1.0f;
+    void *d_sp = nullptr;
+    size_t sp_cap = 0;
+    std::vector<void *> d_spb;
+    std::vector<size_t> spb_cap;
 
     // PCM of the last decode in HBM (f32) and its PCM16 image (synthesize_to_file)
     void *d_pcm = nullptr, *d_pcm16 = nullptr;
@@ -249,6 +256,9 @@ struct TestToSpeech::Impl {
         if (rs) mio_hip_resampler_destroy(rs);
         if (dev && d_rs_in) mio_hip_free(dev, d_rs_in);
         if (dev && d_rs_out) mio_hip_free(dev, d_rs_out);
+        if (dev && d_sp) mio_hip_free(dev, d_sp);
+        for (void *p : d_spb)
+            if (dev && p) mio_hip_free(dev, p);
         if (llm) mio_hip_llm_free(llm);
         if (dev && d_pcm) mio_hip_free(dev, d_pcm);
         if (dev && d_pcm16) mio_hip_free(dev, d_pcm16);
@@ -322,6 +332,30 @@ struct TestToSpeech::Impl {
         return true;
     }
 
+    // samples after the speaking rate for n before it (ceil(n / s), mio_hip.h "speaking rate")
+    size_t sped_samples(size_t n) const { return (size_t)std::ceil((double)n / (double)speed); }
+
+    // the speaking rate on B utterances of len[b] device floats at src[b], as ONE
+    // mio_hip_pcm_speed call: src[b] / len[b] become the time-scaled floats (in dst[b], grown as
+    // needed). At speed 1 nothing is launched and nothing changes.
+    bool apply_speed(const float **src, int *len, int B, void **dst, size_t *dst_cap) {
+        if (speed == 1.0f) return true;
+        std::vector<int64_t> n((size_t)B), cap((size_t)B), got((size_t)B);
+        std::vector<float *> out((size_t)B);
+        for (int b = 0; b < B; ++b) {
+            n[b] = len[b], cap[b] = (int64_t)sped_samples((size_t)len[b]);
+            if (!ensure(dst[b], dst_cap[b], (size_t)cap[b] * sizeof(float) + 64)) return false;
+            out[b] = (float *)dst[b];
+        }
+        if (mio_hip_pcm_speed(dev, src, n.data(), B, speed, out.data(), cap.data(), got.data(), nullptr, nullptr) !=
+            MIO_OK) {
+            fprintf(stderr, "TestToSpeech: speaking rate failed: %s\n", mio_hip_last_error());
+            return false;
+        }
+        for (int b = 0; b < B; ++b) src[b] = out[b], len[b] = (int)got[b];
+        return true;
+    }
+
     // samples at the output rate for n at the codec's (ceil(n L / M), mio_hip.h "output rate")
     size_t out_samples(size_t n) const {
         int info[5] = {1, 1, 0, 0, 0};
@@ -390,12 +424,15 @@ struct TestToSpeech::Impl {
             }
             return true;
         }
+        // the speaking rate first, on the iSTFT's floats (speed 1: d_pcm itself, nothing launched)
+        const float *src = (const float *)d_pcm;
+        if (!apply_speed(&src, &len, 1, &d_sp, &sp_cap)) return false;
         if (rs && !native_rate) {  // at the output rate: the gain (peak of the native-rate signal) fused into the resampler
             const size_t cap = out_samples((size_t)len);
             int64_t got = 0;
             if (!ensure(d_rs_out, rs_out_cap, cap * sizeof(float) + 64)) return false;
             pcm.resize(cap);
-            if (mio_hip_pcm_finish_rate(rs, (const float *)d_pcm, len, normalize ? 1 : 0, (float *)d_rs_out, nullptr,
+            if (mio_hip_pcm_finish_rate(rs, src, len, normalize ? 1 : 0, (float *)d_rs_out, nullptr,
                                         (int64_t)cap, &got, nullptr, nullptr) != MIO_OK ||
                 (got && mio_hip_memcpy_d2h(dev, pcm.data(), d_rs_out, (size_t)got * sizeof(float)) != MIO_OK)) {
                 fprintf(stderr, "TestToSpeech: PCM epilogue failed: %s\n", mio_hip_last_error());
@@ -403,12 +440,12 @@ struct TestToSpeech::Impl {
             }
             return true;
         }
-        if (normalize && mio_hip_pcm_normalize(dev, (const float *)d_pcm, len, (float *)d_pcm, nullptr, nullptr)) {
+        if (normalize && mio_hip_pcm_normalize(dev, src, len, const_cast<float *>(src), nullptr, nullptr)) {
             fprintf(stderr, "TestToSpeech: peak normalisation failed: %s\n", mio_hip_last_error());
             return false;
         }
         pcm.resize(len);
-        if (len && mio_hip_memcpy_d2h(dev, pcm.data(), d_pcm, (size_t)len * sizeof(float)) != MIO_OK) {
+        if (len && mio_hip_memcpy_d2h(dev, pcm.data(), src, (size_t)len * sizeof(float)) != MIO_OK) {
             fprintf(stderr, "TestToSpeech: PCM copy failed: %s\n", mio_hip_last_error());
             return false;
         }
@@ -493,6 +530,27 @@ TestToSpeech::~TestToSpeech() = default;
 bool TestToSpeech::is_ready() const { return impl_ && impl_->codec != nullptr; }
 int TestToSpeech::sample_rate() const { return impl_ ? impl_->out_rate : 0; }
 
+// The kernel workspace and the single-utterance buffer are sized here, for max_tokens codes at
+// the slowest speed, so that a synthesis at the new speed allocates nothing.
+bool TestToSpeech::set_speed(float speed) {
+    if (!impl_ || !impl_->dev || !(speed >= 0.5f && speed <= 2.0f)) {
+        fprintf(stderr, "TestToSpeech: speed %g is not supported (0.5 to 2.0)\n", (double)speed);
+        return false;
+    }
+    Impl &I = *impl_;
+    if (speed != 1.0f && I.spt > 0) {
+        const size_t n = (size_t)(config_.max_tokens > 0 ? config_.max_tokens : 700) * I.spt;
+        if (mio_hip_pcm_speed_reserve(I.dev, (int64_t)n) != MIO_OK ||
+            !I.ensure(I.d_sp, I.sp_cap, 2 * n * sizeof(float) + 64)) {
+            fprintf(stderr, "TestToSpeech: speaking-rate buffers failed: %s\n", mio_hip_last_error());
+            return false;
+        }
+    }
+    I.speed = speed;
+    return true;
+}
+float TestToSpeech::speed() const { return impl_ ? impl_->speed : 1.0f; }
+
 bool TestToSpeech::generate_token_text(const std::string &text, const Options &options, std::string &out) {
     out.clear();
     if (options.skip_llm) {
@@ -569,8 +627,10 @@ bool TestToSpeech::synthesize_to_file(const VoiceModel &voice, const std::string
     Impl &I = *impl_;
     int len = 0;
     std::vector<int16_t> pcm16;
+    const float *src = nullptr;
     if (!I.decode_codes_dev(voice, codes, &len, nullptr, nullptr) ||
-        !I.finish_pcm16((const float *)I.d_pcm, len, options.apply_peak_normalization, pcm16))
+        !(src = (const float *)I.d_pcm, I.apply_speed(&src, &len, 1, &I.d_sp, &I.sp_cap)) ||
+        !I.finish_pcm16(src, len, options.apply_peak_normalization, pcm16))
         return false;
     return mio::wav_write_pcm16(output_path, pcm16.data(), pcm16.size(), sample_rate());
 }
@@ -694,9 +754,14 @@ bool TestToSpeech::batch_to_files(const VoiceModel *voices, bool per_utterance, 
             fprintf(stderr, "TestToSpeech: codec decode failed: %s\n", mio_hip_last_error());
             return false;
         }
+        // the speaking rate on the whole group as one call (speed 1: nothing)
+        std::vector<const float *> fp(op.begin(), op.end());
+        I.d_spb.resize(std::max(I.d_spb.size(), (size_t)B), nullptr);
+        I.spb_cap.resize(I.d_spb.size(), 0);
+        if (!I.apply_speed(fp.data(), len.data(), B, I.d_spb.data(), I.spb_cap.data())) return false;
         for (int b = 0; b < B; ++b) {
             std::vector<int16_t> pcm16;
-            if (!I.finish_pcm16(op[b], len[b], options.apply_peak_normalization, pcm16)) return false;
+            if (!I.finish_pcm16(fp[b], len[b], options.apply_peak_normalization, pcm16)) return false;
             if (!mio::wav_write_pcm16(output_paths[g0 + b], pcm16.data(), pcm16.size(), sample_rate())) return false;
         }
     }
@@ -726,6 +791,11 @@ bool TestToSpeech::synthesize_stream_profiled(const VoiceModel &voice, const std
     profile = StreamProfile{};
     const auto t0 = clk::now();
     if (!callback || !is_ready()) return false;
+    if (impl_->speed != 1.0f) {  // streamed emission of time-scaled audio is not built
+        fprintf(stderr, "TestToSpeech: streaming at speed %g is not supported (set_speed(1) to stream)\n",
+                (double)impl_->speed);
+        return false;
+    }
     if (chunk_samples == 0) chunk_samples = 4096;
     Impl &I = *impl_;
     const int sr = I.sample_rate;

@@ -22,6 +22,7 @@ struct CliArgs {
     float temperature = 0.8f;
     int max_tokens = 700, n_threads = 4, n_gpu_layers = 0, device = -1;
     int sample_rate = 0;  // --sample-rate: TestToSpeech::Config::output_sample_rate (0 = the codec's)
+    float speed = 1.0f;   // --speed: TestToSpeech::set_speed (1 = as generated)
     size_t chunk_samples = 4096;
     bool skip_llm = false, dump_tensors = false, speech_only = false, ignore_eos = false;
     // the on-device sampler chain (TestToSpeech::Options; neutral by default)
@@ -75,6 +76,9 @@ inline std::vector<CliFlag> cli_common_flags() {
         {{"--sample-rate"}, true,
          "Output rate in Hz: 8000, 16000, 22050, 24000, 32000 or 48000 (default: the codec's own, 44100)",
          [](CliArgs &a, const std::string &v) { a.sample_rate = cli_int(v); }},
+        {{"--speed"}, true,
+         "Speaking rate, 0.5 to 2.0: same voice and pitch, faster or slower (default: 1; streaming tools: 1 only)",
+         [](CliArgs &a, const std::string &v) { a.speed = cli_float(v); }},
         {{"--skip-llm"}, false, "Treat --prompt as raw <|s_N|> token text",
          [](CliArgs &a, const std::string &) { a.skip_llm = true; }},
         {{"--speech-only"}, false, "Benchmark harness: sample only the <|s_N|> speech ids",
@@ -143,7 +147,8 @@ inline bool cli_parse(int argc, char **argv, const std::vector<CliFlag> &flags, 
 // the reference tools' required-argument checks; returns an error text or empty.
 // path_words: main.cpp:109-121 says "--codec path is required" where the examples
 // (stream-benchmark.cpp:93-105, stream-compare.cpp:174-186) say "--codec is required".
-inline std::string cli_check(const CliArgs &a, bool path_words = false) {
+// streams: the tool emits through the streaming entry points, which run at speed 1 only.
+inline std::string cli_check(const CliArgs &a, bool path_words = false, bool streams = false) {
     const std::string p = path_words ? " path" : "";
     if (a.prompt.empty()) return "--prompt is required";
     if (a.codec_path.empty()) return "--codec" + p + " is required";
@@ -154,6 +159,8 @@ inline std::string cli_check(const CliArgs &a, bool path_words = false) {
         if (v != v) return "a sampling option is NaN";
     if (!(a.repeat_penalty > 0.0f)) return "--repeat-penalty must be > 0";
     if (a.sample_rate < 0) return "--sample-rate must be a rate in Hz";
+    if (!(a.speed >= 0.5f && a.speed <= 2.0f)) return "--speed must be in 0.5..2.0";
+    if (streams && a.speed != 1.0f) return "--speed other than 1 is not supported by the streaming tools";
     if (a.repeat_last_n < 0 || a.repeat_last_n > 256) return "--repeat-last-n must be in 0..256";
     for (const std::string &t : {a.cache_type_k, a.cache_type_v})
         if (!t.empty() && t != "f16" && t != "q8_0") return "cache type '" + t + "' is not supported (f16, q8_0)";

@@ -31,7 +31,7 @@ int main(int argc, char **argv) {
         cli_usage(argv[0], what, flags);
         return 1;
     }
-    const std::string err = cli_check(a);
+    const std::string err = cli_check(a, false, true);
     if (!err.empty()) {
         std::fprintf(stderr, "Error: %s\n", err.c_str());
         return 1;

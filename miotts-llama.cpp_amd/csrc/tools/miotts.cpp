@@ -41,6 +41,10 @@ static int run_batch(const CliArgs &a, const std::vector<std::string> &lines,
             rc[(size_t)g] = 1;
             return;
         }
+        if (a.speed != 1.0f && !tts.set_speed(a.speed)) {
+            rc[(size_t)g] = 1;
+            return;
+        }
         // one voice for the shard, or (--voices) the voice of every line of it
         std::vector<VoiceModel> voices(voice_paths.empty() ? 1 : texts.size());
         for (size_t j = 0; j < voices.size(); ++j) {
@@ -145,6 +149,7 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "Error: failed to initialize TestToSpeech\n");
         return 1;
     }
+    if (a.speed != 1.0f && !tts.set_speed(a.speed)) return 1;
     VoiceModel voice;
     if (!voice.load_from_file(a.voice_path)) {
         std::fprintf(stderr, "Error: failed to load voice model: %s\n", a.voice_path.c_str());

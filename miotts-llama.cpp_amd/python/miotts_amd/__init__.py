@@ -7,6 +7,7 @@ visible, every call raises (the driver checks that native code is what ran).
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 from typing import Optional
 
@@ -118,6 +119,8 @@ def _declare(L: ctypes.CDLL) -> None:
                                      ctypes.POINTER(ctypes.c_int64), c_int, _vp]),
         "mio_hip_pcm_finish_rate": (c_int, [_vp, _vp, ctypes.c_int64, c_int, _vp, _vp, ctypes.c_int64,
                                             ctypes.POINTER(ctypes.c_int64), _f32p, _vp]),
+        "mio_hip_pcm_speed_reserve": (c_int, [_vp, ctypes.c_int64]),
+        "mio_hip_pcm_speed": (c_int, [_vp, _vp, _vp, c_int, ctypes.c_float, _vp, _vp, _vp, _vp, _vp]),
         "mio_hip_istft_create": (c_int, [_vp, c_int, c_int, ctypes.POINTER(_vp)]),
         "mio_hip_istft_destroy": (None, [_vp]),
         "mio_hip_istft_out_len": (c_int, [_vp, c_int, c_int, ctypes.POINTER(c_int)]),
@@ -355,6 +358,25 @@ def pcm_finish(dev: "Device", samples: "DeviceArray", n: int, normalize: bool,
     check(lib().mio_hip_pcm_finish(dev.h, samples.ptr if n else None, n, 1 if normalize else 0,
                                    out.ptr if n else None, ctypes.byref(peak), None))
     return out.numpy()[:n], peak.value
+
+
+def pcm_speed(dev: "Device", arrays, speed: float):
+    """Speaking rate by WSOLA (mio_hip_pcm_speed, include/mio_hip.h "speaking rate") on a batch of
+    1..16 host float32 arrays, as one call: (outputs, offsets), per utterance its ceil(n / speed)
+    float32 samples and the int32 offset of each of its ceil(n_out / 512) + 1 frames."""
+    xs = [np.ascontiguousarray(x, np.float32) for x in arrays]
+    B, s = len(xs), float(np.float32(speed))
+    n_out = [int(math.ceil(x.size / s)) if 0.5 <= s <= 2.0 else 0 for x in xs]
+    frames = [-(-n // 512) + 1 for n in n_out]
+    d_in = [dev.upload(x if x.size else np.zeros(1, np.float32)) for x in xs]
+    d_out = [dev.empty((max(n, 1),), np.float32) for n in n_out]
+    d_off = [dev.empty((f,), np.int32) for f in frames]
+    i64 = ctypes.c_int64 * max(B, 1)
+    ptrs = lambda a: (_vp * max(B, 1))(*[d.ptr for d in a])
+    got = i64()
+    check(lib().mio_hip_pcm_speed(dev.h, ptrs(d_in), i64(*[x.size for x in xs]), B, speed, ptrs(d_out),
+                                  i64(*n_out), got, ptrs(d_off), None))
+    return ([d.numpy()[: got[b]] for b, d in enumerate(d_out)], [d.numpy() for d in d_off])
 
 
 class Resampler:
