@@ -159,6 +159,37 @@ int mio_hip_pcm_speed(mio_hip_device *d, const float *const *in, const int64_t *
                       float *const *out, const int64_t *out_cap, int64_t *n_out,
                       int32_t *const *offsets, void *stream);
 
+/* ---------------- pitch: time-scale, then an arbitrary-ratio sinc resampler ----------------
+ * The same words in the same time, `semitones` higher or lower (-12 .. 12), optionally at a
+ * speaking rate `speed`, on f32 PCM before peak normalisation and the output rate. With
+ * r = (float)exp2(semitones / 12.0) and s1 = speed / r (f32): WSOLA at s1 (mio_hip_pcm_speed
+ * above; skipped when s1 == 1), then the resampler at input step r (skipped when r == 1, where the
+ * call is mio_hip_pcm_speed's, bit for bit). Pitch and formants move together: this is
+ * resampling, not PSOLA, and is meant for a few semitones.
+ * The resampler, on x[0 .. n) (x = 0 outside), n_out = ceil(n / (double)r):
+ *   t_j = (double)j (double)r (one rounded product), i_j = floor(t_j), f_j = t_j - i_j;
+ *   c = min(1, 1 / r) in f32 (shifting up low-passes at the new Nyquist); K = ceil(Z / c);
+ *   y[j] = c sum_{k = -K + 1 .. K} x[i_j + k] h(c (k - f_j)), accumulated as one f32 FMA chain in
+ *   ascending k and multiplied by c at the end; 2 K taps, 32 at r <= 1, 64 at r = 2.
+ *   h: the Kaiser-windowed sinc sinc(u) I0(beta sqrt(1 - (u / Z)^2)) / I0(beta), Z = 16 zero
+ *   crossings a side, beta = 0.1102 (80 - 8.7) = 7.857, tabulated in float64 at Q = 512 points per
+ *   zero crossing (Z Q + 1 entries, rounded to f32). With p = |c (k - f_j)| Q formed in float64,
+ *   h = T[floor p] + (p - floor p) (T[floor p + 1] - T[floor p]) (an f32 FMA) for p < Z Q, else 0.
+ * in[b] and out[b] (room for out_cap[b] floats) are device pointers, 1 <= B <= 16 utterances of
+ * n[b] <= 2^30 samples in one call; the resampler is one launch for the batch. n_out[b] (host)
+ * receives the length after both steps, ceil(ceil(n / (double)s1) / (double)r) (the inner ceil
+ * only when s1 != 1). semitones outside [-12, 12] or NaN, or s1 outside [0.5, 2] or NaN, is
+ * MIO_ERR_UNSUPPORTED with the value in the message; out_cap[b] < n_out[b] is MIO_ERR_INVALID,
+ * before anything runs. Queued on `stream`; does not wait. The workspace (the table and the
+ * time-scaled intermediate) belongs to the device and is allocated by the first call or by
+ * mio_hip_pcm_pitch_reserve (for calls whose utterances total up to n_max samples, at any s1;
+ * it reserves mio_hip_pcm_speed's too); a call inside that size allocates nothing. A device's
+ * calls go to one stream. */
+int mio_hip_pcm_pitch_reserve(mio_hip_device *d, int64_t n_max);
+int mio_hip_pcm_pitch(mio_hip_device *d, const float *const *in, const int64_t *n, int B, float speed,
+                      float semitones, float *const *out, const int64_t *out_cap, int64_t *n_out,
+                      void *stream);
+
 /* ---------------- iSTFT ----------------
  * Replaces istft_cache(n_fft, win_length) (istft.h:6-30, istft.cpp:7-32) and
  * istft(spec, n_frames, hop, cache) (istft.h:38-42, istft.cpp:68-108).

@@ -117,6 +117,18 @@ public:
     bool set_speed(float speed);
     float speed() const;
 
+    // (extension) pitch: the same words in the same time, `semitones` higher or lower (-12 .. 12;
+    // default 0 = as generated): WSOLA at speed / 2^(semitones / 12), then an arbitrary-ratio sinc
+    // resampler, on the device between the iSTFT and peak normalisation (mio_hip.h "pitch").
+    // Formants move with the pitch, so it is meant for a few semitones. Same contract as
+    // set_speed: applies to synthesize_to_file, synthesize_to_vector and synthesize_batch_to_files
+    // from the next call on; the streaming entry points refuse to run while the pitch is not 0.
+    // false (and no change) for a value outside the range, a NaN, an instance without a device,
+    // or a combination with the current speed whose time-scale speed / 2^(semitones / 12) leaves
+    // 0.5 .. 2.0 (set_speed refuses such a combination likewise).
+    bool set_pitch(float semitones);
+    float pitch() const;
+
     bool synthesize_to_file(const VoiceModel & voice,
                             const std::string & text,
                             const std::string & output_path,

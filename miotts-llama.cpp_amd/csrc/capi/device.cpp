@@ -77,6 +77,7 @@ extern "C" void mio_hip_device_close(mio_hip_device *d) {
         hipStreamDestroy(d->stream);
     }
     if (d->speed_ws) hipFree(d->speed_ws);
+    if (d->pitch_ws) hipFree(d->pitch_ws);
     delete d;
 }
 

@@ -58,6 +58,10 @@ struct mio_hip_device {
     // speed_frames offsets; allocated by the first call or mio_hip_pcm_speed_reserve
     void *speed_ws = nullptr;
     long long speed_frames = 0;
+    // mio_hip_pcm_pitch's workspace (csrc/capi/pitch_capi.cpp): the prototype table, then
+    // pitch_floats of time-scaled intermediate; allocated by the first call or mio_hip_pcm_pitch_reserve
+    void *pitch_ws = nullptr;
+    long long pitch_floats = 0;
 };
 
 namespace mio {

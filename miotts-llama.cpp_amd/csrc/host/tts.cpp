@@ -237,6 +237,7 @@ struct TestToSpeech::Impl {
     // set_speed: the speaking rate (1 = nothing is launched) and the buffers the time-scaled
     // floats go to: one for a single utterance, one per utterance of a batch group
     float speed = 1.0f;
+    float pitch = 0.0f;  // set_pitch: semitones (0 = the resampler is not launched)
     void *d_sp = nullptr;
     size_t sp_cap = 0;
     std::vector<void *> d_spb;
@@ -332,14 +333,27 @@ struct TestToSpeech::Impl {
         return true;
     }
 
-    // samples after the speaking rate for n before it (ceil(n / s), mio_hip.h "speaking rate")
-    size_t sped_samples(size_t n) const { return (size_t)std::ceil((double)n / (double)speed); }
+    // the two ratios of mio_hip.h "pitch": the resampler's step r and the time-scale s1 = speed / r
+    static float pitch_ratio(float semitones) { return (float)std::exp2((double)semitones / 12.0); }
+    static bool scale_ok(float speed, float semitones) {
+        const float s1 = speed / pitch_ratio(semitones);
+        return s1 >= 0.5f && s1 <= 2.0f;
+    }
 
-    // the speaking rate on B utterances of len[b] device floats at src[b], as ONE
-    // mio_hip_pcm_speed call: src[b] / len[b] become the time-scaled floats (in dst[b], grown as
-    // needed). At speed 1 nothing is launched and nothing changes.
+    // samples after the speaking rate and the pitch for n before them: ceil(n / s) (mio_hip.h
+    // "speaking rate"), or with a pitch ceil(ceil(n / s1) / r) (mio_hip.h "pitch")
+    size_t sped_samples(size_t n) const {
+        if (pitch == 0.0f) return (size_t)std::ceil((double)n / (double)speed);
+        const float r = pitch_ratio(pitch), s1 = speed / r;
+        const double mid = s1 != 1.0f ? std::ceil((double)n / (double)s1) : (double)n;
+        return (size_t)std::ceil(mid / (double)r);
+    }
+
+    // the speaking rate and the pitch on B utterances of len[b] device floats at src[b], as ONE
+    // mio_hip_pcm_speed (pitch 0) or mio_hip_pcm_pitch call: src[b] / len[b] become the new floats
+    // (in dst[b], grown as needed). At speed 1 and pitch 0 nothing is launched and nothing changes.
     bool apply_speed(const float **src, int *len, int B, void **dst, size_t *dst_cap) {
-        if (speed == 1.0f) return true;
+        if (speed == 1.0f && pitch == 0.0f) return true;
         std::vector<int64_t> n((size_t)B), cap((size_t)B), got((size_t)B);
         std::vector<float *> out((size_t)B);
         for (int b = 0; b < B; ++b) {
@@ -347,9 +361,12 @@ struct TestToSpeech::Impl {
             if (!ensure(dst[b], dst_cap[b], (size_t)cap[b] * sizeof(float) + 64)) return false;
             out[b] = (float *)dst[b];
         }
-        if (mio_hip_pcm_speed(dev, src, n.data(), B, speed, out.data(), cap.data(), got.data(), nullptr, nullptr) !=
-            MIO_OK) {
-            fprintf(stderr, "TestToSpeech: speaking rate failed: %s\n", mio_hip_last_error());
+        const int rc = pitch == 0.0f ? mio_hip_pcm_speed(dev, src, n.data(), B, speed, out.data(), cap.data(),
+                                                         got.data(), nullptr, nullptr)
+                                     : mio_hip_pcm_pitch(dev, src, n.data(), B, speed, pitch, out.data(), cap.data(),
+                                                         got.data(), nullptr);
+        if (rc != MIO_OK) {
+            fprintf(stderr, "TestToSpeech: speaking rate / pitch failed: %s\n", mio_hip_last_error());
             return false;
         }
         for (int b = 0; b < B; ++b) src[b] = out[b], len[b] = (int)got[b];
@@ -538,6 +555,11 @@ bool TestToSpeech::set_speed(float speed) {
         return false;
     }
     Impl &I = *impl_;
+    if (!Impl::scale_ok(speed, I.pitch)) {
+        fprintf(stderr, "TestToSpeech: speed %g is not supported at a pitch of %g semitones\n", (double)speed,
+                (double)I.pitch);
+        return false;
+    }
     if (speed != 1.0f && I.spt > 0) {
         const size_t n = (size_t)(config_.max_tokens > 0 ? config_.max_tokens : 700) * I.spt;
         if (mio_hip_pcm_speed_reserve(I.dev, (int64_t)n) != MIO_OK ||
@@ -550,6 +572,29 @@ bool TestToSpeech::set_speed(float speed) {
     return true;
 }
 float TestToSpeech::speed() const { return impl_ ? impl_->speed : 1.0f; }
+
+// As set_speed: the workspace (table, intermediate, WSOLA's own) and the single-utterance buffer
+// are sized here for max_tokens codes, so that a synthesis at the new pitch allocates nothing.
+bool TestToSpeech::set_pitch(float semitones) {
+    if (!impl_ || !impl_->dev || !(semitones >= -12.0f && semitones <= 12.0f) ||
+        !Impl::scale_ok(impl_->speed, semitones)) {
+        fprintf(stderr, "TestToSpeech: a pitch of %g semitones is not supported (-12 to 12, and speed / 2^(pitch / 12) "
+                        "in 0.5 to 2.0)\n", (double)semitones);
+        return false;
+    }
+    Impl &I = *impl_;
+    if (semitones != 0.0f && I.spt > 0) {
+        const size_t n = (size_t)(config_.max_tokens > 0 ? config_.max_tokens : 700) * I.spt;
+        if (mio_hip_pcm_pitch_reserve(I.dev, (int64_t)n) != MIO_OK ||
+            !I.ensure(I.d_sp, I.sp_cap, 2 * n * sizeof(float) + 64)) {
+            fprintf(stderr, "TestToSpeech: pitch buffers failed: %s\n", mio_hip_last_error());
+            return false;
+        }
+    }
+    I.pitch = semitones;
+    return true;
+}
+float TestToSpeech::pitch() const { return impl_ ? impl_->pitch : 0.0f; }
 
 bool TestToSpeech::generate_token_text(const std::string &text, const Options &options, std::string &out) {
     out.clear();
@@ -794,6 +839,11 @@ bool TestToSpeech::synthesize_stream_profiled(const VoiceModel &voice, const std
     if (impl_->speed != 1.0f) {  // streamed emission of time-scaled audio is not built
         fprintf(stderr, "TestToSpeech: streaming at speed %g is not supported (set_speed(1) to stream)\n",
                 (double)impl_->speed);
+        return false;
+    }
+    if (impl_->pitch != 0.0f) {
+        fprintf(stderr, "TestToSpeech: streaming at a pitch of %g semitones is not supported (set_pitch(0) to stream)\n",
+                (double)impl_->pitch);
         return false;
     }
     if (chunk_samples == 0) chunk_samples = 4096;

@@ -23,6 +23,7 @@ struct CliArgs {
     int max_tokens = 700, n_threads = 4, n_gpu_layers = 0, device = -1;
     int sample_rate = 0;  // --sample-rate: TestToSpeech::Config::output_sample_rate (0 = the codec's)
     float speed = 1.0f;   // --speed: TestToSpeech::set_speed (1 = as generated)
+    float pitch = 0.0f;   // --pitch: TestToSpeech::set_pitch, semitones (0 = as generated)
     size_t chunk_samples = 4096;
     bool skip_llm = false, dump_tensors = false, speech_only = false, ignore_eos = false;
     // the on-device sampler chain (TestToSpeech::Options; neutral by default)
@@ -79,6 +80,9 @@ inline std::vector<CliFlag> cli_common_flags() {
         {{"--speed"}, true,
          "Speaking rate, 0.5 to 2.0: same voice and pitch, faster or slower (default: 1; streaming tools: 1 only)",
          [](CliArgs &a, const std::string &v) { a.speed = cli_float(v); }},
+        {{"--pitch"}, true,
+         "Pitch in semitones, -12 to 12: same words and duration, higher or lower (default: 0; streaming tools: 0 only)",
+         [](CliArgs &a, const std::string &v) { a.pitch = cli_float(v); }},
         {{"--skip-llm"}, false, "Treat --prompt as raw <|s_N|> token text",
          [](CliArgs &a, const std::string &) { a.skip_llm = true; }},
         {{"--speech-only"}, false, "Benchmark harness: sample only the <|s_N|> speech ids",
@@ -161,6 +165,8 @@ inline std::string cli_check(const CliArgs &a, bool path_words = false, bool str
     if (a.sample_rate < 0) return "--sample-rate must be a rate in Hz";
     if (!(a.speed >= 0.5f && a.speed <= 2.0f)) return "--speed must be in 0.5..2.0";
     if (streams && a.speed != 1.0f) return "--speed other than 1 is not supported by the streaming tools";
+    if (!(a.pitch >= -12.0f && a.pitch <= 12.0f)) return "--pitch must be in -12..12";
+    if (streams && a.pitch != 0.0f) return "--pitch other than 0 is not supported by the streaming tools";
     if (a.repeat_last_n < 0 || a.repeat_last_n > 256) return "--repeat-last-n must be in 0..256";
     for (const std::string &t : {a.cache_type_k, a.cache_type_v})
         if (!t.empty() && t != "f16" && t != "q8_0") return "cache type '" + t + "' is not supported (f16, q8_0)";

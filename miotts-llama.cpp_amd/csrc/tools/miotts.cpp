@@ -41,7 +41,7 @@ static int run_batch(const CliArgs &a, const std::vector<std::string> &lines,
             rc[(size_t)g] = 1;
             return;
         }
-        if (a.speed != 1.0f && !tts.set_speed(a.speed)) {
+        if ((a.speed != 1.0f && !tts.set_speed(a.speed)) || (a.pitch != 0.0f && !tts.set_pitch(a.pitch))) {
             rc[(size_t)g] = 1;
             return;
         }
@@ -150,6 +150,7 @@ int main(int argc, char **argv) {
         return 1;
     }
     if (a.speed != 1.0f && !tts.set_speed(a.speed)) return 1;
+    if (a.pitch != 0.0f && !tts.set_pitch(a.pitch)) return 1;
     VoiceModel voice;
     if (!voice.load_from_file(a.voice_path)) {
         std::fprintf(stderr, "Error: failed to load voice model: %s\n", a.voice_path.c_str());

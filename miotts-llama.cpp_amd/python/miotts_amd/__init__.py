@@ -121,6 +121,8 @@ def _declare(L: ctypes.CDLL) -> None:
                                             ctypes.POINTER(ctypes.c_int64), _f32p, _vp]),
         "mio_hip_pcm_speed_reserve": (c_int, [_vp, ctypes.c_int64]),
         "mio_hip_pcm_speed": (c_int, [_vp, _vp, _vp, c_int, ctypes.c_float, _vp, _vp, _vp, _vp, _vp]),
+        "mio_hip_pcm_pitch_reserve": (c_int, [_vp, ctypes.c_int64]),
+        "mio_hip_pcm_pitch": (c_int, [_vp, _vp, _vp, c_int, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _vp]),
         "mio_hip_istft_create": (c_int, [_vp, c_int, c_int, ctypes.POINTER(_vp)]),
         "mio_hip_istft_destroy": (None, [_vp]),
         "mio_hip_istft_out_len": (c_int, [_vp, c_int, c_int, ctypes.POINTER(c_int)]),
@@ -377,6 +379,31 @@ def pcm_speed(dev: "Device", arrays, speed: float):
     check(lib().mio_hip_pcm_speed(dev.h, ptrs(d_in), i64(*[x.size for x in xs]), B, speed, ptrs(d_out),
                                   i64(*n_out), got, ptrs(d_off), None))
     return ([d.numpy()[: got[b]] for b, d in enumerate(d_out)], [d.numpy() for d in d_off])
+
+
+PITCH_TILE = 2048  # outputs of one tile of the pitch resampler (PT_TILE, csrc/hip/pcm_pitch.h)
+
+
+def pitch_ratio(semitones: float) -> float:
+    """The resampler's input step of mio_hip_pcm_pitch: (float)exp2(semitones / 12.0)."""
+    return float(np.float32(np.exp2(np.float64(semitones) / 12.0)))
+
+
+def pcm_pitch(dev: "Device", arrays, semitones: float, speed: float = 1.0):
+    """Pitch (mio_hip_pcm_pitch, include/mio_hip.h "pitch") on a batch of 1..16 host float32 arrays,
+    as one call: WSOLA at speed / r, then the sinc resampler at step r = pitch_ratio(semitones).
+    Returns the outputs, per utterance its ceil(ceil(n / s1) / r) float32 samples."""
+    xs = [np.ascontiguousarray(x, np.float32) for x in arrays]
+    B, s = len(xs), float(np.float32(speed))
+    cap = [int(x.size / s) + 4 if 0.25 <= s <= 4.0 else 4 for x in xs]  # n_out is ceil(n / s) or one more
+    d_in = [dev.upload(x if x.size else np.zeros(1, np.float32)) for x in xs]
+    d_out = [dev.empty((c,), np.float32) for c in cap]
+    i64 = ctypes.c_int64 * max(B, 1)
+    ptrs = lambda a: (_vp * max(B, 1))(*[d.ptr for d in a])
+    got = i64()
+    check(lib().mio_hip_pcm_pitch(dev.h, ptrs(d_in), i64(*[x.size for x in xs]), B, speed, semitones, ptrs(d_out),
+                                  i64(*cap), got, None))
+    return [d.numpy()[: got[b]] for b, d in enumerate(d_out)]
 
 
 class Resampler:
